@@ -2,6 +2,13 @@
 """Benchmark of the REVS ADMM hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--homes H] [--T 24] [--mode pdhg]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, walks the spin-up and the warm-up, times exactly K steps, writes the state
+those steps computed when --dump-outputs is given, and prints the headline line.  `--full` adds
+everything else this file measures (the other regimes and sizes, the dense-product comparison, the
+matrix-core roofline, the run to the eps-residual, time to eps from fresh engines, the transient as
+one call, the CPU baseline) to the same line.
 
 N > 1: one rank per GPU, the library's own RCCL communicator (bootstrapped over torch.distributed).
 Either the driver starts the ranks,
@@ -30,18 +37,22 @@ iterations are judged by the tree form of R p in one launch (on a second stream 
 than a block), a failed verdict is rolled back through the four rotating sets of state buffers,
 and the max diff of every iteration -- the convergence test -- is folded on the device into the
 records the host reads.  The transient's cost, the binding regime (folded chain), binary
-residences and the 125 000 x 96 shape of BASELINE config 4 are measured in the same run and
+residences and the 125 000 x 96 shape of BASELINE config 4 are measured in the same run with --full and
 reported as first-class fields beside the headline.
 
 Prints ONE JSON line (rank 0).  `value` = home-QP solves per second, whole job, inputs resident
-in HBM, from the MEDIAN of `--bursts` (15) timed regions of exactly `--steps` iterations each (every one
-bracketed by barrier + synchronize; all listed in `bursts_ms_per_step`); `value_ev_only` counts the residences
-with an EV alone (adoption is stated in config.workload); `value_kkt_presolve`: the same regime with
-revs_pdhg_t::polish = 3 (KKT steps from the carried multiplier before PDHG, which then is not entered);
-`value_feeder_121144`: the reference's own feeder, 15 iterations, on/off chargers, the oracle timed beside it;
+in HBM, from one timed region of exactly `--steps` iterations bracketed by barrier + synchronize
+(`--bursts B` repeats it B times and takes the MEDIAN, all listed in `bursts_ms_per_step`);
+`--dump-outputs DIR`: the state the timed steps leave, as AdmmEngine.get_state() returns it
+(DIR/p_est.npy, p_sch.npy, gamma.npy; float32, the caller's residence order).
+From the same timed region: `value_ev_only` counts the residences
+with an EV alone (adoption is stated in config.workload);
 `collective` (N > 1): the block all-reduce's duration beside its block of sweeps.  `roofline`: the sweep kernel against HBM -- algorithmic bytes per launch / average
 launch duration from two HIP events around the timed region on its stream / sweep launches in it;
-`roofline_valu`: the same kernel against VALU issue (what bounds it since round 3);
+`roofline_valu`: the same kernel against VALU issue (what bounds it since round 3).
+With --full: `breakdown` (transient, residuals, iterations to eps); `value_kkt_presolve`: the same regime with
+revs_pdhg_t::polish = 3 (KKT steps from the carried multiplier before PDHG, which then is not entered);
+`value_feeder_121144`: the reference's own feeder, 15 iterations, on/off chargers, the oracle timed beside it;
 `roofline_binding`: the binding regime's launches; `roofline_matvec`: the f64 matrix-core product
 R p (feeders that are not radial); `roofline_125k_T96`: config 4's per-GPU shape from the committed PMC passes; `cpu_baseline`: the oracle's vectorised home QP over all
 residences on this box's cores (one process per core) plus the operator's voltage product, same
@@ -274,6 +285,37 @@ def feeder_121144(torch, with_cpu):
     return out
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(eng, directory, world, rank):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the ADMM state
+    (P_est, P_sch, G) as AdmmEngine.get_state() returns it, every rank's residences in the workload's
+    order -- as float32 DIR/p_est.npy, p_sch.npy, gamma.npy.  Above DUMP_LIMIT_BYTES in all, a fixed
+    sample of residences (seed 0, the same for every build) is written, its indices in DIR/rows.npy."""
+    names = ("p_est", "p_sch", "gamma")
+    state = [np.ascontiguousarray(a, np.float32) for a in eng.get_state()]
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, state)
+        state = [np.concatenate([p[i] for p in parts]) for i in range(len(names))]
+    if rank != 0:
+        return
+    n = state[0].shape[0]
+    row_bytes = sum(a[0].nbytes for a in state) if n else 0
+    rows = None
+    if n * row_bytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - 4096) // (row_bytes + 8)        # (4096: the .npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        state = [a[rows] for a in state]
+    os.makedirs(directory, exist_ok=True)
+    for name, a in zip(names, state):
+        np.save(os.path.join(directory, name + ".npy"), a)
+    if rows is not None:
+        np.save(os.path.join(directory, "rows.npy"), rows.astype(np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks of this script (this
     process has made no GPU call and makes none), relay rank 0's stdout, exit with the first
@@ -338,13 +380,12 @@ def main():
                          "(rehearsal of N > 1 on a one-GPU box)")
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--bursts", type=int, default=None,
+    ap.add_argument("--bursts", type=int, default=1,
                     help="the timed region -- exactly --steps steps between two barriers -- is repeated this many "
                          "times back to back; ms_per_step / value are the MEDIAN burst, every burst is listed "
-                         "(bursts_ms_per_step).  One burst of 20 steps is a 0.3 ms sample.  Default: 15, but no more "
-                         "than fit into ~400 iterations in all (2 at --steps 200): the run reaches the eps-residual "
-                         "near iteration 490 and drifts back to the voltage boundary -- another regime, reported as "
-                         "value_binding -- a few hundred iterations later")
+                         "(bursts_ms_per_step).  Default 1: the timed steps are exactly --steps.  Keep bursts x steps "
+                         "below ~400: the run reaches the eps-residual near iteration 490 and drifts back to the "
+                         "voltage boundary -- another regime, reported as value_binding -- a few hundred iterations later")
     ap.add_argument("--adoption", type=float, default=0.5,
                     help="share of residences with an EV (the others' home problem is trivial: p = 0)")
     ap.add_argument("--spinup", type=int, default=30,
@@ -384,10 +425,15 @@ def main():
                     help="sharded steady state: collective and verdicts on the compute stream")
     ap.add_argument("--no-converge", action="store_true",
                     help="skip the untimed run to the eps-residual (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they computed (AdmmEngine.get_state(): p_est, p_sch, "
+                         "gamma) as DIR/<name>.npy, float32, at most 64 MB in all (a fixed sample of residences beyond "
+                         "that, its indices in DIR/rows.npy)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: breakdown, the other regimes and sizes, the dense-product "
+                         "comparison, the matrix-core and binding / T = 96 rooflines, time to eps, the CPU baseline")
     args = ap.parse_args()
 
-    if args.bursts is None:
-        args.bursts = int(np.clip(400 // max(args.steps, 1), 1, 15))
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
         return spawn_ranks(args.gpus)        # before anything touches the GPU
 
@@ -510,8 +556,8 @@ def main():
     # The first launch of every kernel loads its code object (4 - 5 ms in all, once per process): a small throw-away
     # engine of the same shape walks through the transient and into the steady state first, so that the spin-up below
     # prices the iterations, not the loader (tools/transient_times.py: 8.5 ms for the first engine's 30 iterations, 3.5 ms
-    # for the second one's in the same process).
-    if world == 1 and not os.environ.get("REVS_BENCH_COLD"):
+    # for the second one's in the same process).  Only breakdown.transient (--full) reads those prices.
+    if args.full and world == 1 and not os.environ.get("REVS_BENCH_COLD"):
         args_homes = args.homes
         wq, eq, _ = build(min(args.homes, 4096), args.T, args.mode, args.stress, args.voltage, lanes_for=args.homes)
         for _ in range(14):
@@ -556,9 +602,160 @@ def main():
     kept = eng.spec_hist[0] - spec0[0]
     streamed = bool(eng._tree is not None and all(r[3] == args.steps for r in burst_rows))
     inner = eng.op_iters_hist[inner0:]
-    rp, rd, dmax, conv = eng.residuals(args.eps)
+    eng.check_status()          # (a residence without a solution, or a PDHG cap reached, fails the run)
     st = eng.status.cpu().numpy()
     pdhg_it = float((st >> 8).sum()) / max(1, int((w.homes[lo:hi]["ev"] != 0).sum())) if args.mode == "pdhg" else None
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, world, rank)
+    if rank == 0:
+        warm = (None if eng.pdhg_dual is None else
+                ("full" if eng.pdhg_dual.dim() == 2 else "scalar"))
+        rec = bool(getattr(eng, "recompute_pe_new", False))
+        inner = int(getattr(eng, "_inner", 1)) if eng._block else 1
+        if eng._block:
+            bph = multi_bytes_per_home(args.T, warm, hist=False, inner=inner)
+        else:
+            bph = agent_bytes_per_home(args.T, warm, fused=True, recompute=rec)
+        bytes_per_launch = bph * n_local
+        launch_ms = dt_ev / n_launch * 1e3 if streamed else None
+        ach = bytes_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms else None
+        traffic, traffic_src = None, None
+        tpath = os.path.join(ROOT, "profiles", "agent_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                if (tj.get("homes") == n_local and tj.get("T") == args.T
+                        and tj.get("mode") == args.mode
+                        and tj.get("algorithmic_bytes_per_launch") == bytes_per_launch):
+                    traffic, traffic_src = tj["hbm_bytes_per_launch"], tj.get("source")
+            except Exception:
+                traffic = None
+        out = {
+            "metric": "agent_qp_solves_per_sec",
+            "value": n_total * args.steps / dt,
+            "unit": "solves/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3,
+            "bursts": len(burst_rows),
+            "bursts_ms_per_step": bursts_ms,
+            "ms_per_step_rule": "median of `bursts` timed regions of exactly `steps` steps each (barrier + synchronize "
+                                "on both sides of every one), run back to back; value = residences / that",
+            "higher_is_better": True,
+            "scaling": args.scaling,
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {
+                "workload": f"synthetic {n_local} homes/GPU x T={args.T} ("
+                            + (f"weak scaling: {args.homes} per GPU" if args.scaling == "weak" else
+                               f"strong scaling: {n_total} in total over {world} GPU(s), BASELINE config 2's shape")
+                            + f") box+SOC home QP, EV adoption {args.adoption:g} (the other residences' "
+                            "problem is p = 0: value_ev_only counts the EV residences alone), "
+                            f"{args.nodes}-node radial feeder, one ADMM iteration per step (voltage "
+                            "rows of the operator's estimate + all home QPs + dual update + "
+                            f"residual terms), timed from a state {args.spinup + args.warmup} ADMM "
+                            "iterations into the run; with --full the transient before it is in "
+                            "breakdown.transient, the binding / binary / 125k x 96 regimes in "
+                            "value_binding / value_binary / value_125k_T96",
+                "homes_per_gpu": n_local, "homes_total": n_total, "T": args.T,
+                "nodes": args.nodes, "home_solver": args.mode, "kappa": w.kappa,
+                "lanes_per_residence": int(eng.pdhg.lanes) or "default (8 x 3 slots at T = 24)",
+                "adoption": args.adoption, "ev_residences_total": int((w.homes["ev"] != 0).sum()),
+                "operator_dtype": "f64", "parallelism": f"homes sharded x{world}, nodes replicated, "
+                                                        "node sums all-reduced"
+                + (f", {eng._block} iterations per collective"
+                   + (" on a second stream" if eng.op.stream_overlap else "") if eng._block else
+                   ", one collective per iteration"),
+                "voltage_rows": ("tree form of R p inside the sweep's launch" if streamed else
+                                 "dense f64 product R p on the matrix cores"),
+                "launches_per_step": (n_launch / args.steps) if streamed else 2,
+                "iterations_per_sweep_launch": inner if streamed else 1,
+                "iterations_per_timed_launch": (args.steps / n_launch) if streamed else 1,
+                "recompute_pe_new": rec,
+                "collective": (None if world == 1 and group is None else
+                               ("hook communicator over gloo, all ranks on cuda:0 (rehearsal)" if args.share_gpu
+                                else "library-owned RCCL communicator" if eng._comm else "torch.distributed")),
+                "launcher": ("bench.py spawned the ranks itself" if os.environ.get("REVS_BENCH_CHILD")
+                             else "external (torch.distributed.run)" if world > 1 else "single process"),
+                "clock_warmup_products": args.clock_warm,
+            },
+            # N > 1: the all-reduce of a block's node sums (events around it on the stream it is issued on) beside that
+            # block's sweep launches: the collective costs the step nothing while it is the shorter of the two
+            "collective": (None if not getattr(timed_steps, "collective", None) else
+                           {"collective_ms_per_block": timed_steps.collective[0],
+                            "block_sweeps_ms": timed_steps.collective[1],
+                            "iterations_in_that_block": timed_steps.collective[2],
+                            "bytes": int(timed_steps.collective[2]) * (eng.M * args.T + 64 * world) * 8,
+                            "bytes_per_iteration": (eng.M * args.T + 64 * world) * 8,
+                            # (a T-double screen of the ranks' row maxima in front of it was evaluated on 8 logical shards
+                            # of this workload and dropped: profiles/r05_screen_bound.txt)
+                            "screened": False,
+                            "hidden": bool(eng.op.stream_overlap and timed_steps.collective[0] < timed_steps.collective[1])}),
+            "roofline": {
+                "kernel": ("agent_step_kernel<MULTI> (%d ADMM iterations of every residence per launch: home QP "
+                           "sweeps + dual updates + next operator home passes, state in registers; voltage "
+                           "rows judged by blocks of %d iterations in their own launch)" % (inner, eng._block)
+                           if streamed and eng._block else
+                           "agent_step_kernel (home QP sweep + dual update + next operator home pass"
+                           + (" + voltage rows of T slots in its first T workgroups)" if streamed else ")")),
+                "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": ach / HBM_PEAK_GBS if ach else None,
+                # PMC counters are collected in separate rocprofv3 passes of this command and
+                # committed under profiles/; NOT measured inside this run
+                "traffic": traffic, "traffic_source": traffic_src,
+                "bytes_per_home": bph, "bytes_per_launch": bytes_per_launch,
+                # (the timed launches carry steps / n_launch iterations each: 20 in the driver's run)
+                "bytes_per_home_per_iteration": bph / max(args.steps / n_launch, 1.0),
+                "sweep_launches_timed": n_launch,
+                # two HIP events around the timed region on the launches' stream / number of sweep
+                # launches in it: the launch duration INCLUDING the inter-kernel boundaries and the
+                # block verdict launches that share the stream (rocprofv3's kernel time is shorter)
+                "avg_launch_ms": launch_ms,
+                "frac_of_achievable_copy_rate": (ach / 6290.0) if ach else None,   # 6.29 TB/s: float4 copy
+                "pdhg_iters_mean": pdhg_it,
+            },
+            # the same timed region counted on the residences that have a QP to solve
+            "value_ev_only": float((w.homes["ev"] != 0).sum()) * args.steps / dt,
+        }
+        # VALU issue: the multi-iteration sweep is bound by instruction issue, not by HBM (its bytes per
+        # ADMM iteration are 1/8 of the one-iteration sweep's).  Instructions per launch from the committed
+        # SQ counter pass (profiles/agent_traffic.json, same workload), duration live (avg_launch_ms).
+        # Peak: VALU_PEAK above (one wave64 VALU instruction per 2 cycles per SIMD; profiles/r05_probe_valu_rate.txt).
+        valu = None
+        try:
+            tj = json.load(open(tpath))
+            c = tj.get("sq_counters_per_launch", {})
+            if (tj.get("homes") == n_local and tj.get("T") == args.T and tj.get("mode") == args.mode
+                    and tj.get("iterations_per_launch") == inner and c.get("SQ_INSTS_VALU") and launch_ms):
+                peak = VALU_PEAK
+                # (the counters are per launch of `inner` iterations; the timed launches carry
+                # steps / n_launch of them each -- 20 in the driver's run)
+                it_launch = args.steps / n_launch
+                ach_v = c["SQ_INSTS_VALU"] * (it_launch / inner) / (launch_ms * 1e-3)
+                valu = {"kernel": "agent_step_kernel<MULTI>", "bound": "valu-issue", "achieved": ach_v / 1e9,
+                        "peak": peak / 1e9, "peak_source": VALU_PEAK_SOURCE,
+                        "unit": "G wave64 VALU instructions/s", "frac": ach_v / peak,
+                        "frac_of_measured_sustained_rate": ach_v / (1024 * 2.4e9 / VALU_CYCLES_SUSTAINED),
+                        "valu_instructions_per_launch": c["SQ_INSTS_VALU"] * (it_launch / inner),
+                        "iterations_per_timed_launch": it_launch,
+                        "valu_instructions_per_wavefront_and_iteration": c["SQ_INSTS_VALU"] / max(c.get("SQ_WAVES", 1), 1) / inner,
+                        "salu_instructions_per_launch": (c["SQ_INSTS_SALU"] * (it_launch / inner) if c.get("SQ_INSTS_SALU") else None),
+                        "valu_busy_share_of_launch": (c["SQ_ACTIVE_INST_VALU"] * (it_launch / inner) * SQ_QUAD / 1024 / (launch_ms * 1e-3 * 2.4e9)
+                                                      if c.get("SQ_ACTIVE_INST_VALU") else None),
+                        "source": tj.get("source")}
+        except Exception:
+            valu = None
+        out["roofline_valu"] = valu
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if group is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+    rp, rd, dmax, conv = eng.residuals(args.eps)
 
     # the same regime with the rows judged by the dense f64 product on the matrix cores (its own
     # launch before every sweep, verdict read by the host): what the tree form replaces.  (A short stretch: the
@@ -708,189 +905,49 @@ def main():
         one_call_ms = (time.perf_counter() - t1) * 1e3
 
     if rank == 0:
-        warm = (None if eng.pdhg_dual is None else
-                ("full" if eng.pdhg_dual.dim() == 2 else "scalar"))
-        rec = bool(getattr(eng, "recompute_pe_new", False))
-        inner = int(getattr(eng, "_inner", 1)) if eng._block else 1
-        if eng._block:
-            bph = multi_bytes_per_home(args.T, warm, hist=False, inner=inner)
-        else:
-            bph = agent_bytes_per_home(args.T, warm, fused=True, recompute=rec)
-        bytes_per_launch = bph * n_local
-        launch_ms = dt_ev / n_launch * 1e3 if streamed else None
-        ach = bytes_per_launch / (launch_ms * 1e-3) / 1e9 if launch_ms else None
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "agent_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if (tj.get("homes") == n_local and tj.get("T") == args.T
-                        and tj.get("mode") == args.mode
-                        and tj.get("algorithmic_bytes_per_launch") == bytes_per_launch):
-                    traffic, traffic_src = tj["hbm_bytes_per_launch"], tj.get("source")
-            except Exception:
-                traffic = None
-        out = {
-            "metric": "agent_qp_solves_per_sec",
-            "value": n_total * args.steps / dt,
-            "unit": "solves/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3,
-            "bursts": len(burst_rows),
-            "bursts_ms_per_step": bursts_ms,
-            "ms_per_step_rule": "median of `bursts` timed regions of exactly `steps` steps each (barrier + synchronize "
-                                "on both sides of every one), run back to back; value = residences / that",
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {
-                "workload": f"synthetic {n_local} homes/GPU x T={args.T} ("
-                            + (f"weak scaling: {args.homes} per GPU" if args.scaling == "weak" else
-                               f"strong scaling: {n_total} in total over {world} GPU(s), BASELINE config 2's shape")
-                            + f") box+SOC home QP, EV adoption {args.adoption:g} (the other residences' "
-                            "problem is p = 0: value_ev_only counts the EV residences alone), "
-                            f"{args.nodes}-node radial feeder, one ADMM iteration per step (voltage "
-                            "rows of the operator's estimate + all home QPs + dual update + "
-                            f"residual terms), timed from a state {args.spinup + args.warmup} ADMM "
-                            "iterations into the run; the transient before it is in "
-                            "breakdown.transient, the binding / binary / 125k x 96 regimes in "
-                            "value_binding / value_binary / value_125k_T96",
-                "homes_per_gpu": n_local, "homes_total": n_total, "T": args.T,
-                "nodes": args.nodes, "home_solver": args.mode, "kappa": w.kappa,
-                "lanes_per_residence": int(eng.pdhg.lanes) or "default (8 x 3 slots at T = 24)",
-                "adoption": args.adoption, "ev_residences_total": int((w.homes["ev"] != 0).sum()),
-                "operator_dtype": "f64", "parallelism": f"homes sharded x{world}, nodes replicated, "
-                                                        "node sums all-reduced"
-                + (f", {eng._block} iterations per collective"
-                   + (" on a second stream" if eng.op.stream_overlap else "") if eng._block else
-                   ", one collective per iteration"),
-                "voltage_rows": ("tree form of R p inside the sweep's launch" if streamed else
-                                 "dense f64 product R p on the matrix cores"),
-                "launches_per_step": (n_launch / args.steps) if streamed else 2,
-                "iterations_per_sweep_launch": inner if streamed else 1,
-                "iterations_per_timed_launch": (args.steps / n_launch) if streamed else 1,
-                "recompute_pe_new": rec,
-                "collective": (None if world == 1 and group is None else
-                               ("hook communicator over gloo, all ranks on cuda:0 (rehearsal)" if args.share_gpu
-                                else "library-owned RCCL communicator" if eng._comm else "torch.distributed")),
-                "launcher": ("bench.py spawned the ranks itself" if os.environ.get("REVS_BENCH_CHILD")
-                             else "external (torch.distributed.run)" if world > 1 else "single process"),
-                "clock_warmup_products": args.clock_warm,
-            },
-            # N > 1: the all-reduce of a block's node sums (events around it on the stream it is issued on) beside that
-            # block's sweep launches: the collective costs the step nothing while it is the shorter of the two
-            "collective": (None if not getattr(timed_steps, "collective", None) else
-                           {"collective_ms_per_block": timed_steps.collective[0],
-                            "block_sweeps_ms": timed_steps.collective[1],
-                            "iterations_in_that_block": timed_steps.collective[2],
-                            "bytes": int(timed_steps.collective[2]) * (eng.M * args.T + 64 * world) * 8,
-                            "bytes_per_iteration": (eng.M * args.T + 64 * world) * 8,
-                            # (a T-double screen of the ranks' row maxima in front of it was evaluated on 8 logical shards
-                            # of this workload and dropped: profiles/r05_screen_bound.txt)
-                            "screened": False,
-                            "hidden": bool(eng.op.stream_overlap and timed_steps.collective[0] < timed_steps.collective[1])}),
-            "roofline": {
-                "kernel": ("agent_step_kernel<MULTI> (%d ADMM iterations of every residence per launch: home QP "
-                           "sweeps + dual updates + next operator home passes, state in registers; voltage "
-                           "rows judged by blocks of %d iterations in their own launch)" % (inner, eng._block)
-                           if streamed and eng._block else
-                           "agent_step_kernel (home QP sweep + dual update + next operator home pass"
-                           + (" + voltage rows of T slots in its first T workgroups)" if streamed else ")")),
-                "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": ach / HBM_PEAK_GBS if ach else None,
-                # PMC counters are collected in separate rocprofv3 passes of this command and
-                # committed under profiles/; NOT measured inside this run
-                "traffic": traffic, "traffic_source": traffic_src,
-                "bytes_per_home": bph, "bytes_per_launch": bytes_per_launch,
-                # (the timed launches carry steps / n_launch iterations each: 20 in the driver's run)
-                "bytes_per_home_per_iteration": bph / max(args.steps / n_launch, 1.0),
-                "sweep_launches_timed": n_launch,
-                # two HIP events around the timed region on the launches' stream / number of sweep
-                # launches in it: the launch duration INCLUDING the inter-kernel boundaries and the
-                # block verdict launches that share the stream (rocprofv3's kernel time is shorter)
-                "avg_launch_ms": launch_ms,
-                "frac_of_achievable_copy_rate": (ach / 6290.0) if ach else None,   # 6.29 TB/s: float4 copy
-                "pdhg_iters_mean": pdhg_it,
-            },
-            "roofline_matvec": {
-                "kernel": "gemm_tn_kernel<double> (voltage rows R.p of the operator's Newton path, M x M x T)",
-                "bound": "mfma", "achieved": gemm_flops / (gemm_ms * 1e-3) / 1e12,
-                "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": gemm_flops / (gemm_ms * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS,
-                "avg_launch_ms": gemm_ms,
-                # 6 flop per byte of R at T = 24: the product streams the matrix
-                "matrix_stream_GBs": 8.0 * eng.M * eng.M / (gemm_ms * 1e-3) / 1e9,
-                "matrix_stream_frac_of_hbm_peak": 8.0 * eng.M * eng.M / (gemm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                "on_path": "since round 3 only for feeders given as a matrix, and in the Newton evaluations of "
-                           "feeders beyond the tree form's 2048 nodes: the steady state, the Newton evaluations and "
-                           "the binding chain judge their rows by the tree form of R p",
-                "mfma_counters": "profiles/r05_pmc_mfma.csv (rocprofv3 --pmc of tools/matvec_run.py: 131 072 v_mfma_f64_16x16x4 per launch, "
-                                 "SQ_VALU_MFMA_BUSY_CYCLES 8 388 608 = 8 192 per SIMD of the launch's ~32 000 cycles: 25 %; x 24/32 useful tile columns)",
-            },
-            # the same timed region counted on the residences that have a QP to solve
-            "value_ev_only": float((w.homes["ev"] != 0).sum()) * args.steps / dt,
-            "value_dense_product_path": dense,
-            "breakdown": {
-                "operator_inner_iters_mean": float(np.mean(inner)) if inner else 0.0,
-                "operator_path": eng.op_path_hist[-1],
-                "steady_state_steps_kept_discarded": [kept, eng.spec_hist[1] - spec0[1]],
-                "operator_voltage_rows": int(eng.M * args.T),
-                "admm_residual_primal": rp, "admm_residual_dual": rd, "admm_max_diff": dmax,
-                "admm_iters_to_eps": iters_to_eps, "eps": args.eps,
-                "admm_iters_to_eps_rule": "first of 8 consecutive iterations with max_h diff[h] <= eps, from the "
-                                          "records the streaming launches fold on the device",
-                # whole-run view: transient + steady iterations of a 400-iteration run
-                "amortized_400_iterations_solves_per_sec":
-                    (n_total * 400 / ((np.sum(spin_ms) + (400 - args.spinup) * dt / args.steps * 1e3)
-                                      * 1e-3)) if spin_ms and args.spinup <= 400 else None,
-                "transient": {
-                    "spinup_iterations": args.spinup,
-                    "ms_per_step_mean": float(np.mean(spin_ms)) if spin_ms else None,
-                    "ms_per_step_max": float(np.max(spin_ms)) if spin_ms else None,
-                    "ms_total": float(np.sum(spin_ms)) if spin_ms else None,
-                    "timed": "every iteration issued and waited for on its own (step + synchronize)",
-                    "one_call_ms_total": one_call_ms,
-                    "one_call_ms_per_step_mean": (one_call_ms / args.spinup) if one_call_ms is not None else None,
-                    "one_call": "the same iterations from iteration 0 again as ONE run_steps call (the iterations behind "
-                                "the transient stream)",
-                    "operator_inner_iters": spin_inner,
-                    "operator_paths": spin_paths,
-                },
+        out["roofline_matvec"] = {
+            "kernel": "gemm_tn_kernel<double> (voltage rows R.p of the operator's Newton path, M x M x T)",
+            "bound": "mfma", "achieved": gemm_flops / (gemm_ms * 1e-3) / 1e12,
+            "peak": F64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+            "frac": gemm_flops / (gemm_ms * 1e-3) / 1e12 / F64_MFMA_PEAK_TFLOPS,
+            "avg_launch_ms": gemm_ms,
+            # 6 flop per byte of R at T = 24: the product streams the matrix
+            "matrix_stream_GBs": 8.0 * eng.M * eng.M / (gemm_ms * 1e-3) / 1e9,
+            "matrix_stream_frac_of_hbm_peak": 8.0 * eng.M * eng.M / (gemm_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+            "on_path": "since round 3 only for feeders given as a matrix, and in the Newton evaluations of "
+                       "feeders beyond the tree form's 2048 nodes: the steady state, the Newton evaluations and "
+                       "the binding chain judge their rows by the tree form of R p",
+            "mfma_counters": "profiles/r05_pmc_mfma.csv (rocprofv3 --pmc of tools/matvec_run.py: 131 072 v_mfma_f64_16x16x4 per launch, "
+                             "SQ_VALU_MFMA_BUSY_CYCLES 8 388 608 = 8 192 per SIMD of the launch's ~32 000 cycles: 25 %; x 24/32 useful tile columns)",
+        }
+        out["value_dense_product_path"] = dense
+        out["breakdown"] = {
+            "operator_inner_iters_mean": float(np.mean(inner)) if inner else 0.0,
+            "operator_path": eng.op_path_hist[-1],
+            "steady_state_steps_kept_discarded": [kept, eng.spec_hist[1] - spec0[1]],
+            "operator_voltage_rows": int(eng.M * args.T),
+            "admm_residual_primal": rp, "admm_residual_dual": rd, "admm_max_diff": dmax,
+            "admm_iters_to_eps": iters_to_eps, "eps": args.eps,
+            "admm_iters_to_eps_rule": "first of 8 consecutive iterations with max_h diff[h] <= eps, from the "
+                                      "records the streaming launches fold on the device",
+            # whole-run view: transient + steady iterations of a 400-iteration run
+            "amortized_400_iterations_solves_per_sec":
+                (n_total * 400 / ((np.sum(spin_ms) + (400 - args.spinup) * dt / args.steps * 1e3)
+                                  * 1e-3)) if spin_ms and args.spinup <= 400 else None,
+            "transient": {
+                "spinup_iterations": args.spinup,
+                "ms_per_step_mean": float(np.mean(spin_ms)) if spin_ms else None,
+                "ms_per_step_max": float(np.max(spin_ms)) if spin_ms else None,
+                "ms_total": float(np.sum(spin_ms)) if spin_ms else None,
+                "timed": "every iteration issued and waited for on its own (step + synchronize)",
+                "one_call_ms_total": one_call_ms,
+                "one_call_ms_per_step_mean": (one_call_ms / args.spinup) if one_call_ms is not None else None,
+                "one_call": "the same iterations from iteration 0 again as ONE run_steps call (the iterations behind "
+                            "the transient stream)",
+                "operator_inner_iters": spin_inner,
+                "operator_paths": spin_paths,
             },
         }
-        # VALU issue: the multi-iteration sweep is bound by instruction issue, not by HBM (its bytes per
-        # ADMM iteration are 1/8 of the one-iteration sweep's).  Instructions per launch from the committed
-        # SQ counter pass (profiles/agent_traffic.json, same workload), duration live (avg_launch_ms).
-        # Peak: VALU_PEAK above (one wave64 VALU instruction per 2 cycles per SIMD; profiles/r05_probe_valu_rate.txt).
-        valu = None
-        try:
-            tj = json.load(open(tpath))
-            c = tj.get("sq_counters_per_launch", {})
-            if (tj.get("homes") == n_local and tj.get("T") == args.T and tj.get("mode") == args.mode
-                    and tj.get("iterations_per_launch") == inner and c.get("SQ_INSTS_VALU") and launch_ms):
-                peak = VALU_PEAK
-                # (the counters are per launch of `inner` iterations; the timed launches carry
-                # steps / n_launch of them each -- 20 in the driver's run)
-                it_launch = args.steps / n_launch
-                ach_v = c["SQ_INSTS_VALU"] * (it_launch / inner) / (launch_ms * 1e-3)
-                valu = {"kernel": "agent_step_kernel<MULTI>", "bound": "valu-issue", "achieved": ach_v / 1e9,
-                        "peak": peak / 1e9, "peak_source": VALU_PEAK_SOURCE,
-                        "unit": "G wave64 VALU instructions/s", "frac": ach_v / peak,
-                        "frac_of_measured_sustained_rate": ach_v / (1024 * 2.4e9 / VALU_CYCLES_SUSTAINED),
-                        "valu_instructions_per_launch": c["SQ_INSTS_VALU"] * (it_launch / inner),
-                        "iterations_per_timed_launch": it_launch,
-                        "valu_instructions_per_wavefront_and_iteration": c["SQ_INSTS_VALU"] / max(c.get("SQ_WAVES", 1), 1) / inner,
-                        "salu_instructions_per_launch": (c["SQ_INSTS_SALU"] * (it_launch / inner) if c.get("SQ_INSTS_SALU") else None),
-                        "valu_busy_share_of_launch": (c["SQ_ACTIVE_INST_VALU"] * (it_launch / inner) * SQ_QUAD / 1024 / (launch_ms * 1e-3 * 2.4e9)
-                                                      if c.get("SQ_ACTIVE_INST_VALU") else None),
-                        "source": tj.get("source")}
-        except Exception:
-            valu = None
-        out["roofline_valu"] = valu
         # the binding regime's launches (rocprofv3 kernel stats committed under profiles/, same command as
         # tools/regime_run.py): the folded chain's sweep against HBM, and the operator launch, which is a
         # latency chain of 2 T workgroups, not a bandwidth or arithmetic kernel

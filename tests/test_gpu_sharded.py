@@ -228,7 +228,7 @@ def test_bench_two_ranks_through_its_own_launcher(gpu_lib, transport):
         pytest.skip("needs two GPUs (the round-end test box has one)")
     bench = os.path.join(os.path.dirname(HERE), "bench.py")
     common = [sys.executable, bench, "--steps", "20", "--bursts", "3", "--homes", "20000", "--nodes", "512", "--scaling", "strong",
-              "--no-extras", "--no-cpu-baseline", "--no-converge", "--lanes", "0"]
+              "--full", "--no-extras", "--no-cpu-baseline", "--no-converge", "--lanes", "0"]
     env = dict(os.environ, OMP_NUM_THREADS="2", OPENBLAS_NUM_THREADS="2", MKL_NUM_THREADS="2")
     lines = []
     for extra in (["--gpus", "1"], ["--gpus", "2"] + (["--share-gpu"] if transport == "share-gpu" else [])):
@@ -244,3 +244,29 @@ def test_bench_two_ranks_through_its_own_launcher(gpu_lib, transport):
     c = two["collective"]
     assert c is not None and c["collective_ms_per_block"] > 0 and c["iterations_in_that_block"] == 20 and c["bytes"] == 20 * (512 * 24 + 128) * 8
     assert one["collective"] is None
+
+
+def test_bench_plain_line_and_dumped_state(gpu_lib, tmp_path):
+    """A plain `python bench.py` times exactly --steps steps and prints the headline alone; --dump-outputs writes the
+    state those steps left (AdmmEngine.get_state()); --full adds the rest of the line and computes the same state."""
+    bench = os.path.join(os.path.dirname(HERE), "bench.py")
+    common = [sys.executable, bench, "--gpus", "1", "--steps", "40", "--warmup", "3", "--homes", "20000", "--nodes", "512"]
+    env = dict(os.environ, OMP_NUM_THREADS="2", OPENBLAS_NUM_THREADS="2", MKL_NUM_THREADS="2")
+    lines = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-extras", "--no-cpu-baseline", "--no-converge"])):
+        r = subprocess.run(common + extra + ["--dump-outputs", str(tmp_path / tag)], capture_output=True, text=True,
+                           timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines[tag] = json.loads([ln for ln in r.stdout.splitlines() if ln.lstrip().startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 40 and plain["bursts"] == 1 and len(plain["bursts_ms_per_step"]) == 1
+    assert plain["value"] == pytest.approx(20000 * 1e3 / plain["ms_per_step"], rel=1e-9)
+    assert "breakdown" not in plain and "roofline_matvec" not in plain and "cpu_baseline" not in plain
+    assert "breakdown" in full and "roofline_matvec" in full and full["steps"] == 40
+    for name in ("p_est", "p_sch", "gamma"):
+        a, b = np.load(tmp_path / "plain" / f"{name}.npy"), np.load(tmp_path / "full" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (20000, 24) and np.isfinite(a).all(), name
+        np.testing.assert_allclose(a, b, rtol=1e-5, atol=1e-6, err_msg=name)
+    assert sorted(os.listdir(tmp_path / "plain")) == ["gamma.npy", "p_est.npy", "p_sch.npy"]

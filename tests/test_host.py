@@ -43,7 +43,7 @@ def test_compute_Rmat_matches_reference_formula(golden):
     assert np.abs(R - ro.compute_Rmat(fd)).max() < 1e-15
 
 
-def test_combine_result_roundtrip(golden):
+def test_combine_result_roundtrip(golden, tmp_path):
     """combine_result writes the reference's out/ text format: re-parse and compare
     with the stored distributed file's numbers."""
     import importlib.util, os
@@ -60,7 +60,7 @@ def test_combine_result_roundtrip(golden):
         "mk", os.path.join(os.path.dirname(__file__), "golden", "make_fixtures.py"))
     mk = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mk)
-    p = os.path.join(os.environ.get("TMPDIR", "/tmp"), "revs_combine.txt")
+    p = str(tmp_path / "revs_combine.txt")
     open(p, "w").write(txt)
     s = mk.read_result(p)
     assert list(s["Residence Usage Profile"]) == res

@@ -12,9 +12,9 @@ O=$R/gpurun_out/prof_$TAG
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 if [[ $PART == *A* ]]; then
-python3 $R/bench.py > $O/bench_line.json 2> $O/bench_line.err
-python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_line_driver_steps20.json 2> $O/bench20.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 $R/bench.py --no-extras --no-cpu-baseline --no-converge > $O/kt.log 2>&1
+python3 $R/bench.py --full > $O/bench_line.json 2> $O/bench_line.err
+python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_line_driver_steps20.json 2> $O/bench20.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o k -- python3 $R/bench.py --full --no-extras --no-cpu-baseline --no-converge > $O/kt.log 2>&1
 cp $(find $O/kt -name "*kernel_stats.csv" | head -1) $O/bench_kernel_stats.csv
 for pass in fetch:FETCH_SIZE write:WRITE_SIZE "sq:SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY" "sq2:SQ_WAIT_INST_ANY SQ_BUSY_CYCLES SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   name=${pass%%:*}; ctr=${pass#*:}
@@ -63,7 +63,7 @@ rm -rf $O/feeder
 if [ -f $R/tune/librevs_bpp.so ]; then REVS_LIB=$R/tune/librevs_bpp.so python3 $R/tools/bpp_stamps.py 2>&1 | tail -4 > $O/bpp_stamps.txt; fi
 # the verdict launch behind a burst of 20 / a block of 32 iterations (tuning build), and the bursts' kernel trace
 if [ -f $R/tune/librevs_vd.so ]; then for k in 20 32; do REVS_LIB=$R/tune/librevs_vd.so python3 $R/tools/verdict_stamps.py $k 2>&1 | tail -7 > $O/verdict_stamps_$k.txt; done; fi
-rocprofv3 --kernel-trace --output-format csv -d $O/tr20 -o t -- python3 $R/bench.py --steps 20 --no-extras --no-cpu-baseline --no-converge > $O/tr20.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/tr20 -o t -- python3 $R/bench.py --full --steps 20 --bursts 15 --no-extras --no-cpu-baseline --no-converge > $O/tr20.log 2>&1
 python3 $R/tools/burst_trace.py $O/tr20 > $O/burst_trace_steps20.txt 2>&1
 rm -rf $O/tr20
 rm -rf $O/kt

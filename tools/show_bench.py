@@ -15,8 +15,9 @@ if j.get("roofline_valu"):
     print("valu", {k: j["roofline_valu"][k] for k in ("frac", "valu_instructions_per_wavefront_and_iteration")})
 if j.get("cpu_baseline"):
     print("cpu", round(j["cpu_baseline"]["value"]), j["cpu_baseline"]["cores"])
-t = j["breakdown"]["transient"]
-print("transient", round(t["ms_total"], 2), round(t["ms_per_step_mean"], 3), round(t["ms_per_step_max"], 2), "one call", t.get("one_call_ms_total") and round(t["one_call_ms_total"], 2), "iters_to_eps", j["breakdown"]["admm_iters_to_eps"])
+t = (j.get("breakdown") or {}).get("transient")      # (bench.py --full only)
+if t:
+    print("transient", round(t["ms_total"], 2), round(t["ms_per_step_mean"], 3), round(t["ms_per_step_max"], 2), "one call", t.get("one_call_ms_total") and round(t["one_call_ms_total"], 2), "iters_to_eps", j["breakdown"]["admm_iters_to_eps"])
 if j.get("time_to_eps"):
     te = j["time_to_eps"]
     print("time_to_eps_ms", te["time_to_eps_ms"] and round(te["time_to_eps_ms"], 3), "iterations", te["iterations"], "runs", [round(x, 2) for x in te["runs_ms"] or []],

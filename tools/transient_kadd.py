@@ -4,7 +4,7 @@ import subprocess
 import sys
 
 for k in sys.argv[1:] or ["3", "4", "6"]:
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "20", "--no-cpu-baseline", "--no-extras", "--no-converge",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "20", "--no-cpu-baseline", "--no-extras", "--no-converge",
                           "--op-kadd", k], capture_output=True, text=True).stdout
     j = json.loads(out.strip().splitlines()[-1])
     t = j["breakdown"]["transient"]
