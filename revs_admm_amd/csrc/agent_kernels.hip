@@ -1392,7 +1392,7 @@ int agent_step_chain(int64_t n_homes, int32_t T, const float *cost, const revs_h
                            node_of, nullptr, nullptr, stream, nullptr, flags, &cf);
 }
 
-// ---- verdicts by blocks (sharded streaming steady state, runtime.cpp) --------------------
+// ---- verdicts by blocks (sharded streaming steady state, plan_stream.cpp) ----------------
 // With residences sharded the node sums of an iteration are only known after an all-reduce, and
 // one collective per 18 us sweep would be the whole step.  So a block of B sweeps runs without
 // verdicts, each accumulating its sums into its own slice of a ring; ONE all-reduce then sums
@@ -1400,7 +1400,7 @@ int agent_step_chain(int64_t n_homes, int32_t T, const float *cost, const revs_h
 // verdict silences everything behind the block; the sweeps behind the failed iteration that
 // did run worked from an estimate that is not the operator's answer: the state a block starts
 // from is never overwritten while its verdicts are pending (the sweeps of a block rotate through
-// the other sets of buffers, runtime.cpp), and the host goes back to it.
+// the other sets of buffers, plan_stream.cpp), and the host goes back to it.
 // more than 64 KB of dynamic LDS (the big tree shapes) has to be granted per kernel, once
 template <int NT, int IPT, typename K>
 static bool tree_big_lds(K kernel, size_t lds) {
