@@ -240,6 +240,23 @@ int revs_residence_solve(int64_t n_homes, int32_t T,
                          const float *tariff, const revs_home_t *homes, const float *load,
                          float *p_out, float *soc_out, float *g_out, void *stream);
 
+/* Lagrangian dual bound of the centralized problem (the certificate of test-centralopt.py:98-116's comparison):
+ *   min sum_h c.g_h, g_h = LOAD_h + p_h;  each residence's own rows (window, 0 <= p <= rating, E_lo <= sum_t p_t <= E_hi);
+ *   vlo <= (R A g)[:, t] <= vhi for every row.
+ * With signed row multipliers y (double[m][T], y > 0 at vhi, y < 0 at vlo) and a scale s >= 0, weak duality gives
+ *   L(s y) = sum_h min_{p_h in X_h} (c + s d[node(h)]).(LOAD_h + p_h) - s sum_{m,t} max(vhi y, vlo y) <= optimum,
+ * d = R y (double[m][T]; d = y = NULL: no multipliers).  integral != 0: chargers on/off (p_t in {0, rating}, nmin <= #on
+ * <= nmax of the record) -- a bound on the MILP, >= the relaxed one at the same y.  The LOAD term is taken over the node
+ * sums of LOAD, load_node double[m][T] (NULL: left out).  node_of int32[n] (the residences' rows); scratch
+ * double[revs_dual_bound_scratch(n_homes, T)] (revs_admm_ops.h); p_node (double[m][T], accumulated into: zero it first;
+ * NULL: not wanted) receives the node sums of the minimiser.  out: device double[4] = {residences' part, LOAD part, row
+ * part, residences whose own rows are empty (their minimum is +inf: the bound then holds no information)}; the
+ * bound is out[0] + out[1] + out[2], bit-identical from call to call.  Enqueue only (capturable).
+ * REVS_EINVAL: T outside 1..REVS_MAX_T, a null pointer, scale < 0, d without y or y without d, vlo > vhi. */
+int revs_dual_bound(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes, const int32_t *node_of,
+                    int32_t m, const double *d, const double *y, const double *load_node, double scale, double vlo,
+                    double vhi, int32_t integral, double *scratch, double *p_node, double *out, void *stream);
+
 /* ---- operator ("Utility") side: see also revs_admm_ops.h -----------------------------
  * The drop-in binds the calls of THIS header: the home sweep (revs_agent_step*), the individual mode
  * (revs_residence_solve), the voltage check below, and the plan calls further down, behind which the whole

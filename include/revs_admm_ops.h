@@ -71,6 +71,9 @@ int revs_aggregate_f64(int32_t m, int32_t T, const int64_t *node_ptr,
 int revs_aggregate_f32(int32_t m, int32_t T, const int64_t *node_ptr,
                        const float *in_home, float *out_node, void *stream);
 
+/* Doubles of scratch revs_dual_bound (revs_admm.h) needs for n_homes residences (0: bad size). */
+int64_t revs_dual_bound_scratch(int64_t n_homes, int32_t T);
+
 /* g0 = (P_est + P_sch)/2 - G/kappa : the unconstrained minimiser of the Utility
  * objective (lpsolver.py:196-207).  float in, double out. */
 int revs_op_g0(int64_t n_homes, int32_t T, const float *p_est, const float *p_sch,

@@ -1253,6 +1253,180 @@ static void launch_agent(const AgentArgs &a, int mode, dim3 grid, hipStream_t s)
         else { CALL(64, 3); }                                      \
     } while (0)
 
+// ---- Lagrangian dual bound of the centralized LP / MILP (revs_dual_bound) -----------------------
+// L(s y) = sum_h min_{p in X_h} (c + s d[node(h)]).(LOAD_h + p) - s sum_{m,t} max(vhi y, vlo y),  d = R y.
+// The inner minimum of a residence is a ranking of its window's reduced costs r_t = c_t + s d[node][t] -- the sweep's
+// lane groups and group_rank, f64 keys, ties to the earlier slot -- and a count of the negative ones:
+//   relaxed:  E* = clamp(rating #{r < 0}, E_lo, E_hi) filled at full rating in rank order (the last slot partial);
+//   integral: n* = clamp(#{r < 0}, nmin, nmax) cheapest slots at full rating.
+// The LOAD term is sum_{n,t} (c_t + s d[n][t]) Lsum[n][t] over the node sums of LOAD (load_node): the launch reads the
+// 32-byte records, the tariff and d, never the profiles.  The first T workgroups take the slot-wise terms (LOAD, rows)
+// of slot blockIdx.x, the others a workgroup of residences each; every workgroup leaves two f64 partials, which
+// dual_bound_finalize_kernel sums in a fixed order: the value is bit-identical from call to call.
+struct BoundArgs {
+    int64_t n;
+    int32_t T, m, nhb;                 // nhb: residence workgroups
+    const float *cost;
+    const revs_home_t *homes;
+    const int32_t *node_of;
+    const double *d, *y, *load_node;   // double[m][T] each (d, y: NULL together = no multipliers)
+    double scale, vlo, vhi;
+    double *scratch;                   // double[2 (T + nhb)]: {LOAD, rows} per slot, then {value, empty} per workgroup
+    double *p_node;                    // += node sums of the minimiser (double[m][T]) or NULL
+};
+
+// (u, v) summed over the 256 threads of a workgroup in a fixed order; every thread gets the sums
+__device__ __forceinline__ void block_sum2(double &u, double &v) {
+    __shared__ double red[2][kBlock / 64];
+    for (int o = 32; o >= 1; o >>= 1) {
+        u += __shfl_xor(u, o, 64);
+        v += __shfl_xor(v, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        red[0][threadIdx.x >> 6] = u;
+        red[1][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+    u = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    v = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+}
+
+template <int LPA>
+__device__ __forceinline__ int group_count(int v) {
+#pragma unroll
+    for (int o = LPA / 2; o >= 1; o >>= 1) v += __shfl_xor(v, o, LPA);
+    return v;
+}
+
+template <int LPA, int SPL, bool INTEGRAL>
+__global__ __launch_bounds__(kBlock) void dual_bound_kernel(const BoundArgs a) {
+    const int tid = threadIdx.x;
+    const int T = a.T;
+    if ((int)blockIdx.x < T) {                     // slot-wise terms of slot t (uniform per workgroup)
+        const int t = (int)blockIdx.x;
+        const double c = (double)a.cost[t];
+        double ld = 0.0, rw = 0.0;
+        for (int nn = tid; nn < a.m; nn += kBlock) {
+#pragma clang fp contract(off)
+            const int64_t o = (int64_t)nn * T + t;
+            if (a.load_node) ld += (c + a.scale * (a.d ? a.d[o] : 0.0)) * a.load_node[o];
+            if (a.y) rw += fmax(a.vhi * a.y[o], a.vlo * a.y[o]);
+        }
+        block_sum2(ld, rw);
+        if (tid == 0) {
+            a.scratch[2 * t] = ld;
+            a.scratch[2 * t + 1] = -a.scale * rw;
+        }
+        return;
+    }
+    constexpr int kHomesPerBlock = kBlock / LPA, kSlots = LPA * SPL, kNodeLoc = 4;
+    const int bid = (int)blockIdx.x - T;
+    const int lig = tid & (LPA - 1);
+    const int t0 = lig * SPL;
+    const int64_t first = (int64_t)bid * kHomesPerBlock;
+    const int64_t agent = first + tid / LPA;
+    const bool live = agent < a.n;
+    revs_home_t h;
+    if (live) h = a.homes[agent];
+    else { h.ev = 0; h.start = 0; h.end = 0; h.nmin = 0; h.nmax = 0; h.rating = 0.f; h.capacity = 1.f; h.initial = 0.f; }
+    const int node = live ? a.node_of[agent] : 0;
+    const bool ev = live && h.ev != 0;
+    double r[SPL], key[SPL];
+    bool win[SPL];
+    int nw = 0, nneg = 0;
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+#pragma clang fp contract(off)
+        const int t = t0 + j;
+        const bool tv = t < T;
+        win[j] = ev && tv && t >= h.start && t < h.end;
+        const double c = tv ? (double)a.cost[t] : 0.0;
+        const double dn = (a.d && win[j]) ? a.d[(int64_t)node * T + t] : 0.0;
+        r[j] = (c + a.scale * dn) + 0.0;          // (+ 0.0: no -0 among the keys)
+        key[j] = win[j] ? r[j] : (double)INFINITY;
+        nw += win[j] ? 1 : 0;
+        nneg += (win[j] && r[j] < 0.0) ? 1 : 0;
+    }
+    nw = group_count<LPA>(nw);
+    nneg = group_count<LPA>(nneg);
+    int rank[SPL];
+    group_rank<LPA, SPL>(key, lig, rank);
+    double p[SPL];
+    bool empty;
+    if constexpr (INTEGRAL) {
+        empty = ev && (h.nmin > h.nmax || h.nmin > nw);
+        const int ns = min(max(nneg, h.nmin), h.nmax);
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) p[j] = (win[j] && !empty && rank[j] < ns) ? (double)h.rating : 0.0;
+    } else {
+#pragma clang fp contract(off)
+        const double rt = (double)h.rating, ini = (double)h.initial, cap = (double)h.capacity;
+        const double elo = ev ? (fmax(0.9, ini) - ini) * cap : 0.0;      // energy_bounds: init <= s_t <= 1, s_T >= 0.9
+        const double ehi = ev ? (1.0 - ini) * cap : 0.0;
+        empty = ev && (elo > ehi || elo > rt * (double)nw);
+        const double es = fmin(fmax(rt * (double)nneg, elo), ehi);
+#pragma unroll
+        for (int j = 0; j < SPL; ++j)
+            p[j] = (win[j] && !empty) ? fmin(rt, fmax(0.0, es - (double)rank[j] * rt)) : 0.0;
+    }
+    double val = 0.0;
+#pragma unroll
+    for (int j = 0; j < SPL; ++j) {
+#pragma clang fp contract(off)
+        val += p[j] * r[j];
+    }
+    double cnt = (empty && lig == 0) ? 1.0 : 0.0;
+    if (a.p_node) {         // (uniform) node sums of the minimiser: LDS for the workgroup's first nodes, as the sweep
+        __shared__ double nacc[kNodeLoc][kSlots];
+        for (int i = tid; i < kNodeLoc * kSlots; i += kBlock) (&nacc[0][0])[i] = 0.0;
+        const int base = a.node_of[first];
+        __syncthreads();
+        const int loc = node - base;
+#pragma unroll
+        for (int j = 0; j < SPL; ++j) {
+            if (p[j] == 0.0) continue;
+            if (loc >= 0 && loc < kNodeLoc) unsafeAtomicAdd(&nacc[loc][t0 + j], p[j]);
+            else unsafeAtomicAdd(&a.p_node[(int64_t)node * T + t0 + j], p[j]);
+        }
+        __syncthreads();
+        for (int i = tid; i < kNodeLoc * kSlots; i += kBlock) {
+            const int l = i / kSlots, t = i - l * kSlots;
+            const double v = nacc[l][t];
+            if (v != 0.0 && t < T && base + l < a.m) unsafeAtomicAdd(&a.p_node[(int64_t)(base + l) * T + t], v);
+        }
+    }
+    block_sum2(val, cnt);
+    if (tid == 0) {
+        a.scratch[2 * (T + bid)] = val;
+        a.scratch[2 * (T + bid) + 1] = cnt;
+    }
+}
+
+// out = {sum of the residences' minima, LOAD term, row term, residences with empty rows}: 256 threads, each folding a
+// fixed strided subset in order, then block_sum2 -- a fixed order whatever the number of workgroups.
+__global__ __launch_bounds__(kBlock) void dual_bound_finalize_kernel(const double *__restrict__ scratch, int32_t T,
+                                                                      int64_t nhb, double *out) {
+    double ld = 0.0, rw = 0.0, hv = 0.0, ec = 0.0;
+    for (int t = threadIdx.x; t < T; t += kBlock) {
+        ld += scratch[2 * t];
+        rw += scratch[2 * t + 1];
+    }
+    const double *hs = scratch + 2 * (int64_t)T;
+    for (int64_t b = threadIdx.x; b < nhb; b += kBlock) {
+        hv += hs[2 * b];
+        ec += hs[2 * b + 1];
+    }
+    block_sum2(ld, rw);
+    __syncthreads();                               // (block_sum2's LDS is reused)
+    block_sum2(hv, ec);
+    if (threadIdx.x == 0) {
+        out[0] = hv;
+        out[1] = ld;
+        out[2] = rw;
+        out[3] = ec;
+    }
+}
+
 }  // namespace revs
 
 using namespace revs;
@@ -1778,5 +1952,46 @@ extern "C" int revs_residence_solve(int64_t n_homes, int32_t T, const float *tar
     REVS_FOR_SHAPE(sh, CALL);
 #undef CALL
     REVS_CHECK_LAUNCH("revs_residence_solve");
+    return REVS_OK;
+}
+
+static int64_t dual_bound_blocks(int64_t n_homes, int32_t T) {
+    const int64_t per = kBlock / pick_shape(T).lpa;
+    return (n_homes + per - 1) / per;
+}
+
+extern "C" int64_t revs_dual_bound_scratch(int64_t n_homes, int32_t T) {
+    if (n_homes < 0 || T <= 0 || T > REVS_MAX_T) return 0;
+    return 2 * ((int64_t)T + dual_bound_blocks(n_homes, T));
+}
+
+extern "C" int revs_dual_bound(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes,
+                               const int32_t *node_of, int32_t m, const double *d, const double *y,
+                               const double *load_node, double scale, double vlo, double vhi, int32_t integral,
+                               double *scratch, double *p_node, double *out, void *stream) {
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_dual_bound: T=%d outside 1..%d", (int)T, REVS_MAX_T);
+    REVS_REQUIRE(n_homes >= 0 && m > 0, "revs_dual_bound: n_homes >= 0 and m > 0 required");
+    REVS_REQUIRE(cost && scratch && out && (n_homes == 0 || (homes && node_of)),
+                 "revs_dual_bound: null pointer argument");
+    REVS_REQUIRE(scale >= 0.0, "revs_dual_bound: scale must be >= 0");       // (also rejects NaN)
+    REVS_REQUIRE(!d || y, "revs_dual_bound: d = R y given without y");
+    REVS_REQUIRE(!y || d, "revs_dual_bound: y given without d = R y");
+    REVS_REQUIRE(vlo <= vhi, "revs_dual_bound: vlo > vhi");
+    const int64_t nhb = dual_bound_blocks(n_homes, T);
+    REVS_REQUIRE(nhb + T < (int64_t)1 << 31, "revs_dual_bound: too many residences for one launch");
+    BoundArgs a{n_homes, T, m, (int32_t)nhb, cost, homes, node_of, d, y, load_node, scale, vlo, vhi, scratch, p_node};
+    const Shape sh = pick_shape(T);
+    const dim3 grid((unsigned)(T + nhb));
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(LPA, SPL)                                                                                  \
+    do {                                                                                                \
+        if (integral) hipLaunchKernelGGL((dual_bound_kernel<LPA, SPL, true>), grid, dim3(kBlock), 0, s, a); \
+        else hipLaunchKernelGGL((dual_bound_kernel<LPA, SPL, false>), grid, dim3(kBlock), 0, s, a);     \
+    } while (0)
+    REVS_FOR_SHAPE(sh, CALL);
+#undef CALL
+    REVS_CHECK_LAUNCH("revs_dual_bound");
+    hipLaunchKernelGGL(dual_bound_finalize_kernel, dim3(1), dim3(kBlock), 0, s, scratch, T, nhb, out);
+    REVS_CHECK_LAUNCH("revs_dual_bound (finalize)");
     return REVS_OK;
 }

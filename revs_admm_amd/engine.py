@@ -25,6 +25,7 @@ import torch
 from . import _lib
 from ._lib import HOME_DTYPE, MODES, PDHG, check, ptr
 from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (re-exported)
+from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
 from .steady_state import SteadyStateMixin
@@ -197,7 +198,7 @@ def _on_current_stream(fn):
     return wrapped
 
 
-class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin):
+class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin):
     """State of one ADMM run on one GPU.
 
     Parameters
@@ -663,7 +664,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin):
 
     # -------------------------------------------------------------- operator
     # (dual Newton path: operator_newton.py; ADMM forms: operator_admm.py; steady state:
-    # steady_state.py -- mixed into this class)
+    # steady_state.py; dual bound and certificate: certificate.py -- mixed into this class)
     def _require_converged(self, ok):
         """An operator answer that did not reach its tolerance is not handed to the residences:
         REVS_ENOTCONV (every rank holds the same node-space state and takes the same decision)."""
