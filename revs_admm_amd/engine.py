@@ -230,7 +230,37 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                  vhigh=1.05, mode="binary", device="cuda:0", pdhg=None,
                  op: OperatorOptions | None = None, group=None, node_counts=None,
                  pdhg_warm=True, feeder=None, comm_hook=None, _kernels=None):
-        if _kernels is None:
+        # (stages in this order: each allocates, sets up the plan or launches on what the ones before it left)
+        native = _kernels is None
+        self._init_device(device, _kernels)
+        load, node_of, Rn, node_ptr = self._init_problem(homes, load, node_of, Rn, kappa, vset, vlow, vhigh, mode, op,
+                                                         group, node_counts, native)
+        self._init_residences(cost, homes, load, node_ptr, pdhg, pdhg_warm)
+        self._init_newton(Rn)
+        self._init_pinned()
+        self._warm_up(native)
+        self._init_plan(node_of, native)
+        self._init_tree(feeder, native)
+        self._init_comm(comm_hook, native)
+        self._init_stream()
+        self._init_r32()
+        self._preallocate()
+
+    def _up(self, a):
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+
+    def _pinned(self, shape, dtype):
+        """Zeroed pinned host memory and the address the kernels reach it by (without a GPU: the host's, for the
+        host stand-in of the kernels)."""
+        t = torch.zeros(shape, dtype=dtype, pin_memory=self.dev.type == "cuda")
+        if self.dev.type != "cuda":
+            return t, t.data_ptr()
+        dp = C.c_void_p()
+        check(self.lib.revs_host_device_ptr(t.data_ptr(), C.byref(dp)), "revs_host_device_ptr")
+        return t, int(dp.value)
+
+    def _init_device(self, device, kernels):
+        if kernels is None:
             self.lib = _lib.load()               # raises when the HIP library is missing
             self.dev = _dev_check(device)        # raises without a GPU
             torch.cuda.set_device(self.dev)
@@ -238,8 +268,11 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
             # tests only (tests/fake_kernels.py): an object exposing the C ABI's entry
             # points over host memory, so the driver logic -- sharding, all-reduce,
             # stopping rules -- can run under gloo without a GPU.  Never set by the product.
-            self.lib = _kernels
+            self.lib = kernels
             self.dev = torch.device(device)
+
+    def _init_problem(self, homes, load, node_of, Rn, kappa, vset, vlow, vhigh, mode, op, group, node_counts, native):
+        """Options, the residences sorted by node, and the node counts over every rank."""
         self.group = group
         self.kappa = float(kappa)
         self.mode = MODES[mode] if isinstance(mode, str) else int(mode)
@@ -247,6 +280,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if self.op.solver == "newton" and np.asarray(Rn).shape[0] > 16384:
             self.op = dataclasses.replace(self.op, solver="admm")   # revs_op_dual_select's limit
         self.vlo, self.vhi = voltage_limits(vset, vlow, vhigh)
+        self._scale = max(abs(self.vlo), abs(self.vhi), 1e-300)     # (the voltage rows are judged relative to it)
 
         load = np.ascontiguousarray(load, np.float32)
         n, T = load.shape
@@ -272,7 +306,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         counts = local_counts.copy()
         # (a comm.LocalRanks rank: logical ranks inside one process -- a host-side transport like a gloo group)
         self._local_group = group is not None and hasattr(group, "allreduce_host")
-        self._host_group = (group is not None and _kernels is None
+        self._host_group = (group is not None and native
                             and (self._local_group or torch.distributed.get_backend(group) != "nccl"))
         if self._local_group:
             counts = group.allreduce_host(counts.astype(np.float64), 0).astype(np.int64)
@@ -283,14 +317,16 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if node_counts is not None:
             counts = np.asarray(node_counts, np.int64)
         self.node_counts = counts
+        return load, node_of, Rn, node_ptr
 
+    def _init_residences(self, cost, homes, load, node_ptr, pdhg, pdhg_warm):
+        """The residences' records and state on the device, and the options of their PDHG solves."""
+        n, T = self.n, self.T
         f32 = dict(dtype=torch.float32, device=self.dev)
-        f64 = dict(dtype=torch.float64, device=self.dev)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
-        self.cost = up(np.asarray(cost, np.float32))
-        self.homes = up(homes[self.perm].view(np.uint8).reshape(n, HOME_DTYPE.itemsize))
-        self.load = up(load[self.perm])
-        self.node_ptr = up(node_ptr)
+        self.cost = self._up(np.asarray(cost, np.float32))
+        self.homes = self._up(homes[self.perm].view(np.uint8).reshape(n, HOME_DTYPE.itemsize))
+        self.load = self._up(load[self.perm])
+        self.node_ptr = self._up(node_ptr)
         self.P_est = torch.zeros(n, T, **f32)          # lpsolver.py:244
         self.P_est_new = torch.zeros(n, T, **f32)
         self.P_sch = torch.zeros(n, T, **f32)          # lpsolver.py:245
@@ -314,7 +350,11 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if self._pdhg_warm:      # one scalar per home, or one per SOC row with full_rows
             self.pdhg_dual = torch.zeros((n, T) if self.pdhg.full_rows else (n,), **f32)
 
-        # ---- operator setup ----
+    def _init_newton(self, Rn):
+        """The operator's state: the ADMM forms' (solver="admm") and the dual Newton path's buffers."""
+        n, M, T, counts = self.n, self.M, self.T, self.node_counts
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        f64 = dict(dtype=torch.float64, device=self.dev)
         self._Rn_host, self._counts_host = Rn, counts
         self._admm_ready = False
         nz = lambda: torch.zeros(M, T, **f64)
@@ -331,8 +371,8 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         # dual Newton path: R itself (d = R^T y; candidate rows of K), and R^T with the rows
         # of nodes without residences zeroed (v = R p is constrained where residences are)
         has = (counts > 0).astype(np.float64)
-        self.R64 = up(Rn)
-        self.R64T = up((Rn * has[:, None]).T)
+        self.R64 = self._up(Rn)
+        self.R64T = self._up((Rn * has[:, None]).T)
         A = _lib.DUAL_AMAX
         self.yd = [nz(), nz()]                         # multipliers: current, trial
         self.pnq = torch.zeros(3, M, T, **f64)
@@ -364,109 +404,110 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self.spec_hist = [0, 0]                        # speculative sweeps kept / discarded
         self.P_sch_alt = torch.zeros(n, T, **f32) if self.op.solver == "newton" else None
         self.G_alt = torch.zeros(n, T, **f32) if self.op.solver == "newton" else None
+
+    def _init_pinned(self):
+        """The records the kernels and the host exchange through pinned host memory (no copy launches)."""
         cuda = self.dev.type == "cuda"
+        T = self.T
         # per-slot stats are written by the select kernel straight into pinned host memory
-        self.stats_host = [torch.zeros(T, 8, dtype=torch.float64, pin_memory=cuda) for _ in range(2)]
-        self.stats_dev = []
-        for t in self.stats_host:
-            if cuda:
-                dp = C.c_void_p()
-                check(self.lib.revs_host_device_ptr(t.data_ptr(), C.byref(dp)),
-                      "revs_host_device_ptr")
-                self.stats_dev.append(int(dp.value))
-            else:
-                self.stats_dev.append(t.data_ptr())
-        self.stats_ev = [torch.cuda.Event() if cuda else None for _ in range(2)]
+        self.stats_host, self.stats_dev = [], []
+        for _ in range(2):
+            t, dp = self._pinned((T, 8), torch.float64)
+            self.stats_host.append(t)
+            self.stats_dev.append(dp)
         # step lengths (host -> kernel) and pivot counts (kernel -> host) live in pinned host
         # memory as well: no copy launches inside a Newton iteration
-        self.alpha_h = torch.zeros(T, dtype=torch.float64, pin_memory=cuda)
-        self.info_h = torch.zeros(T, dtype=torch.int32, pin_memory=cuda)
-        self.alpha_dev, self.info_dev = self.alpha_h.data_ptr(), self.info_h.data_ptr()
+        self.alpha_h, self.alpha_dev = self._pinned(T, torch.float64)
+        self.info_h, self.info_dev = self._pinned(T, torch.int32)
         # ... and the word check_status() has the residences' status bits OR-ed into (revs_status_or)
-        self._flag_h = torch.zeros(2, dtype=torch.int32, pin_memory=cuda)
+        self._flag_h, dp = self._pinned(2, torch.int32)
         self._flag_np = self._flag_h.numpy()
-        self._flag_dev = None
+        self._flag_dev = dp if cuda else None
         # ... and the residual records (revs_residual_finalize's float[4]) of iterations outside the streaming loop,
         # which run(eps=) collects until its stopping rule is next evaluated
-        self._dmx_h = torch.zeros(64, 4, dtype=torch.float32, pin_memory=cuda)
+        self._dmx_h, dp = self._pinned((64, 4), torch.float32)
         self._dmx_np = self._dmx_h.numpy()
-        self._dmx_dev = None
-        if cuda:
-            for name, t in (("alpha_dev", self.alpha_h), ("info_dev", self.info_h), ("_flag_dev", self._flag_h),
-                            ("_dmx_dev", self._dmx_h)):
-                dp = C.c_void_p()
-                check(self.lib.revs_host_device_ptr(t.data_ptr(), C.byref(dp)),
-                      "revs_host_device_ptr")
-                setattr(self, name, int(dp.value))
+        self._dmx_dev = dp if cuda else None
         self.newton_hist: list[tuple] = []
-        if cuda and self.op.solver == "newton" and _kernels is None:
-            # first use of a kernel loads its code object (1-2 ms each on this stack): touch the
-            # Newton-iteration kernels now, with empty candidate lists, not inside the first solve
-            check(self.lib.revs_op_dual_model(M, T, ptr(self.R64), ptr(self.pnq[1]), ptr(self.c_idx[0]),
-                                              ptr(self.c_cnt[0]), ptr(self.c_val[0]), self.kappa,
-                                              self.op.newton_delta, self.op.newton_pivots, self.nks,
-                                              ptr(self.k_slabs), ptr(self.k_full), ptr(self.yhat),
-                                              self.info_dev, self.stream), "revs_op_dual_model")
-            check(self.lib.revs_op_dual_step(T, ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
-                                             ptr(self.c_val[0]), ptr(self.yhat), self.alpha_dev,
-                                             ptr(self.yd[1]), self.stats_dev[1] + 32, self.stream),
-                  "revs_op_dual_step")
-            check(self.lib.revs_op_dual_model_small(M, T, ptr(self.R64), ptr(self.pnq[1]),
-                                                    ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
-                                                    ptr(self.c_val[0]), self.kappa,
-                                                    self.op.newton_delta, self.op.newton_pivots,
-                                                    ptr(self.k_full), ptr(self.yhat), self.info_dev,
-                                                    self.stream), "revs_op_dual_model_small")
-            self._gemm1(self.R64, self.yd[0], self.d_sl)
-            torch.cuda.synchronize(self.dev)
-        # steady-state iteration as ONE native call (one GPU; see revs_plan_spec_step)
+
+    def _warm_up(self, native):
+        """First use of a kernel loads its code object (1-2 ms each on this stack): touch the Newton-iteration kernels
+        now, with empty candidate lists, not inside the first solve."""
+        if not (self.dev.type == "cuda" and self.op.solver == "newton" and native):
+            return
+        M, T = self.M, self.T
+        check(self.lib.revs_op_dual_model(M, T, ptr(self.R64), ptr(self.pnq[1]), ptr(self.c_idx[0]),
+                                          ptr(self.c_cnt[0]), ptr(self.c_val[0]), self.kappa,
+                                          self.op.newton_delta, self.op.newton_pivots, self.nks,
+                                          ptr(self.k_slabs), ptr(self.k_full), ptr(self.yhat),
+                                          self.info_dev, self.stream), "revs_op_dual_model")
+        check(self.lib.revs_op_dual_step(T, ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
+                                         ptr(self.c_val[0]), ptr(self.yhat), self.alpha_dev,
+                                         ptr(self.yd[1]), self.stats_dev[1] + 32, self.stream),
+              "revs_op_dual_step")
+        check(self.lib.revs_op_dual_model_small(M, T, ptr(self.R64), ptr(self.pnq[1]),
+                                                ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
+                                                ptr(self.c_val[0]), self.kappa,
+                                                self.op.newton_delta, self.op.newton_pivots,
+                                                ptr(self.k_full), ptr(self.yhat), self.info_dev,
+                                                self.stream), "revs_op_dual_model_small")
+        self._gemm1(self.R64, self.yd[0], self.d_sl)
+        torch.cuda.synchronize(self.dev)
+
+    def _init_plan(self, node_of, native):
+        """The plan: the steady-state and chained iterations as native calls (revs_plan_*)."""
         self._plan = None
         self._fused_ready = False        # the last kept sweep did the next evaluation's home pass
         self._fused_p = None             # ... and where it left the node sums
         self.recompute_pe_new = False
         self._ar_ahead = False           # ... already exchanged between the ranks
         self._prod_ahead = False         # ... and the product on them already enqueued
-        if cuda and self.op.solver == "newton" and _kernels is None and self.op.native_plan:
-            d = _lib.PlanDesc()
-            d.n_homes, d.m, d.T = n, M, T
-            d.node_ptr, d.R, d.Rt = ptr(self.node_ptr), ptr(self.R64), ptr(self.R64T)
-            d.kappa, d.vlo, d.vhi = self.kappa, self.vlo, self.vhi
-            d.kadd, d.ksplit = self.op.newton_kadd, self.ksplit1
-            d.d_slabs, d.v_slabs, d.pnq = ptr(self.d_sl), ptr(self.v_sl), ptr(self.pnq)
-            d.vfull, d.viol, d.partial = ptr(self.vfull), ptr(self.violw), ptr(self.d_part)
-            d.cand_idx, d.cand_cnt, d.cand_val = (ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
-                                                  ptr(self.c_val[0]))
-            d.stats, d.stats_host = self.stats_dev[0], self.stats_host[0].data_ptr()
-            d.cost, d.homes, d.load = ptr(self.cost), ptr(self.homes), ptr(self.load)
-            d.diff, d.dsq, d.status = ptr(self.diff), ptr(self.dsq), ptr(self.status)
-            d.pdhg_dual, d.mode, d.pdhg = ptr(self.pdhg_dual), self.mode, self.pdhg
-            self.node_of_dev = up(node_of[self.perm].astype(np.int32))
-            self.P_est_alt = torch.zeros(n, T, **f32)
-            self.p_alt = nz()                         # second buffer of the fused node sums
-            d.node_of = ptr(self.node_of_dev)
-            # with no multipliers the sweep recomputes the operator's answer instead of reading it
-            # (same bits, one input stream less: 20.0 -> 19.0 us per launch at 100k homes x 24,
-            # round 2; OperatorOptions(recompute_pe_new=False) restores the read)
-            d.recompute_pe_new = int(bool(self.op.recompute_pe_new))
-            self.recompute_pe_new = bool(d.recompute_pe_new)
-            d.cand_idx1, d.cand_cnt1, d.cand_val1 = (ptr(self.c_idx[1]), ptr(self.c_cnt[1]),
-                                                     ptr(self.c_val[1]))
-            d.stats1, d.stats1_host = self.stats_dev[1], self.stats_host[1].data_ptr()
-            d.yhat, d.k_full, d.info = ptr(self.yhat), ptr(self.k_full), self.info_dev
-            d.delta, d.eps, d.max_pivots = self.op.newton_delta, self.op.eps, self.op.newton_pivots
-            self._plan_desc = d
-            self._plan = self.lib.revs_plan_create(C.byref(d))
-            if not self._plan:
-                raise _lib.RevsError("revs_plan_create failed: "
-                                     + self.lib.revs_last_error().decode())
-            check(self.lib.revs_plan_set_fold_redo(self._plan, int(self.op.fold_redo)), "revs_plan_set_fold_redo")
-            check(self.lib.revs_plan_set_kadd_cold(self._plan, int(self.op.newton_kadd_cold), int(self.op.newton_kadd_cold_at)),
-                  "revs_plan_set_kadd_cold")
-            no = _lib.NewtonOpts(ptr(self.k_slabs), self.nks, self.alpha_h.data_ptr(), self.alpha_dev,
-                                 self.info_h.data_ptr(), int(self.op.newton_max), int(self.op.newton_ls))
-            check(self.lib.revs_plan_set_newton(self._plan, C.byref(no)), "revs_plan_set_newton")
-        # third node-sum buffer and the feeder as a tree: streaming steady state
-        self.p_alt2 = nz()
+        if not (self.dev.type == "cuda" and self.op.solver == "newton" and native and self.op.native_plan):
+            return
+        n, M, T = self.n, self.M, self.T
+        d = _lib.PlanDesc()
+        d.n_homes, d.m, d.T = n, M, T
+        d.node_ptr, d.R, d.Rt = ptr(self.node_ptr), ptr(self.R64), ptr(self.R64T)
+        d.kappa, d.vlo, d.vhi = self.kappa, self.vlo, self.vhi
+        d.kadd, d.ksplit = self.op.newton_kadd, self.ksplit1
+        d.d_slabs, d.v_slabs, d.pnq = ptr(self.d_sl), ptr(self.v_sl), ptr(self.pnq)
+        d.vfull, d.viol, d.partial = ptr(self.vfull), ptr(self.violw), ptr(self.d_part)
+        d.cand_idx, d.cand_cnt, d.cand_val = (ptr(self.c_idx[0]), ptr(self.c_cnt[0]),
+                                              ptr(self.c_val[0]))
+        d.stats, d.stats_host = self.stats_dev[0], self.stats_host[0].data_ptr()
+        d.cost, d.homes, d.load = ptr(self.cost), ptr(self.homes), ptr(self.load)
+        d.diff, d.dsq, d.status = ptr(self.diff), ptr(self.dsq), ptr(self.status)
+        d.pdhg_dual, d.mode, d.pdhg = ptr(self.pdhg_dual), self.mode, self.pdhg
+        self.node_of_dev = self._up(node_of[self.perm].astype(np.int32))
+        self.P_est_alt = torch.zeros(n, T, dtype=torch.float32, device=self.dev)
+        self.p_alt = torch.zeros(M, T, dtype=torch.float64, device=self.dev)    # second buffer of the fused node sums
+        d.node_of = ptr(self.node_of_dev)
+        # with no multipliers the sweep recomputes the operator's answer instead of reading it
+        # (same bits, one input stream less: 20.0 -> 19.0 us per launch at 100k homes x 24,
+        # round 2; OperatorOptions(recompute_pe_new=False) restores the read)
+        d.recompute_pe_new = int(bool(self.op.recompute_pe_new))
+        self.recompute_pe_new = bool(d.recompute_pe_new)
+        d.cand_idx1, d.cand_cnt1, d.cand_val1 = (ptr(self.c_idx[1]), ptr(self.c_cnt[1]),
+                                                 ptr(self.c_val[1]))
+        d.stats1, d.stats1_host = self.stats_dev[1], self.stats_host[1].data_ptr()
+        d.yhat, d.k_full, d.info = ptr(self.yhat), ptr(self.k_full), self.info_dev
+        d.delta, d.eps, d.max_pivots = self.op.newton_delta, self.op.eps, self.op.newton_pivots
+        self._plan_desc = d
+        self._plan = self.lib.revs_plan_create(C.byref(d))
+        if not self._plan:
+            raise _lib.RevsError("revs_plan_create failed: "
+                                 + self.lib.revs_last_error().decode())
+        check(self.lib.revs_plan_set_fold_redo(self._plan, int(self.op.fold_redo)), "revs_plan_set_fold_redo")
+        check(self.lib.revs_plan_set_kadd_cold(self._plan, int(self.op.newton_kadd_cold), int(self.op.newton_kadd_cold_at)),
+              "revs_plan_set_kadd_cold")
+        no = _lib.NewtonOpts(ptr(self.k_slabs), self.nks, self.alpha_h.data_ptr(), self.alpha_dev,
+                             self.info_h.data_ptr(), int(self.op.newton_max), int(self.op.newton_ls))
+        check(self.lib.revs_plan_set_newton(self._plan, C.byref(no)), "revs_plan_set_newton")
+
+    def _init_tree(self, feeder, native):
+        """The streaming steady state's third node-sum buffer, and the feeder as a tree (OperatorOptions.voltage)."""
+        M, Rn, counts = self.M, self._Rn_host, self.node_counts
+        self.p_alt2 = torch.zeros(M, self.T, dtype=torch.float64, device=self.dev)
         self._burst = max(1, int(self.op.stream_burst))
         self._p_clear = None             # the node-sum array the last streaming launch cleared
         self._tree = None
@@ -475,7 +516,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self._comm = None
         recovered = False
         if (feeder is None and self.op.voltage in ("auto", "tree") and M <= 4096 and self.op.solver == "newton"
-                and _kernels is None):
+                and native):
             # the caller holds only the matrix (lpsolver.py:184-189 hands the solver R, not the network): a radial
             # feeder is recovered from it -- junctions without a residence become extra tree nodes -- and verified
             # against Rn below like a feeder the caller passed; anything else stays on the dense product
@@ -507,7 +548,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                     tr, rejected = None, True              # (Rn is not a radial feeder's matrix: dense product)
             if tr is not None:
                 self._tree_host = tr
-                self._tree_dev = {k: up(tr[k].view(np.int64) if k == "pack" else tr[k]) for k in ("pack", "w")}
+                self._tree_dev = {k: self._up(tr[k].view(np.int64) if k == "pack" else tr[k]) for k in ("pack", "w")}
                 self._tree = _lib.Tree(tr["n"], ptr(self._tree_dev["pack"]), ptr(self._tree_dev["w"]))
                 if self._plan is not None:
                     check(self.lib.revs_plan_set_tree(self._plan, C.byref(self._tree)),
@@ -522,8 +563,15 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         elif self.op.voltage == "tree":
             raise ValueError('OperatorOptions(voltage="tree") needs feeder=')
         self.tree_recovered = bool(recovered and self._tree is not None)   # the tree form runs on a tree recovered from Rn
+
+    def _init_comm(self, comm_hook, native):
+        """Residences sharded over a group: the library's communicator -- over the caller's transport, or its own
+        RCCL one -- in the plan."""
+        group = self.group
         self._hook_ref = None
-        if group is not None and cuda and _kernels is None and (comm_hook is not None or self._host_group):
+        if not (group is not None and self.dev.type == "cuda" and native):
+            return
+        if comm_hook is not None or self._host_group:
             # the caller's transport behind the library's communicator (revs_comm_create_hook)
             if self._local_group:
                 ws, rk = group.size, group.rank_id
@@ -535,9 +583,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
             self._comm = self.lib.revs_comm_create_hook(self._hook_ref, None, rk, ws)
             if not self._comm:
                 raise _lib.RevsError("revs_comm_create_hook failed: " + self.lib.revs_last_error().decode())
-            if self._plan is not None:
-                check(self.lib.revs_plan_set_comm(self._plan, self._comm), "revs_plan_set_comm")
-        elif group is not None and cuda and _kernels is None and self.op.library_comm:
+        elif self.op.library_comm:
             # the library's own RCCL communicator: unique id from rank 0 over the caller's group
             ws, rk = torch.distributed.get_world_size(group), torch.distributed.get_rank(group)
             idb = (C.c_char * 128)()
@@ -549,8 +595,13 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
             self._comm = self.lib.revs_comm_create(raw, rk, ws)
             if not self._comm:
                 raise _lib.RevsError("revs_comm_create failed: " + self.lib.revs_last_error().decode())
-            if self._plan is not None:
-                check(self.lib.revs_plan_set_comm(self._plan, self._comm), "revs_plan_set_comm")
+        else:
+            return
+        if self._plan is not None:
+            check(self.lib.revs_plan_set_comm(self._plan, self._comm), "revs_plan_set_comm")
+
+    def _init_stream(self):
+        """The streaming steady state: its records, its call arguments built once, its block form on the plan."""
         self._block = 0
         self._sets = None               # buffer pools of the block form (allocated on first use)
         # max_h diff[h] (lpsolver.py:284) of the iterations whose sweeps folded it on the device:
@@ -565,31 +616,34 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self._stream_st_ref = C.byref(self._stream_st)
         self._stream_out = (C.c_int32(), C.c_double())
         self._stream_out_ref = (C.addressof(self._stream_out[0]), C.addressof(self._stream_out[1]))
-        self._scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
         self._pn0 = None
         if (self._plan is not None and self._tree is not None and self.op.stream_block > 1
                 and self.recompute_pe_new and (self._comm is not None or self.op.stream_block_single)):
             self._block = min(int(self.op.stream_block), _lib.STREAM_BLOCK_MAX)
             check(self.lib.revs_plan_set_stream_block(self._plan, self._block, int(self.op.stream_overlap)),
                   "revs_plan_set_stream_block")
-            self._inner = max(1, min(int(self.op.stream_inner), int(self.lib.revs_agent_max_inner(T, int(self.pdhg.lanes)))))
+            self._inner = max(1, min(int(self.op.stream_inner), int(self.lib.revs_agent_max_inner(self.T, int(self.pdhg.lanes)))))
             check(self.lib.revs_plan_set_stream_inner(self._plan, self._inner), "revs_plan_set_stream_inner")
             self._sets_st = _lib.StreamSets()
             self._sets_by, self._sets_sig, self._pn_ptr = {}, None, {}
             self._sets_ref = C.byref(self._sets_st)
-        # R (float) for the voltage check
-        self.R32 = up(Rn.astype(np.float32))
-        self.node_load = torch.zeros(M, T, **f32)
-        self.volt = torch.zeros(M, T, **f32)
-        # What the run loops would allocate on first use, now (OperatorOptions.preallocate): the pools the state
-        # rotates through, the folded chain's third multiplier array, the plan's ring / events / chain buffers
-        # (revs_plan_prepare) -- a fresh engine's first run then makes no allocation between its launches
-        # (~0.5 ms of the 2.2 ms transient at 100 000 x 24, tools/transient_hostgaps.py).
+
+    def _init_r32(self):
+        """R (float) for the voltage check."""
+        self.R32 = self._up(self._Rn_host.astype(np.float32))
+        self.node_load = torch.zeros(self.M, self.T, dtype=torch.float32, device=self.dev)
+        self.volt = torch.zeros(self.M, self.T, dtype=torch.float32, device=self.dev)
+
+    def _preallocate(self):
+        """What the run loops would allocate on first use, now (OperatorOptions.preallocate): the pools the state
+        rotates through, the folded chain's third multiplier array, the plan's ring / events / chain buffers
+        (revs_plan_prepare) -- a fresh engine's first run then makes no allocation between its launches
+        (~0.5 ms of the 2.2 ms transient at 100 000 x 24, tools/transient_hostgaps.py)."""
         if self._plan is not None and self._tree is not None and self.op.preallocate:
             self._state_pools()
             self._y_spare = torch.zeros_like(self.yd[0])
             check(self.lib.revs_plan_prepare(self._plan), "revs_plan_prepare")
-            if cuda:
+            if self.dev.type == "cuda":
                 torch.cuda.synchronize(self.dev)
 
     # ------------------------------------------------------------------ util
@@ -663,8 +717,9 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
               "revs_gemm_tn_f64_split")
 
     # -------------------------------------------------------------- operator
-    # (dual Newton path: operator_newton.py; ADMM forms: operator_admm.py; steady state:
-    # steady_state.py; dual bound and certificate: certificate.py -- mixed into this class)
+    # (dual Newton path and the chained iteration: operator_newton.py; ADMM forms: operator_admm.py; the speculative
+    # iteration and the streaming loops: steady_state.py; dual bound and certificate: certificate.py -- mixed into
+    # this class.  step() and run_steps() below choose the path; the mixins' methods run it.)
     def _require_converged(self, ok):
         """An operator answer that did not reach its tolerance is not handed to the residences:
         REVS_ENOTCONV (every rank holds the same node-space state and takes the same decision)."""
@@ -674,6 +729,12 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                 f"Newton path gave up (more than {_lib.DUAL_AMAX} binding rows in a slot, no ascent, or "
                 f"{self.op.newton_max} iterations) and the ADMM form stopped at max_iter = "
                 f"{self.op.max_iter} above eps = {self.op.eps:g}")
+
+    def _admm_take_over(self):
+        """The dual Newton path gave up on this iteration: the ADMM forms solve it, from a cold start."""
+        self._fast_cold = True
+        self.op_cold = True
+        self._require_converged(self.operator_solve(admm_only=True))
 
     def operator_solve(self, admm_only=False):
         """Utility(graph, P_est[k], P_sch[k], G[k]).solve() -> P_est[k+1]
@@ -795,142 +856,23 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         return r[0], r[1], r[2], bool(r[3] > 0.5)
 
     @_on_current_stream
-    def step(self, write_sc=True, events=None):
-        """One iteration of the while-loop of lpsolver.py:254-287.  `events`: HIP events
-        [1], [2] recorded between the operator part and the home sweep, and after the sweep
-        (bench.py's per-kernel timing; [0] is the caller's: the previous step's [2])."""
-        rec = (lambda i: events[i].record()) if events else (lambda i: None)
+    def step(self, write_sc=True):
+        """One iteration of the while-loop of lpsolver.py:254-287."""
         o = self.op
-        if not write_sc and not events and self._fused_ready and self._stream_ok():
+        if not write_sc and self._fused_ready and self._stream_ok():
             self._stream_run(1)              # steady state: one launch, verdict inside it
             return
         self._p_clear = None                 # (every other path rewrites the node-sum arrays)
         if o.solver == "newton" and o.speculate and self._spec_ok:
-            self._fold_resume = False
-            # steady state: the multipliers of the last iteration are expected to stand
-            scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
-            if self._plan is not None:               # one native call: enqueue, wait, judge
-                rm = C.c_double()
-                evh = [None, None]
-                if events:
-                    for i in (1, 2):
-                        if not events[i].cuda_event:
-                            events[i].record()       # creates the hipEvent behind the object
-                        evh[i - 1] = events[i].cuda_event
-                fused_in = self._fused_ready
-                p0 = self.pnq[0]
-                p_in = self._fused_p if fused_in else p0
-                p_out = None
-                if o.fuse_home_pass and not self._y_support:
-                    p_out = self.p_alt if p_in.data_ptr() == p0.data_ptr() else p0
-                self._fused_ready = False
-
-                def call(phase):
-                    check(self.lib.revs_plan_spec_step(
-                        self._plan, phase, ptr(self.yd[0]), int(self._y_support), ptr(self.P_est),
-                        ptr(self.P_est_new), ptr(self.P_sch), ptr(self.G), ptr(self.P_sch_alt),
-                        ptr(self.G_alt), ptr(self.S) if write_sc else None,
-                        ptr(self.Csoc) if write_sc else None, int(fused_in), ptr(p_in), ptr(p_out),
-                        ptr(self.P_est_alt), C.byref(rm), evh[0], evh[1],
-                        self.stream), "revs_plan_spec_step")
-                ar_ahead = prod_ahead = False
-                skip_product = fused_in and self._ar_ahead and self._prod_ahead
-                if self.group is None:
-                    call(3)
-                else:                                # home pass, exchange of p, the rest
-                    if not fused_in:
-                        call(1)
-                    if not (fused_in and self._ar_ahead):
-                        self._allreduce(p_in)        # the only exchange of the iteration
-                    self._ar_ahead = self._prod_ahead = False
-                    if p_out is None:
-                        call(2 | (4 if skip_product else 0))
-                    else:
-                        # enqueue product and sweep, then -- before waiting for the verdict --
-                        # the exchange of the node sums this sweep leaves for the NEXT
-                        # evaluation: it is stream-ordered behind the sweep, and its host-side
-                        # cost overlaps the sweep instead of standing between two iterations
-                        # (a discarded sweep makes it a wasted, harmless exchange; every rank
-                        # takes the same decisions, so the collectives stay in step)
-                        call(2 | 16 | (4 if skip_product else 0))
-                        self._allreduce(p_out)
-                        ar_ahead = True
-                        if fused_in:
-                            # ... and the next product behind it (not after an evaluation whose
-                            # stats a discard would continue from: its node sums must survive)
-                            check(self.lib.revs_plan_spec_step(
-                                self._plan, 64, ptr(self.yd[0]), 0, None, None, None, None, None, None,
-                                None, None, 0, ptr(p_out), ptr(p_in), None, None, None, None,
-                                self.stream), "revs_plan_spec_step")
-                            prod_ahead = True
-                        call(32)
-                fuse_out = p_out is not None
-                kept = rm.value / scale <= o.eps
-                # after a fused home pass the stats carry no dual value: a discarded sweep is
-                # followed by a fresh evaluation instead of a continuation from these stats
-                stt = None if (kept or fused_in) else self.stats_host[0].numpy().copy()
-                if kept and fuse_out:
-                    self._fused_ready, self._fused_p = True, p_out
-                    self._ar_ahead, self._prod_ahead = ar_ahead, prod_ahead
-            else:
-                self._dual_launch(self.yd[0], self._y_support, 0, full=False)
-                rec(1)
-                self.agent_step(write_sc, to_alt=True)
-                rec(2)
-                stt = self._dual_wait(0)
-                kept = stt[:, 0].max() / scale <= o.eps
-            if kept:
-                self.P_sch, self.P_sch_alt = self.P_sch_alt, self.P_sch
-                self.G, self.G_alt = self.G_alt, self.G
-                self.op_iters_hist.append(1)
-                self.op_path_hist.append("dual")
-                self.newton_hist.append((0, 1, 0))
-                self.op_converged = True
-                self.spec_hist[0] += 1
-                self._spec_back = 1
-            else:                          # rows need work: finish the solve, redo the sweep
-                self._spec_discard(stt, write_sc)
+            self._spec_step(write_sc)        # steady state: the multipliers of the last iteration are expected to stand
         elif o.solver == "newton" and o.chain and self._chain_ok:
-            # binding steady state: the last solve was one Newton iteration on the small model;
-            # enqueue the same again, and the sweep behind it, before reading anything
-            self._fused_ready = False
-            if not events and self._fold_ok():
+            if self._fold_ok():
                 self._chain_run(1, write_sc)         # (books the iteration itself)
                 return
-            self._fold_resume = False
-            if self._plan is not None and self.group is None:
-                # one native call: the six launches, the wait and the verdict
-                acc, nsum, nmax = C.c_int32(), C.c_int32(), C.c_int32()
-                evh = [None, None]
-                if events:
-                    for i in (1, 2):
-                        if not events[i].cuda_event:
-                            events[i].record()
-                        evh[i - 1] = events[i].cuda_event
-                sup0 = self._sup if (self._y_support and self._sup is not None) else -1
-                check(self.lib.revs_plan_chain_step(
-                    self._plan, ptr(self.yd[0]), ptr(self.yd[1]), int(self._y_support), sup0,
-                    int(self._chain_few), ptr(self.P_est), ptr(self.P_est_new), ptr(self.P_sch),
-                    ptr(self.G), ptr(self.P_sch_alt), ptr(self.G_alt),
-                    ptr(self.S) if write_sc else None, ptr(self.Csoc) if write_sc else None,
-                    C.addressof(acc), C.addressof(nsum), C.addressof(nmax), evh[0], evh[1],
-                    self.stream), "revs_plan_chain_step")
-                self._chain_finish(bool(acc.value), nsum.value, nmax.value, write_sc)
-            else:
-                self._chain_launch(write_sc, rec)
-                # (_chain_accept books the usual outcome itself)
-                if self._chain_accept():
-                    self.P_sch, self.P_sch_alt = self.P_sch_alt, self.P_sch
-                    self.G, self.G_alt = self.G_alt, self.G
-                    self.chain_hist[0] += 1
-                else:
-                    self._chain_finish(False, 0, 0, write_sc)
+            self._chain_step(write_sc)       # binding steady state: one Newton iteration enqueued unread
         else:
-            self._fused_ready = False
             self._require_converged(self.operator_solve())
-            rec(1)
             self.agent_step(write_sc)
-            rec(2)
         self.P_est, self.P_est_new = self.P_est_new, self.P_est
         if self._fused_ready:             # the next P_est_new is already in the spare buffer
             self.P_est_new, self.P_est_alt = self.P_est_alt, self.P_est_new
@@ -938,13 +880,11 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
 
     @_on_current_stream
     def run_steps(self, count):
-        """`count` iterations of step(write_sc=False).  Consecutive steady-state iterations
-        (one GPU, no multipliers, speculation on) run inside ONE native call,
-        revs_plan_spec_run -- the buffer rotation included, no Python between the launches --
-        which returns at the first sweep that has to be discarded; that iteration is finished
-        here as step() would, and the loop goes on.  Same trajectory as calling step()."""
+        """`count` iterations of step(write_sc=False).  Consecutive steady-state iterations run inside ONE native call
+        where one applies -- the streaming loop (_stream_run), the chained Newton iteration (_chain_run) or, one GPU
+        without the feeder's tree, revs_plan_spec_run (_spec_run) -- which returns at the first iteration it cannot
+        keep; that iteration is finished as step() would, and the loop goes on.  Same trajectory as calling step()."""
         o, done = self.op, 0
-        scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
         while done < count:
             if self._stream_ok():
                 if not self._fused_ready:            # entry: one step of the general driver
@@ -957,52 +897,10 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
             if ((native or (o.solver == "newton" and self._fold_ok())) and o.chain and self._chain_ok
                     and not (o.speculate and self._spec_ok)):
                 done += self._chain_run(count - done)        # (sharded: the folded chain only)
-                continue
-            if not (native and o.speculate and self._spec_ok and o.fuse_home_pass
-                    and not self._y_support):
+            elif native and o.speculate and self._spec_ok and o.fuse_home_pass and not self._y_support:
+                done += self._spec_run(count - done)
+            else:
                 self.step(write_sc=False)
-                done += 1
-                continue
-            p0 = self.pnq[0]
-            self._p_clear = None
-            if self._fused_ready and self._fused_p is self.p_alt2:     # (revs_plan_spec_run knows two arrays)
-                p0.copy_(self.p_alt2)
-                self._fused_p = p0
-            bufs = (self.P_est, self.P_est_new, self.P_est_alt, self.P_sch, self.P_sch_alt, self.G,
-                    self.G_alt)
-            st = _lib.SpecState(*[ptr(t) for t in bufs], ptr(p0), ptr(self.p_alt),
-                                ptr(self._fused_p) if self._fused_ready else None,
-                                int(self._fused_ready))
-            kept, fin, rm = C.c_int32(), C.c_int32(), C.c_double()
-            check(self.lib.revs_plan_spec_run(self._plan, count - done, ptr(self.yd[0]), C.byref(st),
-                                              scale, o.eps, C.addressof(kept), C.addressof(fin),
-                                              C.addressof(rm), self.stream), "revs_plan_spec_run")
-            n = kept.value
-            by = {t.data_ptr(): t for t in bufs}
-            self.P_est, self.P_est_new, self.P_est_alt = (by[st.p_est], by[st.p_est_new],
-                                                          by[st.p_est_alt])
-            self.P_sch, self.P_sch_alt = by[st.p_sch], by[st.p_sch_alt]
-            self.G, self.G_alt = by[st.gamma], by[st.gamma_alt]
-            self._fused_ready = bool(st.fused_ready)
-            if self._fused_ready:
-                self._fused_p = p0 if st.fused_p == p0.data_ptr() else self.p_alt
-            if n:
-                self.op_iters_hist.extend([1] * n)
-                self.op_path_hist.extend(["dual"] * n)
-                self.newton_hist.extend([(0, 1, 0)] * n)
-                self.op_converged = True
-                self.spec_hist[0] += n
-                self._spec_back = 1
-                self.iteration += n
-                done += n
-            if done < count and n < count - (done - n):
-                # the call stopped at a sweep to discard: finish that iteration as step() does
-                fused_in = bool(fin.value)
-                self._fused_ready = False
-                stt = None if fused_in else self.stats_host[0].numpy().copy()
-                self._spec_discard(stt, False)
-                self.P_est, self.P_est_new = self.P_est_new, self.P_est
-                self.iteration += 1
                 done += 1
 
     def check_status(self, launch_only=False, deferred=False):
@@ -1219,6 +1117,17 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         for h in (self.op_iters_hist, self.op_path_hist, self.newton_hist, self.stream_calls):
             h.clear()
         self.spec_hist, self.chain_hist, self.model_calls, self.fold_steps = [0, 0], [0, 0], [0, 0], 0
+
+    def _rebind(self, st, bufs, ys=()):
+        """Point the state tensors (with `ys`: the multipliers too) at the buffers a native call left them in: the
+        fields of its struct `st` hold their addresses, `bufs` / `ys` are the candidates.  Returns the address map."""
+        by = {t.data_ptr(): t for t in bufs + ys}
+        self.P_est, self.P_est_new = by[st.p_est], by[st.p_est_new]
+        self.P_sch, self.P_sch_alt = by[st.p_sch], by[st.p_sch_alt]
+        self.G, self.G_alt = by[st.gamma], by[st.gamma_alt]
+        if ys:
+            self.yd = [by[st.y], by[st.y_trial]]
+        return by
 
     def get_state(self):
         """(P_est[k], P_sch[k], G[k]) in the caller's home order."""

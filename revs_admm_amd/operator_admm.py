@@ -1,5 +1,5 @@
 """The operator QP (reference lpsolver.py:163-238) by ADMM in OSQP form -- the fallback of the
-dual Newton path (DESIGN.md section 3.4): home-space form, node-space fast path, rho calibration,
+dual Newton path (DESIGN.md section 3.3): home-space form, node-space fast path, rho calibration,
 hipGraph replay of inner-iteration blocks.  Methods of AdmmEngine (mixed in by engine.py); every
 number is computed by the kernels of csrc/operator_kernels.hip and csrc/gemm_kernels.hip."""
 from __future__ import annotations
@@ -191,8 +191,7 @@ class AdmmFormsMixin:
         return self.res_out.cpu().numpy()
 
     def _rel_residuals(self, r):
-        vscale = max(abs(self.vlo), abs(self.vhi), 1e-300)
-        n_pv = np.maximum(np.maximum(r[3], r[4]), vscale)
+        n_pv = np.maximum(np.maximum(r[3], r[4]), self._scale)
         n_pb = np.maximum(r[5], 1e-12)
         n_d = np.maximum(np.maximum(self.kappa * r[5], r[6]), np.maximum(r[7], 1e-12))
         return np.maximum(r[0] / n_pv, r[1] / n_pb), r[2] / n_d
@@ -277,8 +276,7 @@ class AdmmFormsMixin:
 
     def _fast_residuals(self):
         r = self.res_out.cpu().numpy()          # identical on every rank: no reduction needed
-        vscale = max(abs(self.vlo), abs(self.vhi), 1e-300)
-        rel_p = r[0] / np.maximum(np.maximum(r[3], r[4]), vscale)
+        rel_p = r[0] / np.maximum(np.maximum(r[3], r[4]), self._scale)
         rel_d = r[2] / np.maximum(np.maximum(self.kappa * r[5], r[6]), np.maximum(r[7], 1e-12))
         return rel_p, rel_d
 

@@ -5,6 +5,7 @@ Methods of AdmmEngine (mixed in by engine.py); kernels: csrc/newton_kernels.hip,
 from __future__ import annotations
 
 import ctypes as C
+import time
 
 import numpy as np
 import torch
@@ -52,7 +53,7 @@ class DualNewtonMixin:
             ptr(self.R64), ptr(self.c_idx[sup]), ptr(self.c_cnt[sup]), ptr(y), self.kappa,
             ptr(self.pnq), ptr(self.P_est_new), self.stream), "revs_op_dual_eval_rows")
 
-    def _dual_launch(self, y, use_y: bool, k: int, full: bool = True, sup=None, record=True, kadd=None, dense=False):
+    def _dual_launch(self, y, use_y: bool, k: int, full: bool = True, sup=None, kadd=None, dense=False):
         """Enqueue one evaluation: p, N, D and the voltage rows for the multipliers y;
         candidate lists and stats into buffer set k, stats on their way to pinned host
         memory.  Also writes P_est_new = max(g0 - R^T y / kappa, 0).  Does not wait.
@@ -82,18 +83,22 @@ class DualNewtonMixin:
         self._dual_phase(2, y, use_y, k)
         return self._dual_wait(k)
 
+    def _wait_tag(self, k: int, tag, err: str):
+        """Spin until every slot's record in stats block k (pinned host memory, written behind a system-scope fence)
+        carries `tag`; RevsError(err) after 120 s."""
+        tags = self.stats_host[k].numpy()[:, 5]
+        spins, t0 = 0, None
+        while not (tags == tag).all():
+            spins += 1
+            if spins & 0xFFF == 0:
+                t0 = t0 or time.monotonic()
+                if time.monotonic() - t0 > 120.0:
+                    raise _lib.RevsError(err)
+
     def _dual_wait(self, k: int):
         tag = self._pending_tag[k]
-        if self.stats_ev[k] is not None and tag is not None:
-            tags = self.stats_host[k].numpy()[:, 5]
-            spins, t0 = 0, None
-            while not (tags == tag).all():
-                spins += 1
-                if spins & 0xFFF == 0:
-                    import time
-                    t0 = t0 or time.monotonic()
-                    if time.monotonic() - t0 > 120.0:
-                        raise _lib.RevsError("operator evaluation: timed out waiting for its stats")
+        if self.dev.type == "cuda" and tag is not None:
+            self._wait_tag(k, tag, "operator evaluation: timed out waiting for its stats")
             # (consumed: a later wait on this block without a new evaluation of ours -- the
             # block may since have been written by a native loop, which waits itself -- just reads)
             self._pending_tag[k] = None
@@ -116,7 +121,7 @@ class DualNewtonMixin:
         if o.native_newton and self._plan is not None and (self.group is None or self._comm is not None):
             return self._operator_solve_newton_native(first, pre)
         A = _lib.DUAL_AMAX
-        scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
+        scale = self._scale
         self._fold_resume = False
         ycur, ytrial = self.yd
         cur = 0
@@ -228,28 +233,40 @@ class DualNewtonMixin:
         self.yd = [ycur, ytrial]
         if big:
             return self._operator_solve_newton_big(newton, evals, pivots)
+        if not ok_all:
+            ycur.zero_()
+        return self._solve_book(ok_all, newton, evals, pivots, stt[:, 2].sum(), stt[:, 2].max(), cur, last_small,
+                                pre_kept=ok_all and from_pre and newton <= 1, few=bool(few) if newton >= 1 else False)
+
+    def _solve_book(self, ok, newton, evals, pivots, nsup_sum, nsup_max, cur, last_small=False, pre_kept=False,
+                    few=False, arm=True):
+        """Book a finished operator solve through the dual (the Python loops' or the library's); False when it failed
+        (its multipliers are cleared: the caller's part).  `nsup_sum` / `nsup_max`: rows with a multiplier in all
+        slots / in the fullest; `cur`: the accepted evaluation's candidate set, which lists those rows first (None: not
+        to be used); `arm`: a solve without a Newton iteration counts down to speculation (the big model's leaves the
+        countdown alone)."""
+        o = self.op
         self.newton_hist.append((newton, evals, pivots))
-        self._pre_kept = bool(ok_all and from_pre and newton <= 1)
+        self._pre_kept = bool(pre_kept)
         # a solve of exactly one Newton iteration on the small model tends to repeat: the next
         # one is enqueued whole (_chain_launch)
-        self._chain_ok = bool(ok_all and newton == 1 and last_small and evals == 2)
-        self._chain_few = bool(few) if newton >= 1 else False
+        self._chain_ok = bool(ok and newton == 1 and last_small and evals == 2)
+        self._chain_few = bool(few)
         # speculate on the next iteration after a solve that needed no Newton iteration -- but
         # after a discarded sweep only once 2, 4, ... 64 such solves have gone by (rows that
         # keep moving in and out of their limits would otherwise cost a wasted sweep each time)
-        if ok_all and newton == 0:
+        if arm and ok and newton == 0:
             self._spec_wait = max(self._spec_wait - 1, 0)
             self._spec_ok = self._spec_wait == 0
         else:
             self._spec_ok = False
-        if not ok_all:
-            ycur.zero_()
+        if not ok:
             self._y_support = False
             self._sup = None
             return False
-        self._y_support = bool(stt[:, 2].sum() > 0)
-        # the accepted evaluation's candidate set `cur` lists the rows with y != 0 first
-        self._sup = cur if (self._y_support and stt[:, 2].max() + o.newton_kadd <= _lib.DUAL_FEW) else None
+        self._y_support = bool(nsup_sum > 0)
+        self._sup = (cur if (cur is not None and self._y_support and nsup_max + o.newton_kadd <= _lib.DUAL_FEW)
+                     else None)
         self.op_iters_hist.append(evals)
         self.op_path_hist.append("dual")
         self.op_converged = True
@@ -278,7 +295,7 @@ class DualNewtonMixin:
         the ADMM forms take the iteration, as before."""
         o, lib, M, T, st = self.op, self.lib, self.M, self.T, self.stream
         A2 = _lib.DUAL_AMAX_BIG
-        scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
+        scale = self._scale
         b = self._ensure_big()
         self._fold_resume = False
         self.big_solves = getattr(self, "big_solves", 0) + 1
@@ -331,19 +348,9 @@ class DualNewtonMixin:
             ycur, ytrial = ytrial, ycur
             stt = stn
         self.yd = [ycur, ytrial]
-        self.newton_hist.append((newton, evals, pivots))
-        self._pre_kept = self._chain_ok = self._chain_few = self._spec_ok = False
         if not ok_all:
             ycur.zero_()
-            self._y_support = False
-            self._sup = None
-            return False
-        self._y_support = bool(stt[:, 2].sum() > 0)
-        self._sup = None
-        self.op_iters_hist.append(evals)
-        self.op_path_hist.append("dual")
-        self.op_converged = True
-        return True
+        return self._solve_book(ok_all, newton, evals, pivots, stt[:, 2].sum(), 0, None, arm=False)
 
     def _operator_solve_newton_native(self, first, pre):
         """_operator_solve_newton's loop inside the library (revs_plan_newton_solve): same iterates and the
@@ -351,7 +358,6 @@ class DualNewtonMixin:
         0 / 1; the library works from the pinned blocks themselves and is told the tags the caller saw, so that a
         launch that touched a block in between is an error, not a silently different solve."""
         have_first, have_pre = first is not None, pre is not None
-        o = self.op
         self._fold_resume = False
         ys = (self.yd[0], self.yd[1])
         sup = self._sup if (self._y_support and self._sup is not None) else -1
@@ -367,28 +373,11 @@ class DualNewtonMixin:
         self.model_calls[1] += st.models_general
         if st.big_needed:                        # (y is where the loop stopped, not cleared)
             return self._operator_solve_newton_big(st.newton, st.evals, st.pivots)
-        ok_all, newton = bool(st.ok), st.newton
-        self.newton_hist.append((newton, st.evals, st.pivots))
-        self._pre_kept = bool(st.pre_kept)
-        self._chain_ok = bool(ok_all and newton == 1 and st.last_small and st.evals == 2)
-        self._chain_few = bool(st.few)
-        if ok_all and newton == 0:
-            self._spec_wait = max(self._spec_wait - 1, 0)
-            self._spec_ok = self._spec_wait == 0
-        else:
-            self._spec_ok = False
-        if not ok_all:
-            self._y_support = False
-            self._sup = None
-            return False
-        self._y_support = st.nsup_sum > 0
-        self._sup = st.cur if (self._y_support and st.nsup_max + o.newton_kadd <= _lib.DUAL_FEW) else None
-        self.op_iters_hist.append(st.evals)
-        self.op_path_hist.append("dual")
-        self.op_converged = True
-        return True
+        # (a failed solve's y was cleared by the library)
+        return self._solve_book(bool(st.ok), st.newton, st.evals, st.pivots, st.nsup_sum, st.nsup_max, st.cur,
+                                st.last_small, pre_kept=st.pre_kept, few=st.few)
 
-    def _chain_launch(self, write_sc, rec):
+    def _chain_launch(self, write_sc):
         """The binding steady state without the host in the loop: evaluation of the current
         multipliers (set 0) with its selection, the small model and the step in one launch
         (full step for the slots that evaluation leaves pending, decided on the device:
@@ -396,7 +385,7 @@ class DualNewtonMixin:
         sweep on its answer -- the trial's candidate selection rides in the sweep's launch --,
         all enqueued; nothing is read."""
         o, lib, M, T, st = self.op, self.lib, self.M, self.T, self.stream
-        scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
+        scale = self._scale
         ycur, ytrial = self.yd
         # (no event records in the chain: each costs the stream ~6 us; the host polls the
         # sequence tag the last selection writes)
@@ -435,7 +424,6 @@ class DualNewtonMixin:
         if self.group is not None:
             self._allreduce(self.pnq)
         self._dual_phase(2 | 4, ytrial, True, 1)  # product and rows; selection: in the sweep
-        rec(1)
         self._chain_seq -= 1.0
         check(lib.revs_agent_step_select(
             self.n, T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(self.P_est),
@@ -446,49 +434,57 @@ class DualNewtonMixin:
             o.newton_kadd, ptr(self.vfull), ptr(self.violw), ptr(self.c_idx[1]), ptr(self.c_cnt[1]),
             ptr(self.c_val[1]), self.stats_dev[1], self._chain_seq, None, None, None, nb, st),
             "revs_agent_step_select")
-        rec(2)
 
     def _chain_accept(self):
-        """Wait for the chain's two evaluations and, if they are the usual outcome -- one
-        Newton iteration on the small model, full step accepted, converged -- do the
-        bookkeeping _operator_solve_newton would do for it (revs_newton_chain_accept makes
-        the same checks in one native call).  False: nothing was changed."""
+        """Wait for the chain's two evaluations and test whether they are the usual outcome -- one Newton iteration on
+        the small model, full step accepted, converged -- in one native call (revs_newton_chain_accept).  Returns
+        (accepted, nsum, nmax) for _chain_finish; nothing is changed."""
         o = self.op
-        if self.stats_ev[0] is not None:
+        if self.dev.type == "cuda":
             # the trial's verdict is written early in the sweep's launch: poll its sequence tag
             # (pinned memory) rather than wait for the sweep; stream order puts everything the
             # chain wrote before it
-            tags = self.stats_host[1].numpy()[:, 5]
-            spins, t0 = 0, None
-            while not (tags == self._chain_seq).all():
-                spins += 1
-                if spins & 0xFFF == 0:
-                    import time
-                    t0 = t0 or time.monotonic()
-                    if time.monotonic() - t0 > 120.0:
-                        raise _lib.RevsError("chained Newton iteration: timed out waiting for "
-                                             "the evaluation's sequence tag")
+            self._wait_tag(1, self._chain_seq,
+                           "chained Newton iteration: timed out waiting for the evaluation's sequence tag")
         nsum, nmax = C.c_int32(), C.c_int32()
-        scale = max(abs(self.vlo), abs(self.vhi), 1e-300)
-        if not self.lib.revs_newton_chain_accept(
-                self.T, self.stats_host[0].data_ptr(), self.stats_host[1].data_ptr(), scale, o.eps,
-                _lib.DUAL_AMAX, o.newton_kadd, int(self._chain_few), C.addressof(nsum),
-                C.addressof(nmax)):
-            return False
-        self._chain_book(nsum.value, nmax.value)
-        return True
+        acc = self.lib.revs_newton_chain_accept(
+            self.T, self.stats_host[0].data_ptr(), self.stats_host[1].data_ptr(), self._scale, o.eps,
+            _lib.DUAL_AMAX, o.newton_kadd, int(self._chain_few), C.addressof(nsum), C.addressof(nmax))
+        return bool(acc), nsum.value, nmax.value
 
-    def _chain_book(self, nsum, nmax):
-        o = self.op
-        self.yd = [self.yd[1], self.yd[0]]
-        self.model_calls[0] += 1
-        self.newton_hist.append((1, 2, int(np.abs(self.info_h.numpy()).sum())))
+    def _chain_book(self, n, use_y, sup, pivots=-1):
+        """Book n kept chained iterations -- one Newton iteration on the small model and two evaluations each; the
+        multipliers' support and the candidate set `sup` listing their rows; `pivots`: the last model's pivot count
+        (-1: not read)."""
+        self.model_calls[0] += n
+        self.newton_hist.extend([(1, 2, pivots)] * n)
         self._pre_kept, self._chain_ok, self._spec_ok = True, True, False
-        self._y_support = nsum > 0
-        self._sup = 1 if (self._y_support and nmax + o.newton_kadd <= _lib.DUAL_FEW) else None
-        self.op_iters_hist.append(2)
-        self.op_path_hist.append("dual")
+        self._y_support = use_y
+        self._sup = sup
+        self.op_iters_hist.extend([2] * n)
+        self.op_path_hist.extend(["dual"] * n)
         self.op_converged = True
+
+    def _chain_step(self, write_sc):
+        """step() in the binding steady state where the folded chain does not apply: the last solve was one Newton
+        iteration on the small model; the same again and the sweep behind it are enqueued before anything is read --
+        one native call on a plan (one GPU: the six launches, the wait and the verdict), else issued from here."""
+        self._fused_ready = False
+        self._fold_resume = False
+        if self._plan is not None and self.group is None:
+            acc, nsum, nmax = C.c_int32(), C.c_int32(), C.c_int32()
+            sup0 = self._sup if (self._y_support and self._sup is not None) else -1
+            check(self.lib.revs_plan_chain_step(
+                self._plan, ptr(self.yd[0]), ptr(self.yd[1]), int(self._y_support), sup0,
+                int(self._chain_few), ptr(self.P_est), ptr(self.P_est_new), ptr(self.P_sch),
+                ptr(self.G), ptr(self.P_sch_alt), ptr(self.G_alt),
+                ptr(self.S) if write_sc else None, ptr(self.Csoc) if write_sc else None,
+                C.addressof(acc), C.addressof(nsum), C.addressof(nmax), None, None,
+                self.stream), "revs_plan_chain_step")
+            self._chain_finish(bool(acc.value), nsum.value, nmax.value, write_sc)
+        else:
+            self._chain_launch(write_sc)
+            self._chain_finish(*self._chain_accept(), write_sc)
 
     def _fold_ok(self):
         """The folded chain applies (revs_plan_chain_fold_run): the native plan (sharded: with the library's
@@ -519,13 +515,8 @@ class DualNewtonMixin:
         if self.group is not None:
             # sharded: ONE chained iteration issued in phases around the all-reduces of the node sums
             # (revs_plan_chain_run is the one-GPU loop), judged and booked as step() does
-            self._chain_launch(write_sc, lambda i: None)
-            if self._chain_accept():
-                self.P_sch, self.P_sch_alt = self.P_sch_alt, self.P_sch
-                self.G, self.G_alt = self.G_alt, self.G
-                self.chain_hist[0] += 1
-            else:
-                self._chain_finish(False, 0, 0, write_sc)
+            self._chain_launch(write_sc)
+            self._chain_finish(*self._chain_accept(), write_sc)
             self.P_est, self.P_est_new = self.P_est_new, self.P_est
             self.iteration += 1
             return 1
@@ -538,20 +529,9 @@ class DualNewtonMixin:
         check(self.lib.revs_plan_chain_run(self._plan, count, C.byref(st), int(self._chain_few),
                                            C.addressof(kept), self.stream), "revs_plan_chain_run")
         n = kept.value
-        by = {t.data_ptr(): t for t in bufs}
-        self.P_est, self.P_est_new = by[st.p_est], by[st.p_est_new]
-        self.P_sch, self.P_sch_alt = by[st.p_sch], by[st.p_sch_alt]
-        self.G, self.G_alt = by[st.gamma], by[st.gamma_alt]
-        self.yd = [ys[0], ys[1]] if st.y == ys[0].data_ptr() else [ys[1], ys[0]]
+        self._rebind(st, bufs, ys)
         if n:
-            self.model_calls[0] += n
-            self.newton_hist.extend([(1, 2, -1)] * n)      # (pivot counts not read)
-            self._pre_kept, self._chain_ok, self._spec_ok = True, True, False
-            self._y_support = bool(st.use_y)
-            self._sup = 1 if st.sup0 == 1 else None
-            self.op_iters_hist.extend([2] * n)
-            self.op_path_hist.extend(["dual"] * n)
-            self.op_converged = True
+            self._chain_book(n, bool(st.use_y), 1 if st.sup0 == 1 else None)
             self.chain_hist[0] += n
             self.iteration += n
         if n == count:
@@ -586,27 +566,16 @@ class DualNewtonMixin:
         check(self.lib.revs_plan_chain_fold_run(self._plan, count, C.byref(st), C.addressof(kept), self.stream),
               "revs_plan_chain_fold_run")
         n = kept.value
-        by = {t.data_ptr(): t for t in bufs + third}
-        self.P_est, self.P_est_new = by[st.p_est], by[st.p_est_new]
-        self.P_sch, self.P_sch_alt = by[st.p_sch], by[st.p_sch_alt]
-        self.G, self.G_alt = by[st.gamma], by[st.gamma_alt]
+        by = self._rebind(st, bufs + third, ys)
         self.P_est_alt = by[st.p_est_3]      # (any pool member that is neither P_est nor P_est_new)
         if ypool is not None:
             self.pdhg_dual = next(t for t in ypool if t.data_ptr() == st.pdhg_dual)      # (the plan points at it already)
-        yb = {t.data_ptr(): t for t in ys}
-        self.yd = [yb[st.y], yb[st.y_trial]]
-        self._y_spare = yb[st.y_spare]
+        self._y_spare = by[st.y_spare]
         stepped = st.resume == 2          # stopped behind a good Newton step that needs another: y is that step
         self._fold_resume = st.resume == 1
         if n:
-            self.model_calls[0] += n
-            self.newton_hist.extend([(1, 2, -1)] * n)      # (pivot counts not read)
-            self._pre_kept, self._chain_ok, self._spec_ok = True, True, False
-            self._y_support = bool(st.use_y)
-            self._sup = None         # (the lists of the accepted multipliers may sit in the plan's own sets)
-            self.op_iters_hist.extend([2] * n)
-            self.op_path_hist.extend(["dual"] * n)
-            self.op_converged = True
+            # (_sup: none -- the lists of the accepted multipliers may sit in the plan's own sets)
+            self._chain_book(n, bool(st.use_y), None)
             self.chain_hist[0] += n
             self.iteration += n
             if st.redone and st.resume == 1:   # the last kept iteration took more Newton steps inside the call
@@ -634,9 +603,7 @@ class DualNewtonMixin:
             self._book_step_before(st.pivots if stepped else 0, (1 if stepped else 0) + st.redone)
         self.chain_hist[1] += 1
         if not ok:
-            self._fast_cold = True
-            self.op_cold = True
-            self._require_converged(self.operator_solve(admm_only=True))
+            self._admm_take_over()
         self.agent_step(write_sc and n == 0)
         self.P_est, self.P_est_new = self.P_est_new, self.P_est
         self.iteration += 1
@@ -657,7 +624,9 @@ class DualNewtonMixin:
         general loop (which reuses the trial where it is exactly its own first step); keep the
         speculative sweep or run it again."""
         if accepted:
-            self._chain_book(nsum, nmax)
+            self.yd = [self.yd[1], self.yd[0]]
+            sup = 1 if (nsum > 0 and nmax + self.op.newton_kadd <= _lib.DUAL_FEW) else None
+            self._chain_book(1, nsum > 0, sup, int(np.abs(self.info_h.numpy()).sum()))
             ok = True
         else:                                # (the tag was seen: both blocks are complete)
             stt0, stn = (self.stats_host[0].numpy().copy(), self.stats_host[1].numpy().copy())
@@ -669,7 +638,5 @@ class DualNewtonMixin:
         else:
             self.chain_hist[1] += 1
             if not ok:
-                self._fast_cold = True
-                self.op_cold = True
-                self._require_converged(self.operator_solve(admm_only=True))
+                self._admm_take_over()
             self.agent_step(write_sc)

@@ -1,14 +1,15 @@
 """The steady state of lpsolver.solve_ADMM's loop (reference lpsolver.py:254-287) while the
-operator's multipliers are zero: bursts enqueued by the native loops -- revs_plan_stream_run_blocks
-(the default since round 3: eight iterations per launch, verdicts by blocks, four rotating sets of
-state buffers) or revs_plan_stream_run (every launch judges itself, section
-3.5) -- verdicts and the convergence record on the device; and what follows a failed verdict.
-Methods of AdmmEngine (mixed in by engine.py)."""
+operator's multipliers are expected to stand: the speculative iteration (the sweep enqueued behind
+the operator's first evaluation, kept if that evaluation finds every row within tolerance) and the
+bursts of the native loops -- revs_plan_stream_run_blocks (the default: verdicts by blocks, up to 32
+iterations per launch, four rotating sets of state buffers),
+revs_plan_stream_run (every launch judges itself) and, without the feeder's tree,
+revs_plan_spec_run -- and what follows a failed verdict.  Methods of AdmmEngine (mixed in by
+engine.py)."""
 from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _lib
@@ -29,6 +30,36 @@ def _dp(t) -> int:
 
 
 class SteadyStateMixin:
+    def _spec_book(self, n):
+        """n speculative or streamed sweeps kept: each iteration's operator solve was its one evaluation."""
+        self.op_iters_hist.extend([1] * n)
+        self.op_path_hist.extend(["dual"] * n)
+        self.newton_hist.extend([(0, 1, 0)] * n)
+        self.op_converged = True
+        self.spec_hist[0] += n
+        self._spec_back = 1
+
+    def _spec_finish(self, n, count, stt=None, hist=None):
+        """After a native loop that enqueued `count` steady-state iterations and kept the first n: book them.  With
+        n < count the verdict of iteration n failed (its sweep wrote to the spares only; every launch behind it was a
+        no-op): finish it as step() finishes a discarded speculative sweep, from the evaluation's stats `stt` when
+        they carry a dual value.  `hist`: row i receives the residences' diff of the i-th iteration.  Returns the
+        number of iterations done."""
+        if n:
+            self._spec_book(n)
+            self.iteration += n
+        if n == count:
+            if hist is not None:
+                self.diff.copy_(hist[n - 1])         # (self.diff: always the last iteration's)
+            return n
+        self._fused_ready = False
+        self._spec_discard(stt, False)
+        self.P_est, self.P_est_new = self.P_est_new, self.P_est
+        self.iteration += 1
+        if hist is not None:
+            hist[n].copy_(self.diff)
+        return n + 1
+
     def _spec_discard(self, stt, write_sc):
         """A speculative sweep whose evaluation found rows beyond tolerance: finish the Newton
         solve (from the evaluation's stats `stt` when they carry a dual value), run the sweep
@@ -39,10 +70,110 @@ class SteadyStateMixin:
         if stt is not None:
             stt = self._dual_complete(self.yd[0], self._y_support, 0)
         if not self._operator_solve_newton(first=stt):
-            self._fast_cold = True
-            self.op_cold = True
-            self._require_converged(self.operator_solve(admm_only=True))
+            self._admm_take_over()
         self.agent_step(write_sc)
+
+    def _spec_step(self, write_sc):
+        """step() while the multipliers of the last iteration are expected to stand: the operator's first evaluation
+        and the sweep on its answer (into the spare buffers) enqueued together, the sweep kept if the evaluation finds
+        every row within tolerance.  On a plan one native call, revs_plan_spec_step (sharded: in phases around the
+        exchanges of the node sums); else issued from here."""
+        o = self.op
+        self._fold_resume = False
+        if self._plan is not None:               # one native call: enqueue, wait, judge
+            rm = C.c_double()
+            fused_in = self._fused_ready
+            p0 = self.pnq[0]
+            p_in = self._fused_p if fused_in else p0
+            p_out = None
+            if o.fuse_home_pass and not self._y_support:
+                p_out = self.p_alt if p_in.data_ptr() == p0.data_ptr() else p0
+            self._fused_ready = False
+
+            def call(phase):
+                check(self.lib.revs_plan_spec_step(
+                    self._plan, phase, ptr(self.yd[0]), int(self._y_support), ptr(self.P_est),
+                    ptr(self.P_est_new), ptr(self.P_sch), ptr(self.G), ptr(self.P_sch_alt),
+                    ptr(self.G_alt), ptr(self.S) if write_sc else None,
+                    ptr(self.Csoc) if write_sc else None, int(fused_in), ptr(p_in), ptr(p_out),
+                    ptr(self.P_est_alt), C.byref(rm), None, None, self.stream), "revs_plan_spec_step")
+            ar_ahead = prod_ahead = False
+            skip_product = fused_in and self._ar_ahead and self._prod_ahead
+            if self.group is None:
+                call(3)
+            else:                                # home pass, exchange of p, the rest
+                if not fused_in:
+                    call(1)
+                if not (fused_in and self._ar_ahead):
+                    self._allreduce(p_in)        # the only exchange of the iteration
+                self._ar_ahead = self._prod_ahead = False
+                if p_out is None:
+                    call(2 | (4 if skip_product else 0))
+                else:
+                    # enqueue product and sweep, then -- before waiting for the verdict --
+                    # the exchange of the node sums this sweep leaves for the NEXT
+                    # evaluation: it is stream-ordered behind the sweep, and its host-side
+                    # cost overlaps the sweep instead of standing between two iterations
+                    # (a discarded sweep makes it a wasted, harmless exchange; every rank
+                    # takes the same decisions, so the collectives stay in step)
+                    call(2 | 16 | (4 if skip_product else 0))
+                    self._allreduce(p_out)
+                    ar_ahead = True
+                    if fused_in:
+                        # ... and the next product behind it (not after an evaluation whose
+                        # stats a discard would continue from: its node sums must survive)
+                        check(self.lib.revs_plan_spec_step(
+                            self._plan, 64, ptr(self.yd[0]), 0, None, None, None, None, None, None,
+                            None, None, 0, ptr(p_out), ptr(p_in), None, None, None, None,
+                            self.stream), "revs_plan_spec_step")
+                        prod_ahead = True
+                    call(32)
+            kept = rm.value / self._scale <= o.eps
+            # after a fused home pass the stats carry no dual value: a discarded sweep is
+            # followed by a fresh evaluation instead of a continuation from these stats
+            stt = None if (kept or fused_in) else self.stats_host[0].numpy().copy()
+            if kept and p_out is not None:
+                self._fused_ready, self._fused_p = True, p_out
+                self._ar_ahead, self._prod_ahead = ar_ahead, prod_ahead
+        else:
+            self._dual_launch(self.yd[0], self._y_support, 0, full=False)
+            self.agent_step(write_sc, to_alt=True)
+            stt = self._dual_wait(0)
+            kept = stt[:, 0].max() / self._scale <= o.eps
+        if kept:
+            self.P_sch, self.P_sch_alt = self.P_sch_alt, self.P_sch
+            self.G, self.G_alt = self.G_alt, self.G
+            self._spec_book(1)
+        else:                          # rows need work: finish the solve, redo the sweep
+            self._spec_discard(stt, write_sc)
+
+    def _spec_run(self, count):
+        """Up to `count` speculative iterations inside ONE native call, revs_plan_spec_run (one GPU, no multipliers,
+        the fused home pass; the buffer rotation included, no Python between the launches), which returns at the
+        first sweep that has to be discarded.  Returns the number of iterations done."""
+        p0 = self.pnq[0]
+        self._p_clear = None
+        if self._fused_ready and self._fused_p is self.p_alt2:     # (revs_plan_spec_run knows two arrays)
+            p0.copy_(self.p_alt2)
+            self._fused_p = p0
+        bufs = (self.P_est, self.P_est_new, self.P_est_alt, self.P_sch, self.P_sch_alt, self.G,
+                self.G_alt)
+        st = _lib.SpecState(*[ptr(t) for t in bufs], ptr(p0), ptr(self.p_alt),
+                            ptr(self._fused_p) if self._fused_ready else None,
+                            int(self._fused_ready))
+        kept, fin, rm = C.c_int32(), C.c_int32(), C.c_double()
+        check(self.lib.revs_plan_spec_run(self._plan, count, ptr(self.yd[0]), C.byref(st),
+                                          self._scale, self.op.eps, C.addressof(kept), C.addressof(fin),
+                                          C.addressof(rm), self.stream), "revs_plan_spec_run")
+        n = kept.value
+        by = self._rebind(st, bufs)
+        self.P_est_alt = by[st.p_est_alt]
+        self._fused_ready = bool(st.fused_ready)
+        if self._fused_ready:
+            self._fused_p = p0 if st.fused_p == p0.data_ptr() else self.p_alt
+        # (the stats of a discarded sweep's evaluation carry a dual value unless it followed a fused home pass)
+        stt = None if (n == count or fin.value) else self.stats_host[0].numpy().copy()
+        return self._spec_finish(n, count, stt)
 
     def _stream_ok(self):
         """The steady state as one launch per iteration (revs_plan_stream_run) applies: a plan
@@ -100,36 +231,23 @@ class SteadyStateMixin:
                                             self._stream_out_ref[0], self._stream_out_ref[1], self.stream),
               "revs_plan_stream_run")
         n = kept.value
-        self.stream_calls.append((count, n))
-        self._burst = min(4 * self._burst, o.stream_burst_max) if n == count else o.stream_burst
         self.P_est, self.P_est_new, self.P_est_alt = (by[st.p_est[i]] for i in range(3))
         self.P_sch, self.P_sch_alt = by[st.p_sch[0]], by[st.p_sch[1]]
         self.G, self.G_alt = by[st.gamma[0]], by[st.gamma[1]]
         self._fused_p = by[st.p[0]]
         self._p_clear = by[st.p[1]] if n == count else None
+        return self._stream_finish(count, n, hist)
+
+    def _stream_finish(self, count, n, hist):
+        """The rest of a streaming burst of `count` launches of which n were kept: its record, the next burst's
+        length (x4 after a fully kept one, back to stream_burst after a failed verdict), the node sums the loop
+        left exchanged (sharded) but not multiplied, and the booking."""
+        o = self.op
+        self.stream_calls.append((count, n))
+        self._burst = min(4 * self._burst, o.stream_burst_max) if n == count else o.stream_burst
         self._prod_ahead = False
         self._ar_ahead = self.group is not None
-        if n:
-            self.op_iters_hist.extend([1] * n)
-            self.op_path_hist.extend(["dual"] * n)
-            self.newton_hist.extend([(0, 1, 0)] * n)
-            self.op_converged = True
-            self.spec_hist[0] += n
-            self._spec_back = 1
-            self.iteration += n
-        if n == count:
-            if hist is not None:
-                self.diff.copy_(hist[n - 1])         # (self.diff: always the last iteration's)
-            return n
-        # iteration n's verdict failed (its sweep wrote to the spares only; every launch behind
-        # it was a no-op): finish it as step() does for a discarded speculative sweep
-        self._fused_ready = False
-        self._spec_discard(None, False)
-        self.P_est, self.P_est_new = self.P_est_new, self.P_est
-        self.iteration += 1
-        if hist is not None:
-            hist[n].copy_(self.diff)
-        return n + 1
+        return self._spec_finish(n, count, None, hist)
 
     def _state_pools(self):
         """The pools the residences' state buffers rotate through (allocated on first use): four sets for the
@@ -189,8 +307,6 @@ class SteadyStateMixin:
                                                    self._dmax_addr, self.stream),
               "revs_plan_stream_run_blocks")
         n = kept.value
-        self.stream_calls.append((count, n))
-        self._burst = min(4 * self._burst, o.stream_burst_max) if n == count else o.stream_burst
         self.P_est, self.P_est_alt = by[st.p_est[0]], by[st.p_est[1]]
         self.P_sch, self.P_sch_alt = by[st.p_sch[0]], by[st.p_sch[1]]
         self.G, self.G_alt = by[st.gamma[0]], by[st.gamma[1]]
@@ -199,29 +315,8 @@ class SteadyStateMixin:
         self._sets_sig = ((id(self.P_est), id(self.P_est_new), id(self.P_sch), id(self.G), id(self.pdhg_dual))
                           if n == count else None)
         self._p_clear = None
-        self._prod_ahead = False
-        self._ar_ahead = self.group is not None
         if n == count:
             self._fused_p = p0_out
-        it = self.iteration
         if n:
-            self._max_diff_bursts.append((it, self._dmax_buf[:n]))      # (folded into max_diff when it is next read)
-        if n:
-            self.op_iters_hist.extend([1] * n)
-            self.op_path_hist.extend(["dual"] * n)
-            self.newton_hist.extend([(0, 1, 0)] * n)
-            self.op_converged = True
-            self.spec_hist[0] += n
-            self._spec_back = 1
-            self.iteration += n
-        if n == count:
-            if hist is not None:
-                self.diff.copy_(hist[n - 1])
-            return n
-        self._fused_ready = False
-        self._spec_discard(None, False)
-        self.P_est, self.P_est_new = self.P_est_new, self.P_est
-        self.iteration += 1
-        if hist is not None:
-            hist[n].copy_(self.diff)
-        return n + 1
+            self._max_diff_bursts.append((self.iteration, self._dmax_buf[:n]))   # (folded into max_diff when next read)
+        return self._stream_finish(count, n, hist)
