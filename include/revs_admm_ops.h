@@ -404,6 +404,50 @@ int revs_op_dual_step_big(int32_t T, const int64_t *cand_idx, const int32_t *can
                           const double *yhat, const double *alpha, const double *y, int32_t m, double *y_trial,
                           double *lin_out, void *stream);
 
+/* ---- network report: line flows, line loading and node voltages of a home profile -------------------------------
+ * What the reference draws for every result (drawing.py:29-78, compute_flows / compute_voltage), from the feeder as
+ * a tree (revs_tree_t, revs_admm.h) instead of the inverse of the incidence matrix:
+ *   flow[e][t]    = power through the line from tree node e to its parent = sum of g over the residences in e's subtree
+ *   loading[e][t] = |flow| / rating[e]                      (NaN where the line has no rating)
+ *   volt[n][t]    = sqrt(vset^2 - (R g)[n][t]) at EVERY tree node; NaN where the radicand is negative (the collapse of
+ *                   LinDistFlow under an impossible load: numpy gives the reference the same NaN), never a trap
+ * and per slot one revs_net_summary_t for loading (over the rated lines) and one for volt (over the masked nodes):
+ * the numbers of the reference's box plots (matplotlib.cbook.boxplot_stats: quartiles by numpy.percentile's linear
+ * interpolation, whiskers at the farthest datum within 1.5 IQR of the box, fliers beyond them) and the operator's
+ * first questions.  Order statistics are exact.  NaNs are counted and left out of the statistics.
+ *
+ * revs_net_node_sums: node_g[m][t] = sum over the homes of node m (node_ptr: CSR offsets int64[m + 1], homes sorted by
+ * node) of (double) load[h][t] + (double) p[h][t]; load may be NULL (p alone).  One accumulator per (node, slot), the
+ * homes in ascending index: the same bits from call to call, and -- residences sharded with every node's homes on
+ * one rank -- after the all-reduce (which then adds exact zeros) the same bits for any number of ranks.
+ *
+ * revs_net_report: one workgroup per slot, every tree shape up to REVS_TREE_MAX.  Device arrays by preorder position
+ * (tree->n entries): rating (double; <= 0: unrated, left out of loading; NULL: no line is rated), node_mask (uint8, 0:
+ * left out of the voltage summary; NULL: every node), node_of_pos (int32: the caller's index of the node at that
+ * position, outside 0..n_out-1: a padding position, nothing is written for it; NULL: the position itself).  node_g
+ * double[m][T].  Outputs, each may be NULL but not all: flow_out, loading_out, volt_out double[n_out][T] in the
+ * caller's node order, summary_out revs_net_summary_t[2][T] ([0]: loading, [1]: volt).  Reads nothing else and writes
+ * nothing else.  REVS_EINVAL: T outside 1..REVS_MAX_T, a null tree or node_g, a tree over REVS_TREE_MAX or not padded,
+ * n_out outside 1..tree->n, vset not finite, vmin > vmax, every output NULL. */
+typedef struct {
+    double min, q1, median, q3, max;   /* of the `count` values summarised (NaN when count == 0) */
+    double whisker_lo, whisker_hi;     /* the farthest values within 1.5 (q3 - q1) of the box */
+    double worst_value;                /* loading: the largest; volt: the voltage of worst_index */
+    int32_t count;                     /* values summarised: rated lines / masked nodes, NaNs left out */
+    int32_t n_fliers;                  /* values beyond the whiskers */
+    int32_t n_violations;              /* loading > 1; volt outside [vmin, vmax] */
+    int32_t n_nan;                     /* rated lines / masked nodes whose value is a NaN */
+    int32_t worst_index;               /* caller's index of the line of largest loading / of the node farthest outside
+                                        * (or nearest to the edge of) [vmin, vmax]; the lowest on ties; -1: count == 0 */
+    int32_t reserved[3];
+} revs_net_summary_t;                  /* 96 bytes */
+int revs_net_node_sums(int32_t m, int32_t T, const int64_t *node_ptr, const float *load, const float *p,
+                       double *node_g, void *stream);
+int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree_host, const double *node_g, const double *rating,
+                    const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out, double vset, double vmin,
+                    double vmax, double *flow_out, double *loading_out, double *volt_out,
+                    revs_net_summary_t *summary_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

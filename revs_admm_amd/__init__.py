@@ -3,6 +3,8 @@
     lpsolver       the reference's call surface (solve_ADMM, solve_residence, compute_Rmat)
     revs_fixture   REVS class (read_inputs / get_*_optimal) over the engine
     engine         array-level AdmmEngine: device buffers + kernel driver
+    network        AdmmEngine.network_report: line flows / loading, node voltages and their box-plot numbers
+    drawing        the reference's compute_flows / compute_voltage over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)
 

@@ -1,0 +1,539 @@
+// The network report (include/revs_admm_ops.h, "network report"): what the feeder looks like under a home
+// profile -- the power through every line, its loading, the voltage of every node, and per slot the box-plot
+// numbers of loading and voltage -- from the tree form of tree_body.h, one workgroup per slot.
+//
+//   revs_net_node_sums   node_g[m][t] = sum over the homes of m of (double) load + (double) p, one thread per
+//                        (node, slot), the homes in ascending index, one accumulator: a fixed order
+//   revs_net_report      net_report_kernel<NT, IPT>, the four shapes of tree_shape()
+//
+// The scans are tree_scan's (tree_body.h), restated here with the two intermediate values kept that tree_scan
+// multiplies away or masks: C[end_j] - C[j], the load of j's subtree, IS the flow of the line above j, and
+// Pre[j] - F[cle_j] IS the voltage drop at j, checked row or not.  tree_body.h is not touched: the sweep's and the
+// operator's kernels compile from the same text as before.
+//
+// The summary's order statistics are exact and need no sort.  Every value summarised is a non-negative double
+// (|flow| / rating, a square root), so its bit pattern orders like the value; the k-th smallest key is built bit by
+// bit from the top, one count of "keys below the trial" per bit, for the three quartile ranks of both quantities at
+// once: 63 rounds of IPT x 6 compares per thread (the compare's lane mask, a population count: no cross-lane
+// reduction) and ONE barrier each, on values that never leave the registers.  A bitonic sort of the same 16 384
+// doubles is 55 barrier-separated stages per quantity with 128 KB of LDS traffic in each.
+#include "common.h"
+#include "tree_body.h"
+
+#include <math.h>
+
+namespace revs {
+
+__global__ void net_node_sums_kernel(int m, int Ts, const int64_t *node_ptr, const float *load, const float *p,
+                                     double *out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= m * Ts) return;
+    const int node = idx / Ts, t = idx - node * Ts;
+    const int64_t i0 = node_ptr[node], i1 = node_ptr[node + 1];
+    double acc = 0.0;
+    if (load) {
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) acc += (double)load[i * Ts + t] + (double)p[i * Ts + t];
+    } else {
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) acc += (double)p[i * Ts + t];
+    }
+    out[idx] = acc;
+}
+
+struct NetArgs {
+    TreeArgs tr;
+    const double *g;              // node sums double[m][T]
+    const double *rating;         // per position, or NULL
+    const uint8_t *mask;          // per position, or NULL
+    const int32_t *nop;           // node_of_pos, or NULL (identity)
+    int32_t m, T, n_out;
+    double vset2, vmin, vmax;
+    double *flow, *loading, *volt;
+    revs_net_summary_t *sum;      // [2][T], or NULL
+};
+
+constexpr unsigned long long kNoKey = ~0ull;     // an entry left out of the summary (no trial key is above 2^63)
+constexpr int kNetRed = 8;                       // values one block reduction carries
+
+// doubles behind the scans' LDS: kNetRed per wavefront for the reductions, two count buffers of 16 bytes per wavefront
+__host__ __device__ inline size_t net_lds_bytes(int n) {
+    const TreeShape sh = tree_shape(n);
+    return tree_lds_bytes(n) + sizeof(double) * (size_t)(sh.nt / 64) * (kNetRed + 4);
+}
+
+__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {      // a value every lane holds, into SGPRs
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (unsigned long long)hi << 32 | lo;
+}
+__device__ __forceinline__ double uniform_d(double v) {
+    return __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(v)));
+}
+
+// max / sum of N values over the workgroup, every thread gets them; `red`: NT / 64 * kNetRed doubles.  Sums are of
+// counts (exact in doubles: any order gives the same bits).
+template <int NT, int N, bool SUM>
+__device__ __forceinline__ void block_reduce_multi(double (&v)[N], double *red) {
+    static_assert(N <= kNetRed, "");
+    const int tid = threadIdx.x, wave = tid >> 6;
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = SUM ? wave_sum_d(v[e]) : wave_max_d(v[e]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) red[wave * kNetRed + e] = v[e];
+    }
+    __syncthreads();
+    // the wavefronts' values across the first NT / 64 lanes of a row of 16, combined by rotations inside the row (one
+    // load per value in flight, not NT / 64), then into SGPRs: every lane holds the same
+    const int lane = tid & 63;
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        double r = lane < NT / 64 ? red[lane * kNetRed + e] : (SUM ? 0.0 : -__builtin_inf());
+        r = SUM ? r + dpp_rot_d<0x128>(r) : fmax(r, dpp_rot_d<0x128>(r));          // (all four: every lane of the row
+        r = SUM ? r + dpp_rot_d<0x124>(r) : fmax(r, dpp_rot_d<0x124>(r));          //  ends with the row's total)
+        r = SUM ? r + dpp_rot_d<0x122>(r) : fmax(r, dpp_rot_d<0x122>(r));
+        r = SUM ? r + dpp_rot_d<0x121>(r) : fmax(r, dpp_rot_d<0x121>(r));
+        v[e] = uniform_d(r);
+    }
+    __syncthreads();
+}
+
+__device__ __forceinline__ double key_val(unsigned long long k) { return __longlong_as_double((long long)k); }   // kNoKey: a NaN
+
+// numpy.percentile's linear interpolation between the order statistics a <= b at fraction t (_lerp), without
+// contraction to fused multiply-adds: the same roundings as numpy's
+__device__ __forceinline__ double np_lerp(double a, double b, double t) {
+    const double d = __dsub_rn(b, a);
+    return t >= 0.5 ? __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, t))) : __dadd_rn(a, __dmul_rn(d, t));
+}
+
+// flow_j = C[end_j] - C[j] at this thread's positions (a), C the inclusive prefix of the injections in preorder.
+// se[i]: the low half of pack (src + 1 | end << 16).  Ends behind a barrier: every read of C is done.
+template <int NT, int IPT>
+__device__ __forceinline__ void net_flow_scan(const NetArgs &A, int t, double *lds, const unsigned (&se)[IPT], double (&a)[IPT]) {
+    const int tid = threadIdx.x, j0 = IPT * tid;
+    const bool act = j0 < A.tr.n;
+    double *base = lds + 2, *red0 = lds + 2 + NT * IPT;
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {          // (positions without a row fetch row 0: straight-line loads, masked behind them)
+        const int s = (int)(se[i] & 0xFFFFu) - 1;
+        const bool ok = act && s >= 0 && s < A.m;
+        const double v = A.g[(int64_t)(ok ? s : 0) * A.T + t];
+        a[i] = ok ? v : 0.0;
+    }
+#pragma unroll
+    for (int i = 1; i < IPT; ++i) a[i] += a[i - 1];
+    const double cex = block_excl_offset<NT>(a[IPT - 1], red0);
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2)
+            *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i] + cex, a[i + 1] + cex}};
+    }
+    __syncthreads();
+    if (act) {
+#pragma unroll
+        for (int i = IPT - 1; i >= 1; --i) a[i] = base[(int)(se[i] >> 16) - 1] - (a[i - 1] + cex);
+        a[0] = base[(int)(se[0] >> 16) - 1] - cex;
+    }
+    __syncthreads();
+}
+
+// A chunk's caller-side node indices (-1: a padding position or a thread beyond the tree), ratings and mask bits:
+// one branch on the optional array, vector loads behind it.
+constexpr int kNetChunk = 8;       // positions whose side data (index, rating, mask) are in flight at once: the 1024 x 16
+                                   // shape takes its 16 in two halves, fenced for the scheduler, to stay inside 128 registers
+#define NET_CHUNK_FENCE() __builtin_amdgcn_sched_barrier(0)
+template <int IPT>
+__device__ __forceinline__ void net_load_nd(const NetArgs &A, bool act, int jl, int (&nd)[IPT]) {
+    if (A.nop) {
+#pragma unroll
+        for (int i = 0; i < IPT; i += 4) {
+            const int4 u = *reinterpret_cast<const int4 *>(A.nop + jl + i);
+            nd[i] = u.x; nd[i + 1] = u.y; nd[i + 2] = u.z; nd[i + 3] = u.w;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) nd[i] = jl + i;
+    }
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) nd[i] = (act && nd[i] >= 0 && nd[i] < A.n_out) ? nd[i] : -1;
+}
+template <int IPT>
+__device__ __forceinline__ void net_load_rating(const NetArgs &A, int jl, double (&r)[IPT]) {
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) r[i] = 0.0;
+    if (A.rating) {
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2) {
+            const TreeD2 u = *reinterpret_cast<const TreeD2 *>(A.rating + jl + i);
+            r[i] = u.v[0]; r[i + 1] = u.v[1];
+        }
+    }
+}
+
+// The key a line's loading enters the summary by (kNoKey: unrated, a padding position or a NaN), and the loading.
+__device__ __forceinline__ unsigned long long net_loading_key(double flow, double r, bool valid, double &ld) {
+    ld = r > 0.0 ? fabs(flow) / r : __builtin_nan("");
+    return (valid && ld == ld) ? (unsigned long long)__double_as_longlong(ld + 0.0) : kNoKey;
+}
+
+template <int NT, int IPT>
+__global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
+    extern __shared__ double net_lds[];
+    double *lds = net_lds;
+    const TreeArgs &tr = A.tr;
+    const int tid = threadIdx.x, t = (int)blockIdx.x, T = A.T, n = tr.n, j0 = IPT * tid;
+    const bool act = j0 < n;
+    const int jl = act ? j0 : 0;                                    // (threads beyond the tree load position 0's data, unused)
+    double *base = lds + 2, *red0 = lds + 2 + NT * IPT, *red1 = red0 + NT / 64;
+    double *red = red1 + NT / 64;                                   // block_reduce_multi's
+    unsigned long long *cbuf = reinterpret_cast<unsigned long long *>(red + (NT / 64) * kNetRed);   // [2][NT / 64][2]
+    // Registers: the 1024 x 16 shape has 128 per thread, and IPT doubles are 2 IPT of them.  The packed indices are
+    // held as the half a phase needs; and where IPT = 16 the loading keys are not carried through the voltage
+    // scans beside a, b and those indices -- the flow scan is run again behind them (the same bits: its order is
+    // fixed), two barriers against spills inside the selection's 63 rounds.
+    constexpr bool kRescan = IPT > 8;
+    if (tid == 0) lds[1] = 0.0;                                     // base[-1]
+
+    double a[IPT], b[IPT];
+    unsigned long long lkey[IPT], vkey[IPT];
+    double nanl = 0.0, nanv = 0.0;                                  // rated lines / masked nodes whose value is a NaN
+    {
+        unsigned se[IPT];
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2) {
+            const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + i);
+            se[i] = (unsigned)u.v[0]; se[i + 1] = (unsigned)u.v[1];
+        }
+        net_flow_scan<NT, IPT>(A, t, lds, se, a);
+    }
+    // ---- flow and loading out; w' = w flow
+#pragma unroll
+    for (int c = 0; c < IPT; c += kNetChunk) {
+        int nd[kNetChunk];
+        double r[kNetChunk];
+        net_load_nd<kNetChunk>(A, act, jl + c, nd);
+        net_load_rating<kNetChunk>(A, jl + c, r);
+        if (A.flow) {
+#pragma unroll
+            for (int i = 0; i < kNetChunk; ++i)
+                if (nd[i] >= 0) A.flow[(int64_t)nd[i] * T + t] = a[c + i];
+        }
+#pragma unroll
+        for (int i = 0; i < kNetChunk; ++i) {
+            const bool rated = nd[i] >= 0 && r[i] > 0.0;
+            const unsigned long long k = net_loading_key(a[c + i], r[i], rated, r[i]);      // (r: the loading from here)
+            if constexpr (!kRescan) {
+                lkey[c + i] = k;
+                nanl += (rated && k == kNoKey) ? 1.0 : 0.0;
+            }
+        }
+        if (A.loading) {
+#pragma unroll
+            for (int i = 0; i < kNetChunk; ++i)
+                if (nd[i] >= 0) A.loading[(int64_t)nd[i] * T + t] = r[i];
+        }
+#pragma unroll
+        for (int i = 0; i < kNetChunk; i += 2) {
+            const TreeD2 wv = *reinterpret_cast<const TreeD2 *>(tr.w + jl + c + i);
+            a[c + i] = act ? a[c + i] * wv.v[0] : 0.0; a[c + i + 1] = act ? a[c + i + 1] * wv.v[1] : 0.0;
+        }
+        NET_CHUNK_FENCE();
+    }
+    if (act) {
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2) *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i], a[i + 1]}};
+    }
+    __syncthreads();
+
+    // ---- the same values in end-order, both prefixes, drop_j = Pre[j] - F_excl[cle_j]
+    {
+        unsigned ec[IPT];                                           // eo | cle << 16
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2) {
+            const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + i);
+            ec[i] = (unsigned)(u.v[0] >> 32); ec[i + 1] = (unsigned)(u.v[1] >> 32);
+        }
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) b[i] = act ? base[(int)(ec[i] & 0xFFFFu)] : 0.0;
+#pragma unroll
+        for (int i = 1; i < IPT; ++i) { a[i] += a[i - 1]; b[i] += b[i - 1]; }
+        const double pex = block_excl_offset<NT>(a[IPT - 1], red1); // (its barrier: every read of w' is done)
+        const double fex = block_excl_offset<NT>(b[IPT - 1], red0);
+        if (act) {
+#pragma unroll
+            for (int i = 0; i < IPT; i += 2)
+                *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{b[i] + fex, b[i + 1] + fex}};
+        }
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < IPT; c += kNetChunk) {
+            int nd[kNetChunk];
+            net_load_nd<kNetChunk>(A, act, jl + c, nd);
+            const unsigned long long mk = A.mask ? *reinterpret_cast<const unsigned long long *>(A.mask + jl + c) : ~0ull;
+#pragma unroll
+            for (int i = 0; i < kNetChunk; ++i) {
+                const bool in = nd[i] >= 0 && ((mk >> (8 * i)) & 0xFFu) != 0ull;
+                const double x = A.vset2 - ((a[c + i] + pex) - base[act ? (int)(ec[c + i] >> 16) - 1 : -1]);
+                const double v = x < 0.0 ? __builtin_nan("") : sqrt(x);      // (collapse under LinDistFlow: a NaN, as numpy's)
+                if (A.volt && nd[i] >= 0) A.volt[(int64_t)nd[i] * T + t] = v;
+                vkey[c + i] = (in && v == v) ? (unsigned long long)__double_as_longlong(v + 0.0) : kNoKey;
+                nanv += (in && v != v) ? 1.0 : 0.0;
+            }
+            NET_CHUNK_FENCE();
+        }
+    }
+    if (!A.sum) return;
+    if constexpr (kRescan) {
+        __syncthreads();                                            // (every read of F is done)
+        unsigned se[IPT];
+#pragma unroll
+        for (int i = 0; i < IPT; i += 2) {
+            const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + i);
+            se[i] = (unsigned)u.v[0]; se[i + 1] = (unsigned)u.v[1];
+        }
+        net_flow_scan<NT, IPT>(A, t, lds, se, a);
+#pragma unroll
+        for (int c = 0; c < IPT; c += kNetChunk) {
+            int nd[kNetChunk];
+            double r[kNetChunk];
+            net_load_nd<kNetChunk>(A, act, jl + c, nd);
+            net_load_rating<kNetChunk>(A, jl + c, r);
+#pragma unroll
+            for (int i = 0; i < kNetChunk; ++i) {
+                const bool rated = nd[i] >= 0 && r[i] > 0.0;
+                lkey[c + i] = net_loading_key(a[c + i], r[i], rated, r[i]);
+                nanl += (rated && lkey[c + i] == kNoKey) ? 1.0 : 0.0;
+            }
+            NET_CHUNK_FENCE();
+        }
+    }
+
+    // ---- counts and extremes
+    const double ninf = -__builtin_inf();
+    double s[6] = {0.0, 0.0, nanl, nanv, 0.0, 0.0};                 // values, NaNs, violations of {loading, volt}
+    double x[5] = {ninf, ninf, ninf, ninf, ninf};                   // -min L, max L, -min V, max V, largest excursion of V
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+        const double l = key_val(lkey[i]), v = key_val(vkey[i]);
+        if (lkey[i] != kNoKey) {
+            s[0] += 1.0; s[4] += l > 1.0 ? 1.0 : 0.0;
+            x[0] = fmax(x[0], -l); x[1] = fmax(x[1], l);
+        }
+        if (vkey[i] != kNoKey) {
+            s[1] += 1.0; s[5] += (v < A.vmin || v > A.vmax) ? 1.0 : 0.0;
+            x[2] = fmax(x[2], -v); x[3] = fmax(x[3], v);
+            x[4] = fmax(x[4], fmax(A.vmin - v, v - A.vmax));
+        }
+    }
+    block_reduce_multi<NT, 6, true>(s, red);
+    block_reduce_multi<NT, 5, false>(x, red);
+    // the worst line / node: the lowest node index among those that attain the extreme
+    double wi[2] = {ninf, ninf};
+    double vworst = ninf;                                           // (a candidate's own voltage: the owner writes it below)
+    int iworst = -1;
+#pragma unroll
+    for (int c = IPT - kNetChunk; c >= 0; c -= kNetChunk) {         // (descending: the thread's lowest index stays)
+        int nd[kNetChunk];
+        net_load_nd<kNetChunk>(A, act, jl + c, nd);
+#pragma unroll
+        for (int i = kNetChunk - 1; i >= 0; --i) {
+            const double v = key_val(vkey[c + i]);                  // (a NaN for an entry left out: every test fails)
+            if (key_val(lkey[c + i]) == x[1]) wi[0] = fmax(wi[0], -(double)nd[i]);
+            if (fmax(A.vmin - v, v - A.vmax) == x[4] && -(double)nd[i] >= wi[1]) { wi[1] = -(double)nd[i]; iworst = nd[i]; vworst = v; }
+        }
+        NET_CHUNK_FENCE();
+    }
+    block_reduce_multi<NT, 2, false>(wi, red);
+
+    // ---- the quartiles' lower order statistics: rank (k - 1) q / 4 of k values, q = 1, 2, 3, bit by bit
+    const int kcnt[2] = {(int)s[0], (int)s[1]};
+    int rank[6], rem[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const int r = (kcnt[e / 3] > 0 ? kcnt[e / 3] - 1 : 0) * (e % 3 + 1);
+        rank[e] = r >> 2; rem[e] = r & 3;
+    }
+    unsigned long long ans[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
+    const int wave = tid >> 6;
+#pragma unroll 1
+    for (int bit = 62; bit >= 0; --bit) {
+        unsigned long long trial[6];
+        unsigned int c[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int e = 0; e < 6; ++e) trial[e] = ans[e] | (1ull << bit);
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                c[e] += (unsigned)__popcll(__ballot(lkey[i] < trial[e]));
+                c[3 + e] += (unsigned)__popcll(__ballot(vkey[i] < trial[3 + e]));
+            }
+        }
+        // (a wavefront's counts are <= 64 IPT, the workgroup's <= 16 384: 16-bit fields never carry)
+        unsigned long long *cb = cbuf + (size_t)(bit & 1) * (NT / 64) * 2;
+        if ((tid & 63) == 0) {
+            cb[2 * wave] = c[0] | (unsigned long long)c[1] << 16 | (unsigned long long)c[2] << 32;
+            cb[2 * wave + 1] = c[3] | (unsigned long long)c[4] << 16 | (unsigned long long)c[5] << 32;
+        }
+        __syncthreads();        // (the one barrier of a round: the buffers alternate, and a wavefront that writes
+                                //  round r + 2 has passed round r + 1's barrier, behind every read of round r)
+        // the wavefronts' counts summed across the first NT / 64 lanes of a row (block_reduce_multi's way), by halves:
+        // no field carries into the next
+        unsigned d[4] = {0u, 0u, 0u, 0u};
+        if ((tid & 63) < NT / 64) {
+            const TreeU2 u = *reinterpret_cast<const TreeU2 *>(cb + 2 * (tid & 63));
+            d[0] = (unsigned)u.v[0]; d[1] = (unsigned)(u.v[0] >> 32); d[2] = (unsigned)u.v[1]; d[3] = (unsigned)(u.v[1] >> 32);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            d[k] += (unsigned)dpp_i<0x128>((int)d[k]);
+            d[k] += (unsigned)dpp_i<0x124>((int)d[k]);
+            d[k] += (unsigned)dpp_i<0x122>((int)d[k]);
+            d[k] += (unsigned)dpp_i<0x121>((int)d[k]);
+            d[k] = __builtin_amdgcn_readfirstlane(d[k]);
+        }
+        const int tot[6] = {(int)(d[0] & 0xFFFFu), (int)(d[0] >> 16), (int)d[1], (int)(d[2] & 0xFFFFu), (int)(d[2] >> 16), (int)d[3]};
+#pragma unroll
+        for (int e = 0; e < 6; ++e)
+            if (tot[e] <= rank[e]) ans[e] = trial[e];
+    }
+
+    // ---- their upper neighbours: the same value when it repeats past the rank, else the smallest value above it
+    double cle[6], nxt[6];
+#pragma unroll
+    for (int e = 0; e < 6; ++e) { cle[e] = 0.0; nxt[e] = ninf; }
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            if (lkey[i] != kNoKey) {
+                if (lkey[i] <= ans[e]) cle[e] += 1.0; else nxt[e] = fmax(nxt[e], -key_val(lkey[i]));
+            }
+            if (vkey[i] != kNoKey) {
+                if (vkey[i] <= ans[3 + e]) cle[3 + e] += 1.0; else nxt[3 + e] = fmax(nxt[3 + e], -key_val(vkey[i]));
+            }
+        }
+    }
+    block_reduce_multi<NT, 6, true>(cle, red);
+    block_reduce_multi<NT, 6, false>(nxt, red);
+    double qv[6];                                                   // Q1, median, Q3 of {loading, volt}
+#pragma unroll
+    for (int e = 0; e < 6; ++e) {
+        const double lo = key_val(ans[e]);
+        const bool last = rank[e] + 1 >= kcnt[e / 3];               // (numpy clips the upper index to k - 1)
+        const double hi = (last || (int)cle[e] > rank[e] + 1) ? lo : -nxt[e];
+        qv[e] = np_lerp(lo, hi, 0.25 * (double)rem[e]);
+    }
+    // ---- whiskers: the farthest datum within 1.5 IQR of the box (matplotlib.cbook.boxplot_stats), then the fliers
+    double lim[4], wk[4] = {ninf, ninf, ninf, ninf};                // -whisker_lo, whisker_hi of {loading, volt}
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const double iqr = __dsub_rn(qv[3 * q + 2], qv[3 * q]);
+        lim[2 * q] = __dsub_rn(qv[3 * q], __dmul_rn(1.5, iqr));
+        lim[2 * q + 1] = __dadd_rn(qv[3 * q + 2], __dmul_rn(1.5, iqr));
+    }
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+        const double l = key_val(lkey[i]), v = key_val(vkey[i]);    // (a NaN for an entry left out: every test fails)
+        if (l >= lim[0]) wk[0] = fmax(wk[0], -l);
+        if (l <= lim[1]) wk[1] = fmax(wk[1], l);
+        if (v >= lim[2]) wk[2] = fmax(wk[2], -v);
+        if (v <= lim[3]) wk[3] = fmax(wk[3], v);
+    }
+    block_reduce_multi<NT, 4, false>(wk, red);
+    double wlo[2], whi[2], fl[2] = {0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        wlo[q] = (wk[2 * q] == ninf || -wk[2 * q] > qv[3 * q]) ? qv[3 * q] : -wk[2 * q];
+        whi[q] = (wk[2 * q + 1] == ninf || wk[2 * q + 1] < qv[3 * q + 2]) ? qv[3 * q + 2] : wk[2 * q + 1];
+    }
+#pragma unroll
+    for (int i = 0; i < IPT; ++i) {
+        const double l = key_val(lkey[i]), v = key_val(vkey[i]);
+        fl[0] += (l < wlo[0] || l > whi[0]) ? 1.0 : 0.0;
+        fl[1] += (v < wlo[1] || v > whi[1]) ? 1.0 : 0.0;
+    }
+    block_reduce_multi<NT, 2, true>(fl, red);
+
+    if (tid == 0) {
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            revs_net_summary_t r;
+            const bool any = kcnt[q] > 0;
+            const double nan = __builtin_nan("");
+            r.min = any ? -x[2 * q] : nan;
+            r.q1 = any ? qv[3 * q] : nan;
+            r.median = any ? qv[3 * q + 1] : nan;
+            r.q3 = any ? qv[3 * q + 2] : nan;
+            r.max = any ? x[2 * q + 1] : nan;
+            r.whisker_lo = any ? wlo[q] : nan;
+            r.whisker_hi = any ? whi[q] : nan;
+            r.worst_value = nan;
+            r.count = kcnt[q];
+            r.n_fliers = any ? (int)fl[q] : 0;
+            r.n_violations = (int)s[4 + q];
+            r.n_nan = (int)s[2 + q];
+            r.worst_index = any ? (int)-wi[q] : -1;
+            r.reserved[0] = r.reserved[1] = r.reserved[2] = 0;
+            if (any && q == 0) r.worst_value = x[1];
+            A.sum[(size_t)q * T + t] = r;
+        }
+    }
+    // the worst node's own voltage: its owner knows it (written behind thread 0's record)
+    __syncthreads();
+    if (kcnt[1] > 0 && iworst >= 0 && (double)iworst == -wi[1]) A.sum[(size_t)T + t].worst_value = vworst;
+}
+
+}  // namespace revs
+
+using namespace revs;
+
+extern "C" int revs_net_node_sums(int32_t m, int32_t T, const int64_t *node_ptr, const float *load, const float *p,
+                                  double *node_g, void *stream) {
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_net_node_sums: T=%d outside 1..%d", (int)T, REVS_MAX_T);
+    REVS_REQUIRE(m > 0, "revs_net_node_sums: m > 0 required");
+    REVS_REQUIRE(node_ptr && p && node_g, "revs_net_node_sums: null pointer argument");
+    const int64_t total = (int64_t)m * T;
+    hipLaunchKernelGGL(net_node_sums_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       m, T, node_ptr, load, p, node_g);
+    REVS_CHECK_LAUNCH("revs_net_node_sums");
+    return REVS_OK;
+}
+
+extern "C" int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g, const double *rating,
+                               const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out, double vset,
+                               double vmin, double vmax, double *flow_out, double *loading_out, double *volt_out,
+                               revs_net_summary_t *summary_out, void *stream) {
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_net_report: T=%d outside 1..%d", (int)T, REVS_MAX_T);
+    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "revs_net_report: m=%d outside 1..65535", (int)m);
+    REVS_REQUIRE(tree && node_g && tree->pack && tree->w, "revs_net_report: null pointer argument");
+    REVS_REQUIRE(tree->n > 0 && tree->n <= REVS_TREE_MAX && tree->n % tree_shape(tree->n).ipt == 0,
+                 "revs_net_report: tree of %d nodes (at most %d, a multiple of 8; of 16 beyond 8192)", (int)tree->n,
+                 REVS_TREE_MAX);
+    REVS_REQUIRE(n_out > 0 && n_out <= tree->n, "revs_net_report: n_out=%d outside 1..tree nodes", (int)n_out);
+    REVS_REQUIRE(vset == vset && vset >= 0.0 && vset < INFINITY, "revs_net_report: vset must be finite and >= 0");
+    REVS_REQUIRE(vmin <= vmax, "revs_net_report: vmin > vmax");         // (also rejects NaN)
+    REVS_REQUIRE(flow_out || loading_out || volt_out || summary_out, "revs_net_report: every output is NULL");
+    NetArgs A;
+    A.tr = TreeArgs{tree->n, (const unsigned long long *)tree->pack, tree->w};
+    A.g = node_g; A.rating = rating; A.mask = node_mask; A.nop = node_of_pos;
+    A.m = m; A.T = T; A.n_out = n_out;
+    A.vset2 = vset * vset; A.vmin = vmin; A.vmax = vmax;
+    A.flow = flow_out; A.loading = loading_out; A.volt = volt_out; A.sum = summary_out;
+    const size_t lds = net_lds_bytes(tree->n);
+    const TreeShape sh = tree_shape(tree->n);
+#define NK(NT, IPT)                                                                                              \
+    do {                                                                                                         \
+        if (!grant_lds(reinterpret_cast<const void *>(net_report_kernel<NT, IPT>), lds, "network report"))       \
+            return REVS_ELAUNCH;                                                                                 \
+        hipLaunchKernelGGL((net_report_kernel<NT, IPT>), dim3(T), dim3(NT), lds, (hipStream_t)stream, A);        \
+    } while (0)
+    if (sh.nt == 256) NK(256, 8);
+    else if (sh.nt == 512) NK(512, 8);
+    else if (sh.ipt == 8) NK(1024, 8);
+    else NK(1024, 16);
+#undef NK
+    REVS_CHECK_LAUNCH("revs_net_report");
+    return REVS_OK;
+}

@@ -1,0 +1,66 @@
+"""The two power-flow functions of the reference's drawing.py (lines 29-78) over the GPU network report:
+
+    from revs_admm_amd.drawing import compute_flows, compute_voltage
+
+Same arguments and the same dicts back -- {edge: loading per slot} over graph.edges, {node: voltage per slot} over
+the non-substation nodes -- so the code that feeds the reference's box plots runs unchanged.  The figures
+themselves (matplotlib, seaborn, geopandas) are outside the project.
+
+Line ratings are the caller's data: an edge attribute `rating` (kVA) on the graph, or `rating=` as a mapping from
+the edges' `type` attribute to kVA (the reference keeps such a table inside compute_flows; INTEGRATION.md shows how
+to pass one)."""
+from __future__ import annotations
+
+import numpy as np
+
+from .lpsolver import feeder_arrays
+from .network import report_for_tree
+
+__all__ = ["compute_flows", "compute_voltage"]
+
+
+def _edge_ratings(graph, rating):
+    """kVA of every edge, in graph.edges order."""
+    edges = list(graph.edges)
+    if rating is not None:
+        missing = sorted({graph.edges[e].get("type") for e in edges} - set(rating), key=str)
+        if missing:
+            raise KeyError(f"compute_flows: rating= has no entry for line type {missing[0]!r}")
+        return np.array([float(rating[graph.edges[e]["type"]]) for e in edges])
+    if edges and all("rating" in graph.edges[e] for e in edges):
+        return np.array([float(graph.edges[e]["rating"]) for e in edges])
+    raise ValueError("compute_flows needs line ratings: give every edge a `rating` attribute (kVA), or pass "
+                     "rating={line type: kVA} for the edges' `type` attribute")
+
+
+def _node_profile(graph, p_sch):
+    res = [n for n in graph if graph.nodes[n]["label"] == "H"]
+    nonsub = [n for n in graph if graph.nodes[n]["label"] != "S"]
+    return res, nonsub, np.array([p_sch[h] for h in res], np.float64)
+
+
+def compute_flows(graph, p_sch, rating=None, device="cuda:0"):
+    """drawing.py:29-58: {edge: [flow / rating per slot]} in graph.edges order, signed like the reference's
+    A^-1 P (positive from the edge's first node to its second; the box plots take the absolute value)."""
+    rate = _edge_ratings(graph, rating)
+    res, nonsub, P = _node_profile(graph, p_sch)
+    parent, edge_r, cons_of = feeder_arrays(graph, res)
+    pos = {n: i for i, n in enumerate(nonsub)}
+    child = np.empty(len(rate), np.int64)       # the tree node below each edge, and the edge's sign towards it
+    sign = np.empty(len(rate))
+    for k, (u, v) in enumerate(graph.edges):
+        down = pos.get(v, -1) >= 0 and parent[pos[v]] == pos.get(u, -1)
+        child[k], sign[k] = (pos[v], 1.0) if down else (pos[u], -1.0)
+    node_rating = np.zeros(len(nonsub))
+    node_rating[child] = rate
+    rep = report_for_tree(parent, edge_r, cons_of, P, rating=node_rating, device=device)
+    signed = sign[:, None] * np.sign(rep.flow[child]) * rep.loading[child]
+    return {e: signed[k].tolist() for k, e in enumerate(graph.edges)}
+
+
+def compute_voltage(graph, p_sch, vset=1.0, device="cuda:0"):
+    """drawing.py:60-78: {node: [sqrt(vset^2 - (R P)[node]) per slot]} over the non-substation nodes."""
+    res, nonsub, P = _node_profile(graph, p_sch)
+    parent, edge_r, cons_of = feeder_arrays(graph, res)
+    rep = report_for_tree(parent, edge_r, cons_of, P, vset=vset, device=device)
+    return {n: rep.volt[i].tolist() for i, n in enumerate(nonsub)}

@@ -26,6 +26,7 @@ from . import _lib
 from ._lib import HOME_DTYPE, MODES, PDHG, check, ptr
 from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (re-exported)
 from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
+from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
 from .steady_state import SteadyStateMixin
@@ -198,7 +199,7 @@ def _on_current_stream(fn):
     return wrapped
 
 
-class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin):
+class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin):
     """State of one ADMM run on one GPU.
 
     Parameters
@@ -280,6 +281,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if self.op.solver == "newton" and np.asarray(Rn).shape[0] > 16384:
             self.op = dataclasses.replace(self.op, solver="admm")   # revs_op_dual_select's limit
         self.vlo, self.vhi = voltage_limits(vset, vlow, vhigh)
+        self.vset, self.vlow, self.vhigh = float(vset), float(vlow), float(vhigh)      # (network_report's voltages)
         self._scale = max(abs(self.vlo), abs(self.vhi), 1e-300)     # (the voltage rows are judged relative to it)
 
         load = np.ascontiguousarray(load, np.float32)
@@ -548,6 +550,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                     tr, rejected = None, True              # (Rn is not a radial feeder's matrix: dense product)
             if tr is not None:
                 self._tree_host = tr
+                self._tree_nodes = len(par)            # (before padding: the nodes network_report reports)
                 self._tree_dev = {k: self._up(tr[k].view(np.int64) if k == "pack" else tr[k]) for k in ("pack", "w")}
                 self._tree = _lib.Tree(tr["n"], ptr(self._tree_dev["pack"]), ptr(self._tree_dev["w"]))
                 if self._plan is not None:
@@ -1144,8 +1147,9 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         return out
 
     def voltage(self, profile=None):
-        """R . (node aggregate of a home profile) on the f32 matrix cores: the
-        operator's voltage-sensitivity check (lpsolver.py:191-193, drawing.py:60-78)."""
+        """R . (node aggregate of a home profile) at the residence rows, on the f32 matrix cores: the
+        left-hand side of the operator's voltage rows (lpsolver.py:191-193).  Not a voltage: the voltages of
+        drawing.py:60-78, sqrt(vset^2 - R p) at every node of the feeder in f64, are network_report().volt."""
         prof = self.P_sch if profile is None else profile
         check(self.lib.revs_aggregate_f32(self.M, self.T, ptr(self.node_ptr), ptr(prof),
                                           ptr(self.node_load), self.stream), "revs_aggregate_f32")

@@ -12,8 +12,9 @@ def feeder_tree(parent, edge_r, cons_of, checked):
     edge_r[i]   resistance of the edge from i to its parent
     cons_of[i]  constraint row (0..M-1) of node i, or -1
     checked[r]  whether row r is constrained (it carries residences, lpsolver.py:188-189)
-    Returns dict(n, src, end, eo, cle, w, pack) of numpy arrays (see include/revs_admm.h; the device
-    gets `pack` and `w`, the separate index arrays serve tree_voltage_host)."""
+    Returns dict(n, src, end, eo, cle, w, pack, order) of numpy arrays (see include/revs_admm.h; the device
+    gets `pack` and `w`, the separate index arrays serve tree_voltage_host; order[j] = the tree node at preorder
+    position j -- the padding nodes are those >= len(parent) -- which the network report un-permutes by)."""
     parent = np.asarray(parent, np.int64)
     # the kernel's threads own 8 consecutive positions (16 in the shape for more than 8192 nodes):
     pad = (-len(parent)) % (8 if -(-len(parent) // 8) * 8 <= 8192 else 16)
@@ -55,7 +56,7 @@ def feeder_tree(parent, edge_r, cons_of, checked):
     pack = ((src + 1).astype(np.uint64) | (end.astype(np.uint64) << np.uint64(16))
             | (eo.astype(np.uint64) << np.uint64(32)) | (cle.astype(np.uint64) << np.uint64(48)))
     return dict(n=n, src=src.astype(np.int32), end=end.astype(np.int32), eo=eo.astype(np.int32),
-                cle=cle.astype(np.int32), w=w, pack=pack)
+                cle=cle.astype(np.int32), w=w, pack=pack, order=order)
 
 
 def tree_voltage_host(tree, p):
@@ -71,6 +72,27 @@ def tree_voltage_host(tree, p):
     out = np.zeros_like(p)
     out[src[src >= 0]] = v[src >= 0]
     return out
+
+
+def tree_report_host(tree, p, n_nodes=None):
+    """tree_voltage_host at EVERY tree node, with the intermediate it multiplies away: (flow, drop), each
+    (n_nodes, T) in the caller's node order -- flow[i] the sum of p over the rows in i's subtree (the power through
+    the line from i to its parent), drop[i] = (R p)[i], checked row or not.  numpy restatement of the network
+    report's scans."""
+    n, src = tree["n"], tree["src"]
+    n_nodes = n if n_nodes is None else n_nodes
+    inj = np.where(src >= 0, 1.0, 0.0)[:, None] * p[np.maximum(src, 0)]
+    C = np.concatenate([np.zeros((1, p.shape[1])), np.cumsum(inj, 0)])
+    flow = C[tree["end"]] - C[:-1]
+    wp = tree["w"][:, None] * flow
+    pre = np.cumsum(wp, 0)
+    F = np.concatenate([np.zeros((1, p.shape[1])), np.cumsum(wp[tree["eo"]], 0)])
+    drop = pre - F[tree["cle"]]
+    keep = tree["order"] < n_nodes
+    out_f, out_d = np.zeros((n_nodes, p.shape[1])), np.zeros((n_nodes, p.shape[1]))
+    out_f[tree["order"][keep]] = flow[keep]
+    out_d[tree["order"][keep]] = drop[keep]
+    return out_f, out_d
 
 
 def tree_from_R(R, rtol=1e-12):

@@ -103,6 +103,23 @@ class REVS:
                        kwargs.get("adoption", 90), kwargs.get("rating", 4800), kwargs.get("seed"))
         return Pres, Pev, soc
 
+    def result_frames(self, demand, dist, community=None, start=11, end=23, shift=6, rating=None):
+        """The two long tables the reference's box plots are drawn from (drawing.py:125-176, boxplot_flow /
+        boxplot_volt), as dicts of numpy arrays: ({"hour", "loading"}, {"hour", "voltage"}) -- for every slot
+        start..end the hour label and the loading in % of every edge of `dist`; the hour label and the voltage of
+        every node of `community` (default: every non-substation node).  `rating`: see drawing.compute_flows."""
+        from .drawing import compute_flows, compute_voltage
+        flows = compute_flows(dist, demand, rating=rating, device=self.device)
+        volts = compute_voltage(dist, demand, device=self.device)
+        nodes = list(community) if community is not None else list(volts)
+        slots = range(start, end + 1)
+        label = {t: f"{(t + shift - 1) % 24}:00 - {(t + shift) % 24}:00" for t in slots}
+        fl = {"hour": np.array([label[t] for t in slots for _ in flows]),
+              "loading": np.array([abs(flows[e][t]) * 100.0 for t in slots for e in flows])}
+        vo = {"hour": np.array([label[t] for t in slots for _ in nodes]),
+              "voltage": np.array([volts[n][t] for t in slots for n in nodes])}
+        return fl, vo
+
     def plot_result(self, *a, **k):
         """revs_fixture.py:282-...: figures (drawing.py: matplotlib / geopandas) are outside the hot
         path.  Warns and returns, so that a script written for the reference (test-optimizer.py:55-58
