@@ -448,6 +448,50 @@ int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree_host, const do
                     double vmax, double *flow_out, double *loading_out, double *volt_out,
                     revs_net_summary_t *summary_out, void *stream);
 
+/* ---- study report: the network report of S schedules on one feeder, and box-plot numbers pooled over groups ---------
+ * What the reference publishes is an ensemble (seeds x adoption x method): box plots pooled over all schedules of a
+ * group, and per schedule and slot the number of nodes at or below a voltage band.  Quantiles do not compose, so the
+ * pooled numbers are selected on the device from the keys of every schedule of the group.
+ *
+ * revs_net_study: revs_net_report's kernel on a T x S grid -- scenario s reads node_g[s] (double[S][m][T]) and writes
+ * flow_out / loading_out / volt_out[s] (double[S][n_out][T]) and summary_out[s] (revs_net_summary_t[S][2][T]): bit for
+ * bit what revs_net_report gives for that schedule alone.  tree, rating, node_mask, node_of_pos, n_out, vset, vmin,
+ * vmax: as there, shared by every scenario.  In the same workgroup:
+ *   band_count_out int32[S][T][B]: the number of masked nodes with volt <= band[b] (cumulative, any order of the
+ *                  thresholds, a NaN voltage is never counted); band: HOST array of B <= 8 finite thresholds
+ *   pooled_out     revs_net_pooled_t[G][2][T] ([0]: loading, [1]: volt): the summary rule over the multiset of all
+ *                  values of the scenarios with group[s] == g.  group: HOST array int32[S] in -1 .. G-1 (-1: in no
+ *                  pool).  A second launch on the same stream selects the order statistics exactly (digit-wise radix
+ *                  select over the keys the first launch staged in `scratch`, revs_net_study_scratch bytes).  A pool of
+ *                  one scenario equals that scenario's revs_net_summary_t in every shared field.  Worst ties: the
+ *                  lowest scenario, then the lowest caller-side index.
+ * Any output may be NULL, not all.  Reads nothing else; writes the outputs and the scratch.  REVS_EINVAL, before any
+ * launch: every case of revs_net_report; S outside 1..REVS_STUDY_MAX_S; G outside 0..S; B outside 0..8; a group id
+ * outside -1..G-1; a threshold that is not finite; band / group NULL where B / G > 0; pooled_out without scratch (or
+ * with G == 0); every output NULL.
+ * revs_net_study_scratch: 2 S T tree_n 8 bytes (keys [quantity][slot][scenario][position]); 0 for a bad size. */
+#define REVS_STUDY_MAX_S 4096
+#define REVS_STUDY_MAX_BANDS 8
+typedef struct {
+    double min, q1, median, q3, max;   /* as revs_net_summary_t, over the pool */
+    double whisker_lo, whisker_hi;
+    double worst_value;
+    int32_t count;
+    int32_t n_fliers;
+    int32_t n_violations;
+    int32_t n_nan;
+    int32_t worst_index;               /* caller's index of the worst line / node, in scenario worst_scenario */
+    int32_t worst_scenario;            /* -1: count == 0 */
+    int32_t reserved[2];
+} revs_net_pooled_t;                   /* 96 bytes */
+int64_t revs_net_study_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_study(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const double *node_g,
+                   const double *rating, const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out,
+                   double vset, double vmin, double vmax, const int32_t *group, int32_t G, const double *band,
+                   int32_t B, double *flow_out, double *loading_out, double *volt_out,
+                   revs_net_summary_t *summary_out, revs_net_pooled_t *pooled_out, int32_t *band_count_out,
+                   void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -122,6 +122,8 @@ TREE_SWEEP_MAX = 2048    # REVS_TREE_SWEEP_MAX
 CHAIN_FOLD_MAX_M = 2048  # REVS_CHAIN_FOLD_MAX_M
 STREAM_BLOCK_MAX = 256   # REVS_STREAM_BLOCK_MAX
 AGENT_MAX_INNER = 32     # REVS_AGENT_MAX_INNER
+STUDY_MAX_S = 4096       # REVS_STUDY_MAX_S
+STUDY_MAX_BANDS = 8      # REVS_STUDY_MAX_BANDS
 
 
 class RevsError(RuntimeError):
@@ -248,6 +250,9 @@ SIGNATURES = {
     "revs_plan_status_flags": (_i32, [_p, _i32]),
     "revs_net_node_sums": (C.c_int, [_i32, _i32, _p, _p, _p, _p, _p]),
     "revs_net_report": (C.c_int, [_i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _p, _p]),
+    "revs_net_study_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_study": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _i32, _p,
+                                 _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -51,9 +51,15 @@ struct NetArgs {
     double vset2, vmin, vmax;
     double *flow, *loading, *volt;
     revs_net_summary_t *sum;      // [2][T], or NULL
+    // the study (revs_net_study): blockIdx.y is the scenario; g, the three arrays and sum are strided by it
+    double band[REVS_STUDY_MAX_BANDS];           // thresholds of the band counts (-inf: unused)
+    int32_t *bandc;               // [S][T][nband], or NULL
+    unsigned long long *stage;    // keys for the pooled selection [2][T][S][tr.n], or NULL
+    int32_t nband;
 };
 
 constexpr unsigned long long kNoKey = ~0ull;     // an entry left out of the summary (no trial key is above 2^63)
+constexpr unsigned long long kNanKey = ~0ull - 1;    // staged only: a rated line / masked node whose value is a NaN
 constexpr int kNetRed = 8;                       // values one block reduction carries
 
 // doubles behind the scans' LDS: kNetRed per wavefront for the reductions, two count buffers of 16 bytes per wavefront
@@ -177,12 +183,31 @@ __device__ __forceinline__ unsigned long long net_loading_key(double flow, doubl
     return (valid && ld == ld) ? (unsigned long long)__double_as_longlong(ld + 0.0) : kNoKey;
 }
 
+// A chunk's keys into the staging row (by preorder position: 64 contiguous bytes per thread and chunk).
+__device__ __forceinline__ void net_stage_chunk(unsigned long long *dst, const unsigned long long (&k)[kNetChunk]) {
+#pragma unroll
+    for (int i = 0; i < kNetChunk; i += 2) *reinterpret_cast<TreeU2 *>(dst + i) = TreeU2{{k[i], k[i + 1]}};
+}
+
 template <int NT, int IPT>
-__global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
+__global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A0) {
     extern __shared__ double net_lds[];
     double *lds = net_lds;
+    NetArgs A = A0;
+    const int tid = threadIdx.x, t = (int)blockIdx.x, T = A.T, n = A.tr.n, j0 = IPT * tid;
+    const int sc = (int)blockIdx.y, S = (int)gridDim.y;            // the scenario (revs_net_report: the only one)
+    {
+        const int64_t arr = (int64_t)sc * A.n_out * T;
+        A.g += (int64_t)sc * A.m * T;
+        if (A.flow) A.flow += arr;
+        if (A.loading) A.loading += arr;
+        if (A.volt) A.volt += arr;
+        if (A.sum) A.sum += (int64_t)sc * 2 * T;
+    }
     const TreeArgs &tr = A.tr;
-    const int tid = threadIdx.x, t = (int)blockIdx.x, T = A.T, n = tr.n, j0 = IPT * tid;
+    // this (slot, scenario)'s staging rows: loading, volt
+    unsigned long long *stl = A.stage ? A.stage + ((int64_t)t * S + sc) * n : nullptr;
+    unsigned long long *stv = A.stage ? stl + (int64_t)T * S * n : nullptr;
     const bool act = j0 < n;
     const int jl = act ? j0 : 0;                                    // (threads beyond the tree load position 0's data, unused)
     double *base = lds + 2, *red0 = lds + 2 + NT * IPT, *red1 = red0 + NT / 64;
@@ -212,6 +237,7 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
     for (int c = 0; c < IPT; c += kNetChunk) {
         int nd[kNetChunk];
         double r[kNetChunk];
+        unsigned long long sk[kNetChunk];
         net_load_nd<kNetChunk>(A, act, jl + c, nd);
         net_load_rating<kNetChunk>(A, jl + c, r);
         if (A.flow) {
@@ -226,7 +252,11 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
             if constexpr (!kRescan) {
                 lkey[c + i] = k;
                 nanl += (rated && k == kNoKey) ? 1.0 : 0.0;
+                sk[i] = (rated && k == kNoKey) ? kNanKey : k;
             }
+        }
+        if constexpr (!kRescan) {
+            if (stl && act) net_stage_chunk(stl + j0 + c, sk);
         }
         if (A.loading) {
 #pragma unroll
@@ -269,6 +299,7 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
 #pragma unroll
         for (int c = 0; c < IPT; c += kNetChunk) {
             int nd[kNetChunk];
+            unsigned long long sk[kNetChunk];
             net_load_nd<kNetChunk>(A, act, jl + c, nd);
             const unsigned long long mk = A.mask ? *reinterpret_cast<const unsigned long long *>(A.mask + jl + c) : ~0ull;
 #pragma unroll
@@ -279,11 +310,32 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
                 if (A.volt && nd[i] >= 0) A.volt[(int64_t)nd[i] * T + t] = v;
                 vkey[c + i] = (in && v == v) ? (unsigned long long)__double_as_longlong(v + 0.0) : kNoKey;
                 nanv += (in && v != v) ? 1.0 : 0.0;
+                sk[i] = (in && v != v) ? kNanKey : vkey[c + i];
             }
+            if (stv && act) net_stage_chunk(stv + j0 + c, sk);
             NET_CHUNK_FENCE();
         }
     }
-    if (!A.sum) return;
+    // ---- band counts: masked nodes with volt <= band[b] (an entry left out or a NaN is a NaN here: never counted)
+    if (A.bandc) {
+        double bc[REVS_STUDY_MAX_BANDS];
+#pragma unroll
+        for (int b = 0; b < REVS_STUDY_MAX_BANDS; ++b) bc[b] = 0.0;
+#pragma unroll
+        for (int i = 0; i < IPT; ++i) {
+            const double v = key_val(vkey[i]);
+#pragma unroll
+            for (int b = 0; b < REVS_STUDY_MAX_BANDS; ++b) bc[b] += v <= A.band[b] ? 1.0 : 0.0;
+        }
+        block_reduce_multi<NT, REVS_STUDY_MAX_BANDS, true>(bc, red);
+        if (tid == 0) {
+            int32_t *o = A.bandc + ((int64_t)sc * T + t) * A.nband;
+#pragma unroll
+            for (int b = 0; b < REVS_STUDY_MAX_BANDS; ++b)
+                if (b < A.nband) o[b] = (int)bc[b];
+        }
+    }
+    if (!A.sum && !(kRescan && stl)) return;
     if constexpr (kRescan) {
         __syncthreads();                                            // (every read of F is done)
         unsigned se[IPT];
@@ -297,6 +349,7 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
         for (int c = 0; c < IPT; c += kNetChunk) {
             int nd[kNetChunk];
             double r[kNetChunk];
+            unsigned long long sk[kNetChunk];
             net_load_nd<kNetChunk>(A, act, jl + c, nd);
             net_load_rating<kNetChunk>(A, jl + c, r);
 #pragma unroll
@@ -304,9 +357,12 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
                 const bool rated = nd[i] >= 0 && r[i] > 0.0;
                 lkey[c + i] = net_loading_key(a[c + i], r[i], rated, r[i]);
                 nanl += (rated && lkey[c + i] == kNoKey) ? 1.0 : 0.0;
+                sk[i] = (rated && lkey[c + i] == kNoKey) ? kNanKey : lkey[c + i];
             }
+            if (stl && act) net_stage_chunk(stl + j0 + c, sk);
             NET_CHUNK_FENCE();
         }
+        if (!A.sum) return;
     }
 
     // ---- counts and extremes
@@ -485,6 +541,220 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A) {
     if (kcnt[1] > 0 && iworst >= 0 && (double)iworst == -wi[1]) A.sum[(size_t)T + t].worst_value = vworst;
 }
 
+
+// ---- the pooled selection (revs_net_study, second launch): one workgroup per (slot, quantity, group) over the staged
+// keys of the group's scenarios.  The k-th smallest key by digits of 8 bits from the top: a pass counts, among the keys
+// that share the prefix found so far, the next digit's 256 values in LDS; the three quartile ranks keep a prefix each
+// and share a histogram while their prefixes agree.  The counts are integers: LDS atomics in any order give the same
+// bits.  The last pass leaves, for free, the number of keys below and equal to each order statistic.
+constexpr int kPoolNT = 1024;
+constexpr int kPoolMaskWords = 448;               // member bit masks of the groups of one launch (3.5 KB of arguments)
+struct PoolArgs {
+    const unsigned long long *stage;              // [2][T][S][n]
+    const int32_t *nop;                           // node_of_pos, or NULL
+    revs_net_pooled_t *out;                       // [G][2][T]
+    int32_t S, T, n, n_out, g0, words;
+    double vmin, vmax;
+    unsigned long long member[kPoolMaskWords];    // [groups of this launch][words]: bit s of a group's mask: scenario s
+};
+
+// one count into h[d] per matching lane: by the first matching lane alone when the wavefront's digits agree (the common
+// case in the top passes, where 64 atomics on one address would queue)
+__device__ __forceinline__ void pool_hist_add(unsigned *h, bool match, unsigned d) {
+    const unsigned long long m = __ballot(match);
+    if (m == 0ull) return;
+    const int first = (int)__builtin_ctzll(m);
+    const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, first);
+    if (__ballot(match && d == d0) == m) {
+        if ((int)(threadIdx.x & 63) == first) atomicAdd(h + d0, (unsigned)__popcll(m));
+    } else if (match) {
+        atomicAdd(h + d, 1u);
+    }
+}
+
+// f(key, scenario, position) over every staged key of the group, every thread the same number of times (threads past
+// the row's end see kNoKey): the callers' lane masks and reductions stay whole
+template <class F>
+__device__ __forceinline__ void pool_for_each(const PoolArgs &A, const unsigned long long *member, const unsigned long long *rows, F f) {
+    for (int w = 0; w < A.words; ++w) {
+        unsigned long long mk = member[w];
+        while (mk) {
+            const int s = 64 * w + (int)__builtin_ctzll(mk);
+            mk &= mk - 1;
+            const unsigned long long *row = rows + (int64_t)s * A.n;
+            for (int jb = 0; jb < A.n; jb += 2 * kPoolNT) {
+                const int j = jb + 2 * (int)threadIdx.x;
+                TreeU2 k{{kNoKey, kNoKey}};
+                if (j < A.n) k = *reinterpret_cast<const TreeU2 *>(row + j);       // (n is even: j + 1 < n)
+                f(k.v[0], s, j);
+                f(k.v[1], s, j + 1);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(kPoolNT) void net_pool_kernel(PoolArgs A) {
+    __shared__ alignas(16) unsigned hist[3 * 256];
+    __shared__ double red[(kPoolNT / 64) * kNetRed];
+    __shared__ unsigned found[3][4];              // per rank: digit, rank left inside the bin, the bin's count
+    constexpr int NT = kPoolNT;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int t = (int)blockIdx.x, q = (int)blockIdx.y, gl = (int)blockIdx.z;
+    const unsigned long long *member = A.member + (size_t)gl * A.words;
+    const unsigned long long *rows = A.stage + ((int64_t)q * A.T + t) * A.S * A.n;
+    const double ninf = -__builtin_inf();
+    const double vmin = A.vmin, vmax = A.vmax;
+    // a value's excursion: the loading itself / the distance outside (negative: inside) the voltage band
+    auto exc = [&](double v) { return q ? fmax(vmin - v, v - vmax) : v; };
+
+    for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
+    __syncthreads();
+    // ---- pass 0: counts and extremes, and the top digit's histogram (one prefix: the empty one)
+    double s[3] = {0.0, 0.0, 0.0};                // values, NaNs, violations
+    double x[3] = {ninf, ninf, ninf};             // -min, max, largest excursion
+    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
+        const bool ok = (k >> 63) == 0ull;
+        const double v = key_val(k);
+        s[0] += ok ? 1.0 : 0.0;
+        s[1] += k == kNanKey ? 1.0 : 0.0;
+        if (ok) {
+            s[2] += (q ? (v < vmin || v > vmax) : v > 1.0) ? 1.0 : 0.0;
+            x[0] = fmax(x[0], -v); x[1] = fmax(x[1], v); x[2] = fmax(x[2], exc(v));
+        }
+        pool_hist_add(hist, ok, (unsigned)(k >> 56));
+    });
+    block_reduce_multi<NT, 3, true>(s, red);
+    block_reduce_multi<NT, 3, false>(x, red);
+    const int kcnt = (int)s[0];
+    revs_net_pooled_t r;
+    const double nan = __builtin_nan("");
+    r.min = r.q1 = r.median = r.q3 = r.max = r.whisker_lo = r.whisker_hi = r.worst_value = nan;
+    r.count = kcnt; r.n_fliers = 0; r.n_violations = (int)s[2]; r.n_nan = (int)s[1];
+    r.worst_index = r.worst_scenario = -1;
+    r.reserved[0] = r.reserved[1] = 0;
+    revs_net_pooled_t *out = A.out + ((size_t)(A.g0 + gl) * 2 + q) * A.T + t;
+    if (kcnt == 0) {                              // (uniform)
+        if (tid == 0) *out = r;
+        return;
+    }
+    // ---- the quartiles' lower order statistics: rank (k - 1) e / 4, e = 1, 2, 3
+    int rank[3], rem4[3];
+    unsigned left[3], eq[3] = {0u, 0u, 0u};       // rank left among the keys that share the prefix; keys equal to ans
+    unsigned long long ans[3] = {0ull, 0ull, 0ull};
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const long long rr = (long long)(kcnt - 1) * (e + 1);
+        rank[e] = (int)(rr >> 2); rem4[e] = (int)(rr & 3);
+        left[e] = (unsigned)rank[e];
+    }
+#pragma unroll 1
+    for (int pass = 0; pass < 8; ++pass) {
+        const int shift = 56 - 8 * pass;
+        // ranks whose prefixes agree share a histogram (the prefixes ascend with the ranks: equal ones are adjacent)
+        int slot[3] = {0, 0, 0};
+        if (pass > 0) {
+            slot[1] = ans[1] == ans[0] ? 0 : 1;
+            slot[2] = ans[2] == ans[1] ? slot[1] : 2;
+            const bool own1 = slot[1] == 1, own2 = slot[2] == 2;
+            const unsigned long long p0 = ans[0] >> (shift + 8), p1 = ans[1] >> (shift + 8), p2 = ans[2] >> (shift + 8);
+            pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
+                const unsigned long long pk = k >> (shift + 8);
+                const unsigned d = (unsigned)(k >> shift) & 0xFFu;
+                pool_hist_add(hist, pk == p0, d);
+                if (own1) pool_hist_add(hist + 256, pk == p1, d);
+                if (own2) pool_hist_add(hist + 512, pk == p2, d);
+            });
+        }
+        __syncthreads();
+        // the bin that holds each rank: wavefront e for rank e, four bins per lane, a prefix sum across the lanes
+        if (wave < 3) {
+            const unsigned *h = hist + 256 * slot[wave];
+            const uint4 c = *reinterpret_cast<const uint4 *>(h + 4 * lane);
+            const unsigned own = c.x + c.y + c.z + c.w;
+            unsigned incl = own;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned up = (unsigned)__shfl_up((int)incl, o);
+                if (lane >= o) incl += up;
+            }
+            const unsigned want = left[wave], excl = incl - own;
+            if (want >= excl && want < incl) {    // (one lane: the bins' counts sum to more than the rank left)
+                unsigned b = 0, below = excl, cnt = c.x;
+                if (want >= below + cnt) { below += cnt; b = 1; cnt = c.y; }
+                if (b == 1 && want >= below + cnt) { below += cnt; b = 2; cnt = c.z; }
+                if (b == 2 && want >= below + cnt) { below += cnt; b = 3; cnt = c.w; }
+                found[wave][0] = 4u * lane + b; found[wave][1] = want - below; found[wave][2] = cnt;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            ans[e] = uniform_u64(ans[e] | (unsigned long long)found[e][0] << shift);       // (every lane holds the same)
+            left[e] = __builtin_amdgcn_readfirstlane(found[e][1]); eq[e] = __builtin_amdgcn_readfirstlane(found[e][2]);
+        }
+        __syncthreads();                          // (every read of hist and found is done)
+        for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
+        __syncthreads();
+    }
+    // ---- the upper neighbours (the smallest key above each), and the worst entry: lowest scenario, then lowest index
+    double nxt[3] = {ninf, ninf, ninf};
+    double wcode = ninf, vworst = nan;            // -(scenario * 65536 + caller's index): exact in a double
+    pool_for_each(A, member, rows, [&](unsigned long long k, int sidx, int j) {
+        if ((k >> 63) != 0ull) return;
+        const double v = key_val(k);
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+            if (k > ans[e]) nxt[e] = fmax(nxt[e], -v);
+        if (exc(v) == x[2]) {
+            const int nd = A.nop ? A.nop[j] : j;
+            const double code = -((double)sidx * 65536.0 + (double)nd);
+            if (code > wcode) { wcode = code; vworst = v; }
+        }
+    });
+    block_reduce_multi<NT, 3, false>(nxt, red);
+    double wc[1] = {wcode};
+    block_reduce_multi<NT, 1, false>(wc, red);
+    double qv[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const double lo = key_val(ans[e]);
+        const int cle = rank[e] - (int)left[e] + (int)eq[e];        // keys <= the order statistic
+        const bool last = rank[e] + 1 >= kcnt;
+        const double hi = (last || cle > rank[e] + 1) ? lo : -nxt[e];
+        qv[e] = np_lerp(lo, hi, 0.25 * (double)rem4[e]);
+    }
+    // ---- whiskers and fliers, as net_report_kernel's
+    const double iqr = __dsub_rn(qv[2], qv[0]);
+    const double lim0 = __dsub_rn(qv[0], __dmul_rn(1.5, iqr)), lim1 = __dadd_rn(qv[2], __dmul_rn(1.5, iqr));
+    double wk[2] = {ninf, ninf};
+    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
+        const double v = key_val(k);              // (a NaN for an entry left out: every test fails)
+        if (v >= lim0) wk[0] = fmax(wk[0], -v);
+        if (v <= lim1) wk[1] = fmax(wk[1], v);
+    });
+    block_reduce_multi<NT, 2, false>(wk, red);
+    const double wlo = (wk[0] == ninf || -wk[0] > qv[0]) ? qv[0] : -wk[0];
+    const double whi = (wk[1] == ninf || wk[1] < qv[2]) ? qv[2] : wk[1];
+    double fl[1] = {0.0};
+    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
+        const double v = key_val(k);
+        fl[0] += (v < wlo || v > whi) ? 1.0 : 0.0;
+    });
+    block_reduce_multi<NT, 1, true>(fl, red);
+    if (tid == 0) {
+        const long long code = (long long)-wc[0];
+        r.min = -x[0]; r.q1 = qv[0]; r.median = qv[1]; r.q3 = qv[2]; r.max = x[1];
+        r.whisker_lo = wlo; r.whisker_hi = whi;
+        r.n_fliers = (int)fl[0];
+        r.worst_scenario = (int)(code >> 16); r.worst_index = (int)(code & 0xFFFF);
+        if (q == 0) r.worst_value = x[1];
+        *out = r;
+    }
+    // the worst node's own voltage: its owner knows it (written behind thread 0's record)
+    __syncthreads();
+    if (q == 1 && wcode == wc[0]) out->worst_value = vworst;
+}
+
 }  // namespace revs
 
 using namespace revs;
@@ -501,39 +771,112 @@ extern "C" int revs_net_node_sums(int32_t m, int32_t T, const int64_t *node_ptr,
     return REVS_OK;
 }
 
-extern "C" int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g, const double *rating,
-                               const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out, double vset,
-                               double vmin, double vmax, double *flow_out, double *loading_out, double *volt_out,
-                               revs_net_summary_t *summary_out, void *stream) {
-    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_net_report: T=%d outside 1..%d", (int)T, REVS_MAX_T);
-    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "revs_net_report: m=%d outside 1..65535", (int)m);
-    REVS_REQUIRE(tree && node_g && tree->pack && tree->w, "revs_net_report: null pointer argument");
+// revs_net_report's and revs_net_study's common checks, and their launch on a T x S grid
+static int net_report_check(const char *who, int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g,
+                            int32_t n_out, double vset, double vmin, double vmax) {
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
+    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "%s: m=%d outside 1..65535", who, (int)m);
+    REVS_REQUIRE(tree && node_g && tree->pack && tree->w, "%s: null pointer argument", who);
     REVS_REQUIRE(tree->n > 0 && tree->n <= REVS_TREE_MAX && tree->n % tree_shape(tree->n).ipt == 0,
-                 "revs_net_report: tree of %d nodes (at most %d, a multiple of 8; of 16 beyond 8192)", (int)tree->n,
+                 "%s: tree of %d nodes (at most %d, a multiple of 8; of 16 beyond 8192)", who, (int)tree->n,
                  REVS_TREE_MAX);
-    REVS_REQUIRE(n_out > 0 && n_out <= tree->n, "revs_net_report: n_out=%d outside 1..tree nodes", (int)n_out);
-    REVS_REQUIRE(vset == vset && vset >= 0.0 && vset < INFINITY, "revs_net_report: vset must be finite and >= 0");
-    REVS_REQUIRE(vmin <= vmax, "revs_net_report: vmin > vmax");         // (also rejects NaN)
-    REVS_REQUIRE(flow_out || loading_out || volt_out || summary_out, "revs_net_report: every output is NULL");
+    REVS_REQUIRE(n_out > 0 && n_out <= tree->n, "%s: n_out=%d outside 1..tree nodes", who, (int)n_out);
+    REVS_REQUIRE(vset == vset && vset >= 0.0 && vset < INFINITY, "%s: vset must be finite and >= 0", who);
+    REVS_REQUIRE(vmin <= vmax, "%s: vmin > vmax", who);                 // (also rejects NaN)
+    return REVS_OK;
+}
+
+static int net_report_launch(const char *who, int32_t S, int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g,
+                             const double *rating, const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out,
+                             double vset, double vmin, double vmax, const double *band, int32_t B, double *flow_out,
+                             double *loading_out, double *volt_out, revs_net_summary_t *summary_out,
+                             int32_t *band_count_out, void *stage, void *stream) {
     NetArgs A;
     A.tr = TreeArgs{tree->n, (const unsigned long long *)tree->pack, tree->w};
     A.g = node_g; A.rating = rating; A.mask = node_mask; A.nop = node_of_pos;
     A.m = m; A.T = T; A.n_out = n_out;
     A.vset2 = vset * vset; A.vmin = vmin; A.vmax = vmax;
     A.flow = flow_out; A.loading = loading_out; A.volt = volt_out; A.sum = summary_out;
+    for (int b = 0; b < REVS_STUDY_MAX_BANDS; ++b) A.band[b] = b < B ? band[b] : -INFINITY;
+    A.bandc = B > 0 ? band_count_out : nullptr; A.nband = B;
+    A.stage = (unsigned long long *)stage;
     const size_t lds = net_lds_bytes(tree->n);
     const TreeShape sh = tree_shape(tree->n);
 #define NK(NT, IPT)                                                                                              \
     do {                                                                                                         \
         if (!grant_lds(reinterpret_cast<const void *>(net_report_kernel<NT, IPT>), lds, "network report"))       \
             return REVS_ELAUNCH;                                                                                 \
-        hipLaunchKernelGGL((net_report_kernel<NT, IPT>), dim3(T), dim3(NT), lds, (hipStream_t)stream, A);        \
+        hipLaunchKernelGGL((net_report_kernel<NT, IPT>), dim3(T, S), dim3(NT), lds, (hipStream_t)stream, A);     \
     } while (0)
     if (sh.nt == 256) NK(256, 8);
     else if (sh.nt == 512) NK(512, 8);
     else if (sh.ipt == 8) NK(1024, 8);
     else NK(1024, 16);
 #undef NK
-    REVS_CHECK_LAUNCH("revs_net_report");
+    REVS_CHECK_LAUNCH(who);
+    return REVS_OK;
+}
+
+extern "C" int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g, const double *rating,
+                               const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out, double vset,
+                               double vmin, double vmax, double *flow_out, double *loading_out, double *volt_out,
+                               revs_net_summary_t *summary_out, void *stream) {
+    const char *who = "revs_net_report";
+    const int rc = net_report_check(who, m, T, tree, node_g, n_out, vset, vmin, vmax);
+    if (rc != REVS_OK) return rc;
+    REVS_REQUIRE(flow_out || loading_out || volt_out || summary_out, "%s: every output is NULL", who);
+    return net_report_launch(who, 1, m, T, tree, node_g, rating, node_mask, node_of_pos, n_out, vset, vmin, vmax, nullptr, 0,
+                             flow_out, loading_out, volt_out, summary_out, nullptr, nullptr, stream);
+}
+
+extern "C" int64_t revs_net_study_scratch(int32_t S, int32_t T, int32_t tree_n) {
+    if (S < 1 || S > REVS_STUDY_MAX_S || T < 1 || T > REVS_MAX_T || tree_n < 1 || tree_n > REVS_TREE_MAX) return 0;
+    return (int64_t)2 * S * T * tree_n * (int64_t)sizeof(unsigned long long);
+}
+
+extern "C" int revs_net_study(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g,
+                              const double *rating, const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out,
+                              double vset, double vmin, double vmax, const int32_t *group, int32_t G, const double *band,
+                              int32_t B, double *flow_out, double *loading_out, double *volt_out,
+                              revs_net_summary_t *summary_out, revs_net_pooled_t *pooled_out, int32_t *band_count_out,
+                              void *scratch, void *stream) {
+    static_assert(sizeof(revs_net_pooled_t) == 96 && sizeof(revs_net_pooled_t) == sizeof(revs_net_summary_t), "");
+    const char *who = "revs_net_study";
+    REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
+    const int rc = net_report_check(who, m, T, tree, node_g, n_out, vset, vmin, vmax);
+    if (rc != REVS_OK) return rc;
+    REVS_REQUIRE(G >= 0 && G <= S, "%s: G=%d outside 0..S", who, (int)G);
+    REVS_REQUIRE(B >= 0 && B <= REVS_STUDY_MAX_BANDS, "%s: B=%d outside 0..%d", who, (int)B, REVS_STUDY_MAX_BANDS);
+    REVS_REQUIRE(G == 0 || group, "%s: group is NULL with G > 0", who);
+    REVS_REQUIRE(B == 0 || band, "%s: band is NULL with B > 0", who);
+    for (int s = 0; s < S && G > 0; ++s)
+        REVS_REQUIRE(group[s] >= -1 && group[s] < G, "%s: group[%d]=%d outside -1..G-1", who, s, (int)group[s]);
+    for (int b = 0; b < B; ++b)
+        REVS_REQUIRE(band[b] - band[b] == 0.0, "%s: band[%d] is not finite", who, b);
+    const bool bands = B > 0 && band_count_out, pooled = pooled_out != nullptr;
+    REVS_REQUIRE(flow_out || loading_out || volt_out || summary_out || pooled || bands, "%s: every output is NULL", who);
+    REVS_REQUIRE(!pooled || G > 0, "%s: pooled_out with G == 0", who);
+    REVS_REQUIRE(!pooled || scratch, "%s: pooled_out needs scratch (revs_net_study_scratch bytes)", who);
+    REVS_REQUIRE(!pooled || ((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", who);
+    const int rc2 = net_report_launch(who, S, m, T, tree, node_g, rating, node_mask, node_of_pos, n_out, vset, vmin, vmax, band,
+                                      bands ? B : 0, flow_out, loading_out, volt_out, summary_out, band_count_out,
+                                      pooled ? scratch : nullptr, stream);
+    if (rc2 != REVS_OK || !pooled) return rc2;
+    // the groups' member masks travel as kernel arguments: as many groups per launch as kPoolMaskWords holds
+    PoolArgs P;
+    P.stage = (const unsigned long long *)scratch; P.nop = node_of_pos; P.out = pooled_out;
+    P.S = S; P.T = T; P.n = tree->n; P.n_out = n_out; P.words = (S + 63) / 64;
+    P.vmin = vmin; P.vmax = vmax;
+    const int per = kPoolMaskWords / P.words;
+    for (int g0 = 0; g0 < G; g0 += per) {
+        const int ng = G - g0 < per ? G - g0 : per;
+        for (int i = 0; i < kPoolMaskWords; ++i) P.member[i] = 0ull;
+        for (int s = 0; s < S; ++s)
+            if (group[s] >= g0 && group[s] < g0 + ng)
+                P.member[(size_t)(group[s] - g0) * P.words + s / 64] |= 1ull << (s % 64);
+        P.g0 = g0;
+        hipLaunchKernelGGL(net_pool_kernel, dim3(T, 2, ng), dim3(kPoolNT), 0, (hipStream_t)stream, P);
+        REVS_CHECK_LAUNCH(who);
+    }
     return REVS_OK;
 }

@@ -39,20 +39,27 @@ def _node_profile(graph, p_sch):
     return res, nonsub, np.array([p_sch[h] for h in res], np.float64)
 
 
-def compute_flows(graph, p_sch, rating=None, device="cuda:0"):
-    """drawing.py:29-58: {edge: [flow / rating per slot]} in graph.edges order, signed like the reference's
-    A^-1 P (positive from the edge's first node to its second; the box plots take the absolute value)."""
+def line_nodes(graph, rating, parent, nonsub):
+    """-> (rating per tree node: that of the line to its parent; the tree node below each edge of graph.edges; the
+    edge's sign towards it)."""
     rate = _edge_ratings(graph, rating)
-    res, nonsub, P = _node_profile(graph, p_sch)
-    parent, edge_r, cons_of = feeder_arrays(graph, res)
     pos = {n: i for i, n in enumerate(nonsub)}
-    child = np.empty(len(rate), np.int64)       # the tree node below each edge, and the edge's sign towards it
+    child = np.empty(len(rate), np.int64)
     sign = np.empty(len(rate))
     for k, (u, v) in enumerate(graph.edges):
         down = pos.get(v, -1) >= 0 and parent[pos[v]] == pos.get(u, -1)
         child[k], sign[k] = (pos[v], 1.0) if down else (pos[u], -1.0)
     node_rating = np.zeros(len(nonsub))
     node_rating[child] = rate
+    return node_rating, child, sign
+
+
+def compute_flows(graph, p_sch, rating=None, device="cuda:0"):
+    """drawing.py:29-58: {edge: [flow / rating per slot]} in graph.edges order, signed like the reference's
+    A^-1 P (positive from the edge's first node to its second; the box plots take the absolute value)."""
+    res, nonsub, P = _node_profile(graph, p_sch)
+    parent, edge_r, cons_of = feeder_arrays(graph, res)
+    node_rating, child, sign = line_nodes(graph, rating, parent, nonsub)
     rep = report_for_tree(parent, edge_r, cons_of, P, rating=node_rating, device=device)
     signed = sign[:, None] * np.sign(rep.flow[child]) * rep.loading[child]
     return {e: signed[k].tolist() for k, e in enumerate(graph.edges)}

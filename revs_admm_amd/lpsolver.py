@@ -21,7 +21,7 @@ from . import _lib
 from .engine import AdmmEngine, OperatorOptions, pack_homes, residence_solve
 
 __all__ = ["compute_Rmat", "solve_ADMM", "solve_residence", "solve_residences",
-           "solve_central", "homes_to_arrays", "feeder_arrays"]
+           "solve_central", "homes_to_arrays", "feeder_arrays", "feeder_of"]
 
 
 def compute_Rmat(graph) -> np.ndarray:
@@ -97,9 +97,20 @@ def homes_to_arrays(homes, res):
     return load, rec
 
 
+def feeder_of(graph):
+    """What solve_ADMM forms from the graph alone -> (R_res, feeder_arrays): the residences' block
+    of compute_Rmat (lpsolver.py:184-189) and the feeder as a tree."""
+    res = [n for n in graph if graph.nodes[n]["label"] == "H"]
+    nonsub = [n for n in graph.nodes if graph.nodes[n]["label"] != "S"]  # lpsolver.py:166
+    R = compute_Rmat(graph)
+    pos = {n: i for i, n in enumerate(nonsub)}
+    resind = [pos[n] for n in res]                                      # lpsolver.py:188-189
+    return R[np.ix_(resind, resind)], feeder_arrays(graph, res)
+
+
 def solve_ADMM(homes, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
                vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None,
-               return_engine=False):
+               return_engine=False, feeder=None):
     """Reference lpsolver.py:242-290.  Returns (diff, P_sch, S, C):
         diff[k+1][h]  float      |P_est[k+1][h] - P_sch[k+1][h]| / T
         P_sch[h]      list[T]    residence net load g_opt of the last iteration
@@ -108,22 +119,19 @@ def solve_ADMM(homes, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.
     `mode="binary"` is the reference's on/off charger (its MIQP, solved exactly);
     `mode="relaxed"` the continuous box+SOC QP solved by the batched PDHG kernel.
     A residence whose window cannot reach 90% SOC raises RevsError where the
-    reference prints 'No solution found' and exits."""
+    reference prints 'No solution found' and exits.  `feeder`: feeder_of(graph), formed
+    once by a caller that solves many scenarios on one graph (REVS.study)."""
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]          # lpsolver.py:167
-    nonsub = [n for n in graph.nodes if graph.nodes[n]["label"] != "S"]  # lpsolver.py:166
     missing = [h for h in res if h not in homes]
     if missing:
         raise KeyError(f"homes lacks residence {missing[0]} of the network")
     load, rec = homes_to_arrays(homes, res)
     if load.shape[1] != len(cost):
         raise ValueError("LOAD and cost must have the same number of slots")
-    R = compute_Rmat(graph)
-    pos = {n: i for i, n in enumerate(nonsub)}
-    resind = [pos[n] for n in res]                                      # lpsolver.py:188-189
-    R_res = R[np.ix_(resind, resind)]
+    R_res, feeder = feeder if feeder is not None else feeder_of(graph)
     eng = AdmmEngine(np.asarray(cost, float), rec, load, np.arange(len(res)), R_res, kappa=kappa,
                      vset=vset, vlow=vlow, vhigh=vhigh, mode=mode, device=device, op=operator,
-                     feeder=feeder_arrays(graph, res))
+                     feeder=feeder)
     d = eng.run(iter_max)
     P_sch, S, C = eng.result()
     diff = {k + 1: {h: float(d[k, i]) for i, h in enumerate(res)} for k in range(iter_max)}

@@ -66,13 +66,10 @@ class NetworkReport:
         return self._worst(self.summary_volt, np.maximum(self.vmin - v, v - self.vmax))
 
 
-def run_report(lib, dev, stream, tree, tree_host, n_nodes, node_g, rating=None, nodes=None, vset=1.0, vmin=0.95,
-               vmax=1.05, arrays=True) -> NetworkReport:
-    """revs_net_report on node sums that lie on the device.  tree: _lib.Tree (device pack / w), tree_host: the dict of
-    feeder_tree, n_nodes: its nodes before padding; node_g: (M, T) float64 device tensor; rating: per tree node (kVA of
-    the line to its parent; NaN or <= 0: unrated) or None; nodes: indices or a boolean mask of the nodes the
-    voltage summary covers (None: all)."""
-    M, T = node_g.shape
+def side_arrays(dev, tree_host, n_nodes, rating=None, nodes=None):
+    """The per-position device arrays of revs_net_report / revs_net_study -> (node_of_pos, rating or None, mask or
+    None): the caller's node index at every preorder position (-1: padding), the rating of the line above it (0:
+    unrated) and whether the voltage summary covers it."""
     order = np.asarray(tree_host["order"], np.int64)
     real = order < n_nodes
     src = np.where(real, order, 0)
@@ -89,6 +86,29 @@ def run_report(lib, dev, stream, tree, tree_host, n_nodes, node_g, rating=None, 
         mk = np.zeros(n_nodes, bool)
         mk[np.asarray(nodes)] = True
         d_mask = up((mk[src] & real).astype(np.uint8))
+    return d_nop, d_rating, d_mask
+
+
+def tree_on_device(dev, parent, edge_r, cons_of, n_rows):
+    """feeder_tree of the whole feeder (every row kept) and its device form -> (tree_host, _lib.Tree, the tensors
+    that back it: keep them alive)."""
+    from .feeder import feeder_tree
+    if len(parent) > _lib.TREE_MAX:
+        raise ValueError(f"feeder has {len(parent)} nodes; the tree form holds {_lib.TREE_MAX}")
+    th = feeder_tree(parent, edge_r, cons_of, np.ones(n_rows, bool))
+    d_pack = torch.from_numpy(th["pack"].view(np.int64)).to(dev)
+    d_w = torch.from_numpy(th["w"]).to(dev)
+    return th, _lib.Tree(th["n"], ptr(d_pack), ptr(d_w)), (d_pack, d_w)
+
+
+def run_report(lib, dev, stream, tree, tree_host, n_nodes, node_g, rating=None, nodes=None, vset=1.0, vmin=0.95,
+               vmax=1.05, arrays=True) -> NetworkReport:
+    """revs_net_report on node sums that lie on the device.  tree: _lib.Tree (device pack / w), tree_host: the dict of
+    feeder_tree, n_nodes: its nodes before padding; node_g: (M, T) float64 device tensor; rating: per tree node (kVA of
+    the line to its parent; NaN or <= 0: unrated) or None; nodes: indices or a boolean mask of the nodes the
+    voltage summary covers (None: all)."""
+    M, T = node_g.shape
+    d_nop, d_rating, d_mask = side_arrays(dev, tree_host, n_nodes, rating, nodes)
     f64 = dict(dtype=torch.float64, device=dev)
     out = [torch.empty(n_nodes, T, **f64) for _ in range(3)] if arrays else [None] * 3
     d_sum = torch.zeros(2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
@@ -106,16 +126,10 @@ def report_for_tree(parent, edge_r, cons_of, node_p, rating=None, nodes=None, vs
     """The report of node injections held on the host: node_p (M, T), row cons_of[i] injected at tree node i.  (The
     engine's network_report sums the residences on the device instead.)"""
     from .engine import _dev_check
-    from .feeder import feeder_tree
     lib, dev = _lib.load(), _dev_check(device)
     node_p = np.ascontiguousarray(node_p, np.float64)
-    if len(parent) > _lib.TREE_MAX:
-        raise ValueError(f"feeder has {len(parent)} nodes; the tree form holds {_lib.TREE_MAX}")
-    th = feeder_tree(parent, edge_r, cons_of, np.ones(node_p.shape[0], bool))
     with torch.cuda.device(dev):
-        d_pack = torch.from_numpy(th["pack"].view(np.int64)).to(dev)
-        d_w = torch.from_numpy(th["w"]).to(dev)
-        tree = _lib.Tree(th["n"], ptr(d_pack), ptr(d_w))
+        th, tree, _keep = tree_on_device(dev, parent, edge_r, cons_of, node_p.shape[0])
         g = torch.from_numpy(node_p).to(dev)
         return run_report(lib, dev, torch.cuda.current_stream(dev).cuda_stream, tree, th, len(parent), g, rating,
                           nodes, vset, vmin, vmax, arrays)

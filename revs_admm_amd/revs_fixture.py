@@ -97,11 +97,71 @@ class REVS:
             homes, dist, tariff, None, kappa=kwargs.get("kappa", 5.0),
             iter_max=kwargs.get("max_iterations", 15), vset=kwargs.get("v0", 1.03),
             vlow=kwargs.get("vlow", 0.95), vhigh=kwargs.get("vhigh", 1.05),
-            mode=kwargs.get("mode", "binary"), device=self.device)
+            mode=kwargs.get("mode", "binary"), device=self.device, feeder=kwargs.get("feeder"))
         if save:
             self._save(combine_result(Pres, Pev, soc, kwargs.get("ev_homes"), diff),
                        kwargs.get("adoption", 90), kwargs.get("rating", 4800), kwargs.get("seed"))
         return Pres, Pev, soc
+
+    def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
+              methods=("distributed", "individual"), group_by="method", **opt):
+        """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
+        compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
+        and reported in one call -> (labels, study.StudyReport).
+
+        For every adoption (%), rating (W) and seed -- in that nesting -- the EV homes are drawn from `community`
+        exactly as read_inputs draws them, then every method of `methods` is solved; labels[s] = dict(method,
+        adoption, rating, seed) of scenario s.  ONE study_report over all schedules' P_res follows, with
+        nodes=community, the graph's line ratings, and pools by `group_by`: one label key or a tuple of them, a group
+        being one distinct combination in order of first appearance ("method" at one adoption and rating:
+        compare_method; "adoption" at one method: compare_adoption; "rating": compare_rating; ("method", "adoption"):
+        every box of a grid).  StudyReport.band_counts / band_mean are compare_node_counts' bars.
+
+        **opt: read_inputs' capacity, initial_soc, start_time, end_time; get_distributed_optimal's kappa,
+        max_iterations, v0, vlow, vhigh, mode; the report's bands, vmin, vmax, arrays, report_vset (default 1.0, as
+        drawing.compute_voltage) and line_rating ({line type: kVA}; default: the edges' `rating` attribute; without
+        either the loading records are empty).  The feeder's matrix and tree are formed once."""
+        from .drawing import line_nodes
+        from .lpsolver import feeder_of
+        from . import study as st
+        keys = (group_by,) if isinstance(group_by, str) else tuple(group_by)
+        unknown = [k for k in keys if k not in ("method", "adoption", "rating", "seed")]
+        unknown += [m for m in methods if m not in ("distributed", "individual")]
+        if unknown:
+            raise ValueError(f"REVS.study: unknown group key or method {unknown[0]!r}")
+        res = [n for n in dist if dist.nodes[n]["label"] == "H"]
+        nonsub = [n for n in dist if dist.nodes[n]["label"] != "S"]
+        pos = {n: i for i, n in enumerate(nonsub)}
+        feeder = feeder_of(dist)
+        parent, edge_r, cons_of = feeder[1]
+        node_rating = None
+        edges = list(dist.edges)
+        if opt.get("line_rating") is not None or (edges and all("rating" in dist.edges[e] for e in edges)):
+            node_rating = line_nodes(dist, opt.get("line_rating"), parent, nonsub)[0]
+        labels, profiles = [], []
+        for adoption in adoptions:
+            for rating in ratings:
+                for seed in seeds:
+                    np.random.seed(int(seed))                  # revs_fixture.py:175-177
+                    ev_homes = np.random.choice(community, int(adoption * 1e-2 * len(community)), replace=False)
+                    homes = get_homes_ev_param(all_homes, dist, ev_homes, rating * 1e-3, opt.get("capacity", 20),
+                                               opt.get("initial_soc", 0.2), opt.get("start_time", 11),
+                                               opt.get("end_time", 23))
+                    for method in methods:
+                        if method == "distributed":
+                            P_res = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[0]
+                        else:
+                            P_res = self.get_individual_optimal(tariff, homes)[0]
+                        labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
+                        profiles.append(np.array([P_res[h] for h in res], np.float64))
+        combos = [tuple(lab[k] for k in keys) for lab in labels]
+        order = list(dict.fromkeys(combos))
+        rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
+                              rating=node_rating, nodes=[pos[h] for h in community],
+                              bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
+                              vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
+                              arrays=opt.get("arrays", False), device=self.device)
+        return labels, rep
 
     def result_frames(self, demand, dist, community=None, start=11, end=23, shift=6, rating=None):
         """The two long tables the reference's box plots are drawn from (drawing.py:125-176, boxplot_flow /

@@ -1,0 +1,143 @@
+"""The study report: the network report of S schedules on one feeder in one pass on the GPU -- what the reference's
+published figures are made of (test-dist-ind-opt.py:219-342 compare_method / compare_rating / compare_adoption: box
+plots per hour pooled over all seeds of a group; test-dist-ind-adopt.py:73-117 compare_node_counts: per seed and hour
+the number of residences at or below 0.92 / 0.95 / 0.98 p.u.).  revs_net_study (include/revs_admm_ops.h, DESIGN.md
+section 3.8): per-schedule summaries and band counts from revs_net_report's kernel on a slots x schedules grid, and the
+pooled box-plot numbers by an exact selection over the group's staged keys.  Drawing stays outside the project."""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr
+from .network import SUMMARY_DTYPE, side_arrays, tree_on_device
+
+# revs_net_pooled_t (include/revs_admm_ops.h): revs_net_summary_t with worst_scenario in the first reserved word
+POOLED_DTYPE = np.dtype([("min", "<f8"), ("q1", "<f8"), ("median", "<f8"), ("q3", "<f8"), ("max", "<f8"),
+                         ("whisker_lo", "<f8"), ("whisker_hi", "<f8"), ("worst_value", "<f8"), ("count", "<i4"),
+                         ("n_fliers", "<i4"), ("n_violations", "<i4"), ("n_nan", "<i4"), ("worst_index", "<i4"),
+                         ("worst_scenario", "<i4"), ("reserved", "<i4", (2,))])
+assert POOLED_DTYPE.itemsize == 96
+
+
+@dataclass
+class StudyReport:
+    """summary_loading / summary_volt: (S, T) SUMMARY_DTYPE records, scenario s's as report_for_tree gives them.
+    pooled_loading / pooled_volt: (G, T) POOLED_DTYPE records over all values of a group's scenarios ((0, T) without
+    groups).  band_counts: (S, T, B) int32, the nodes of `nodes` with volt <= bands[b] (cumulative; NaNs never
+    counted).  flow, loading, volt: (S, nodes, T) float64 or None (arrays=False).  groups: (S,) int, -1: in no pool.
+    node_p: (S, M, T) float64, the profiles reported."""
+    summary_loading: np.ndarray
+    summary_volt: np.ndarray
+    pooled_loading: np.ndarray
+    pooled_volt: np.ndarray
+    band_counts: np.ndarray
+    bands: tuple
+    groups: np.ndarray
+    flow: np.ndarray | None
+    loading: np.ndarray | None
+    volt: np.ndarray | None
+    node_p: np.ndarray
+    vset: float
+    vmin: float
+    vmax: float
+
+    @property
+    def n_groups(self):
+        return len(self.pooled_volt)
+
+    def band_mean(self):
+        """(G, T, B): the mean of the band counts over each group's scenarios -- the height of the reference's bars
+        (seaborn.barplot's estimator).  Its error bars are bootstrapped, i.e. random, and are not reproduced:
+        band_range gives the spread instead.  NaN for a group without scenarios."""
+        out = np.full((self.n_groups,) + self.band_counts.shape[1:], np.nan)
+        for g in range(self.n_groups):
+            if (self.groups == g).any():
+                out[g] = self.band_counts[self.groups == g].mean(axis=0)
+        return out
+
+    def band_range(self):
+        """((G, T, B), (G, T, B)): the smallest and the largest band count over each group's scenarios (-1 for a
+        group without scenarios)."""
+        lo = np.full((self.n_groups,) + self.band_counts.shape[1:], -1, np.int32)
+        hi = lo.copy()
+        for g in range(self.n_groups):
+            if (self.groups == g).any():
+                lo[g] = self.band_counts[self.groups == g].min(axis=0)
+                hi[g] = self.band_counts[self.groups == g].max(axis=0)
+        return lo, hi
+
+
+def native_study(parent, edge_r, cons_of, node_p, groups, n_groups, bands, rating, nodes, vset, vmin, vmax, arrays,
+                 device) -> StudyReport:
+    """revs_net_study on checked arguments: node_p (S, M, T) float64, groups (S,) int32 in -1 .. n_groups - 1.  The
+    one place the library is called from (a host test puts tests/study_ref.py here)."""
+    from .engine import _dev_check
+    lib, dev = _lib.load(), _dev_check(device)
+    S, M, T = node_p.shape
+    n, B, G = len(parent), len(bands), int(n_groups)
+    with torch.cuda.device(dev):
+        th, tree, _keep = tree_on_device(dev, parent, edge_r, cons_of, M)
+        d_nop, d_rating, d_mask = side_arrays(dev, th, n, rating, nodes)
+        g = torch.from_numpy(node_p).to(dev)
+        out = [torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays else [None] * 3
+        d_sum = torch.zeros(S * 2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        d_pool = d_scratch = d_band = None
+        if G:                                   # staging only when pools are asked for
+            d_pool = torch.zeros(G * 2 * T * POOLED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            nbytes = int(lib.revs_net_study_scratch(S, T, th["n"]))
+            if nbytes <= 0:
+                raise ValueError(f"study report: no staging size for S={S}, T={T}, tree of {th['n']}")
+            d_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        if B:
+            d_band = torch.zeros(S, T, B, dtype=torch.int32, device=dev)
+        h_group = np.ascontiguousarray(groups, np.int32)
+        h_band = np.ascontiguousarray(bands, np.float64)
+        check(lib.revs_net_study(S, M, T, C.byref(tree), ptr(g), ptr(d_rating), ptr(d_mask), ptr(d_nop), n, float(vset),
+                                 float(vmin), float(vmax), h_group.ctypes.data if G else None, G,
+                                 h_band.ctypes.data if B else None, B, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                 ptr(d_sum), ptr(d_pool), ptr(d_band), ptr(d_scratch),
+                                 torch.cuda.current_stream(dev).cuda_stream), "revs_net_study")
+        rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, 2, T)
+        pool = (d_pool.cpu().numpy().view(POOLED_DTYPE).reshape(G, 2, T) if G
+                else np.zeros((0, 2, T), POOLED_DTYPE))
+        counts = d_band.cpu().numpy() if B else np.zeros((S, T, 0), np.int32)
+        flow, loading, volt = (None if o is None else o.cpu().numpy() for o in out)
+    return StudyReport(rec[:, 0].copy(), rec[:, 1].copy(), pool[:, 0].copy(), pool[:, 1].copy(), counts,
+                       tuple(float(b) for b in bands), np.asarray(groups, np.int64).copy(), flow, loading, volt,
+                       node_p, float(vset), float(vmin), float(vmax))
+
+
+def study_report(parent, edge_r, cons_of, node_p, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98),
+                 vset=1.0, vmin=0.95, vmax=1.05, arrays=False, device="cuda:0") -> StudyReport:
+    """The report of S schedules on one feeder (network.report_for_tree's arguments; node_p is (S, M, T): row
+    cons_of[i] of scenario s injected at tree node i).
+
+    groups    None: per-scenario outputs only (no staging is allocated).  Else one integer per scenario: the pool it
+              belongs to, 0 .. G-1 with G = max + 1; -1: in none.  pooled_loading / pooled_volt[g] are the box-plot
+              numbers over all values of group g's scenarios -- not obtainable from the per-scenario records, since
+              quantiles do not compose.
+    bands     up to 8 voltage thresholds, any order: band_counts[s, t, b] nodes of `nodes` at or below bands[b].
+    nodes     the nodes the voltage summaries, pools and band counts cover (the reference: the community); None: all.
+    arrays    True: also flow / loading / volt of every scenario, (S, nodes, T)."""
+    node_p = np.ascontiguousarray(node_p, np.float64)
+    if node_p.ndim != 3:
+        raise ValueError(f"study report: node_p must be (scenarios, rows, slots), got {node_p.shape}")
+    S = node_p.shape[0]
+    if not 1 <= S <= _lib.STUDY_MAX_S:
+        raise ValueError(f"study report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    bands = tuple(float(b) for b in bands)
+    if len(bands) > _lib.STUDY_MAX_BANDS or not np.isfinite(bands).all():
+        raise ValueError(f"study report: at most {_lib.STUDY_MAX_BANDS} finite bands, got {bands}")
+    if groups is None:
+        gid, G = np.full(S, -1, np.int32), 0
+    else:
+        gid = np.asarray(groups)
+        if gid.shape != (S,) or not np.issubdtype(gid.dtype, np.integer) or gid.min() < -1:
+            raise ValueError(f"study report: groups must be {S} integers >= -1")
+        gid, G = gid.astype(np.int32), int(gid.max()) + 1
+    return native_study(parent, edge_r, cons_of, node_p, gid, G, bands, rating, nodes, vset, vmin, vmax, arrays, device)
