@@ -241,6 +241,15 @@ int revs_op_export(int64_t n_homes, int32_t T, const double *sb, float *p_est, v
  *   revs_op_dual_step    y_trial = y at the candidates moved by alpha[t] towards yhat (all
  *                        other entries of y_trial must already equal y);
  *                        lin_out[8 t] = gradient . (y_trial - y)                         */
+/* Columns of one launch.  The slots are independent problems, so S scenarios of one feeder (same residences on the same
+ * nodes, state float[n][S][T]) are ONE operator problem of S T columns (revs_admm_amd/ensemble.py): every
+ * entry point of this section that takes T takes up to REVS_ENS_MAX_COLS of them -- the home pass and the row pass of the
+ * dense form (revs_op_dual_eval, _eval_rows, revs_op_dual_rows / _select) walk tiles of 256 columns with a second grid
+ * dimension beyond 256, the others are one workgroup per column.  Up to 256 columns every launch is what it was.  The
+ * dense products keep their own limit (n <= 192 columns): beyond it revs_op_dual_evaluate needs the feeder as a tree
+ * (revs_op_dual_evaluate_tree).  The kernels of the ADMM forms above and the folded chain stay at 256 columns; the ADMM
+ * forms as a solver need the dense products, hence 192. */
+#define REVS_ENS_MAX_COLS 1024
 int revs_op_dual_eval(int32_t m, int32_t T, const int64_t *node_ptr, const float *p_est,
                       const float *p_sch, const float *gamma, int32_t nslab, const double *dsl,
                       double kappa, double *pnq, float *p_est_new, void *stream);

@@ -258,6 +258,8 @@ SIGNATURES = {
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
 DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 feeder; 80 / 128: 11.2 ms against 9.5, r05)
 DUAL_AMAX_BIG = 512      # REVS_DUAL_AMAX_BIG
+ENS_MAX_COLS = 1024      # REVS_ENS_MAX_COLS: columns (scenarios x slots) of one dual Newton launch
+MAX_T = 192              # REVS_MAX_T: slots of a residence sweep, columns of a dense product
 
 _lib = None
 

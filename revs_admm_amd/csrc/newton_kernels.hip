@@ -41,7 +41,9 @@ struct SparseD {
     const double *y;          // [m][T]
 };
 
-template <int TL>
+// TILED (more than 256 columns: an ensemble of scenarios, revs_admm_ops.h): blockIdx.y walks tiles of TL = 256 columns --
+// every column's arithmetic is what the untiled instantiation does for it, in the same order.
+template <int TL, bool TILED = false>
 __global__ __launch_bounds__(256) void op_dual_eval_kernel(
         int m, int T, const int64_t *__restrict__ node_ptr, const float *__restrict__ pe,
         const float *__restrict__ ps, const float *__restrict__ gm, int nslab,
@@ -49,7 +51,8 @@ __global__ __launch_bounds__(256) void op_dual_eval_kernel(
         float *__restrict__ pe_new, const SparseD sp) {
     constexpr int HS = 256 / TL;
     const int node = blockIdx.x;
-    const int t = threadIdx.x % TL, hs = threadIdx.x / TL;
+    const int tl = threadIdx.x % TL, hs = threadIdx.x / TL;
+    const int t = TILED ? tl + (int)blockIdx.y * TL : tl;
     const bool tok = t < T;
     const int64_t total = (int64_t)m * T;
     const int idx = node * T + (tok ? t : 0);
@@ -94,12 +97,12 @@ __global__ __launch_bounds__(256) void op_dual_eval_kernel(
         }
     }
     __shared__ double red[3][HS][TL];
-    red[0][hs][t] = ap; red[1][hs][t] = an; red[2][hs][t] = aq;
+    red[0][hs][tl] = ap; red[1][hs][tl] = an; red[2][hs][tl] = aq;
     __syncthreads();
     if (hs == 0 && tok) {
-        double a = red[0][0][t], b = red[1][0][t], c = red[2][0][t];
+        double a = red[0][0][tl], b = red[1][0][tl], c = red[2][0][tl];
 #pragma unroll
-        for (int k = 1; k < HS; ++k) { a += red[0][k][t]; b += red[1][k][t]; c += red[2][k][t]; }
+        for (int k = 1; k < HS; ++k) { a += red[0][k][tl]; b += red[1][k][tl]; c += red[2][k][tl]; }
         pnq[idx] = a;
         pnq[idx + total] = b;
         pnq[idx + 2 * total] = -0.5 * kappa * c;
@@ -111,13 +114,15 @@ __global__ __launch_bounds__(256) void op_dual_eval_kernel(
 // violation of every row, and per-(row block, slot) partial reductions in a fixed order.
 // Workgroup = 8 rows x TL slot lanes; partial[blk][t] = {max residual, sum D terms,
 // rows with y != 0, violated rows with y = 0}.
-template <int TL>
+// (TILED: as op_dual_eval_kernel -- blockIdx.y walks tiles of 256 columns)
+template <int TL, bool TILED = false>
 __global__ __launch_bounds__(256) void op_dual_rows_kernel(
         int m, int T, int nslab, const double *__restrict__ vsl, const double *__restrict__ pnq,
         const double *__restrict__ y, double vlo, double vhi, double *__restrict__ vfull,
         double *__restrict__ viol, double *__restrict__ partial, double *__restrict__ zero_out) {
     constexpr int HS = 256 / TL;
-    const int t = threadIdx.x % TL, hs = threadIdx.x / TL;
+    const int tl = threadIdx.x % TL, hs = threadIdx.x / TL;
+    const int t = TILED ? tl + (int)blockIdx.y * TL : tl;
     const int rows_per = HS * ((m + HS * (int)gridDim.x - 1) / (HS * (int)gridDim.x));
     const int rb = blockIdx.x * rows_per;
     const int64_t total = (int64_t)m * T;
@@ -141,13 +146,13 @@ __global__ __launch_bounds__(256) void op_dual_rows_kernel(
         }
     }
     __shared__ double red[4][HS][TL];
-    red[0][hs][t] = rmax; red[1][hs][t] = dsum; red[2][hs][t] = nsup; red[3][hs][t] = nvio;
+    red[0][hs][tl] = rmax; red[1][hs][tl] = dsum; red[2][hs][tl] = nsup; red[3][hs][tl] = nvio;
     __syncthreads();
     if (hs == 0 && t < T) {
-        double a = red[0][0][t], b = red[1][0][t], c = red[2][0][t], d = red[3][0][t];
+        double a = red[0][0][tl], b = red[1][0][tl], c = red[2][0][tl], d = red[3][0][tl];
 #pragma unroll
         for (int k = 1; k < HS; ++k) {
-            a = fmax(a, red[0][k][t]); b += red[1][k][t]; c += red[2][k][t]; d += red[3][k][t];
+            a = fmax(a, red[0][k][tl]); b += red[1][k][tl]; c += red[2][k][tl]; d += red[3][k][tl];
         }
         double *o = partial + ((int64_t)blockIdx.x * T + t) * 4;
         o[0] = a; o[1] = b; o[2] = c; o[3] = d;
@@ -1990,7 +1995,7 @@ static int dual_eval_impl(int32_t m, int32_t T, const int64_t *node_ptr, const f
                           const float *p_sch, const float *gamma, int32_t nslab, const double *dsl,
                           double kappa, double *pnq, float *p_est_new, const SparseD &sp,
                           void *stream) {
-    REVS_REQUIRE(m > 0 && T > 0 && T <= 256 && node_ptr && p_est && p_sch && gamma && pnq &&
+    REVS_REQUIRE(m > 0 && T > 0 && T <= REVS_ENS_MAX_COLS && node_ptr && p_est && p_sch && gamma && pnq &&
                  kappa > 0, "revs_op_dual_eval: bad argument");
     REVS_REQUIRE(!dsl || nslab >= 1, "revs_op_dual_eval: nslab=%d", nslab);
 #define EV(TL)                                                                                 \
@@ -1999,7 +2004,10 @@ static int dual_eval_impl(int32_t m, int32_t T, const int64_t *node_ptr, const f
     if (T <= 32) EV(32);
     else if (T <= 64) EV(64);
     else if (T <= 128) EV(128);
-    else EV(256);
+    else if (T <= 256) EV(256);
+    else                 // an ensemble's columns: tiles of 256
+        hipLaunchKernelGGL((op_dual_eval_kernel<256, true>), dim3(m, (T + 255) / 256), dim3(256), 0, S_(stream), m, T,
+                           node_ptr, p_est, p_sch, gamma, nslab, dsl, kappa, pnq, p_est_new, sp);
 #undef EV
     REVS_CHECK_LAUNCH("revs_op_dual_eval");
     return REVS_OK;
@@ -2033,7 +2041,7 @@ static int dual_rows_select(int32_t m, int32_t T, int32_t nslab, const double *v
                             int64_t *cand_idx, int32_t *cand_cnt, double *cand_val, double *stats,
                             double seq, bool defer_select, double *zero_out, void *stream) {
     REVS_REQUIRE(m <= 16384, "revs_op_dual_select: m=%d exceeds 16384 rows", m);
-    REVS_REQUIRE(m > 0 && T > 0 && T <= 256 && nslab >= 1 && vsl && pnq && y && vfull && viol &&
+    REVS_REQUIRE(m > 0 && T > 0 && T <= REVS_ENS_MAX_COLS && nslab >= 1 && vsl && pnq && y && vfull && viol &&
                  partial && cand_idx && cand_cnt && cand_val && stats && vlo <= vhi && kadd >= 0,
                  "revs_op_dual_select: bad argument");
     const int nblk = revs_op_dual_blocks(m);
@@ -2043,7 +2051,10 @@ static int dual_rows_select(int32_t m, int32_t T, int32_t nslab, const double *v
     if (T <= 32) RW(32);
     else if (T <= 64) RW(64);
     else if (T <= 128) RW(128);
-    else RW(256);
+    else if (T <= 256) RW(256);
+    else                 // an ensemble's columns: tiles of 256
+        hipLaunchKernelGGL((op_dual_rows_kernel<256, true>), dim3(nblk, (T + 255) / 256), dim3(256), 0, S_(stream), m, T,
+                           nslab, vsl, pnq, y, vlo, vhi, vfull, viol, partial, zero_out);
 #undef RW
     if (!defer_select) {
         const SelectArgs sa{m, T, nblk, kadd, partial, y, vfull, viol, vlo, vhi, seq,
@@ -2175,7 +2186,7 @@ static bool rows_big_lds(K kernel, size_t lds) {     // more than 64 KB of dynam
 }
 
 static int dual_shift_tree(int32_t m, int32_t T, const revs_tree_t *tree, const double *y, double *d_out, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= 256 && tree_ok_big(tree) && y && d_out, "revs_op_dual_evaluate_tree: bad argument");
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok_big(tree) && y && d_out, "revs_op_dual_evaluate_tree: bad argument");
     const TreeArgs tr{tree->n, (const unsigned long long *)tree->pack, tree->w};
     const size_t lds = tree_lds_bytes(tree->n);
     const TreeShape sh = tree_shape(tree->n);
@@ -2199,7 +2210,7 @@ extern "C" int revs_op_dual_rows_tree(int32_t m, int32_t T, const revs_tree_t *t
                                       double *viol, double *partial, double *zero_out, int64_t *cand_idx,
                                       int32_t *cand_cnt, double *cand_val, double *stats, double seq,
                                       int32_t with_select, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= 256 && tree_ok_big(tree) && pnq && y && vfull && viol &&
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok_big(tree) && pnq && y && vfull && viol &&
                  partial && vlo <= vhi && kadd >= 0 && zero_out != pnq &&
                  (!with_select || (cand_idx && cand_cnt && cand_val && stats)),
                  "revs_op_dual_rows_tree: bad argument (tree nodes <= %d, a multiple of 8; of 16 beyond 8192)", REVS_TREE_MAX);
@@ -2248,7 +2259,7 @@ extern "C" int revs_op_dual_tree_select_model_step(
         int32_t *cand_cnt, double *cand_val, double *stats, double seq, const double *R, double kappa,
         double delta, int32_t max_pivots, double *k_full, double *yhat, int32_t *info, double scale,
         double eps, double *y_trial, double *lin_out, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= 256 && tree_ok(tree) && pnq && y && vfull && viol &&
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok(tree) && pnq && y && vfull && viol &&
                  partial && cand_idx && cand_cnt && cand_val && stats && vlo <= vhi && kadd >= 0 && R && k_full &&
                  yhat && info && kappa > 0 && delta >= 0 && max_pivots > 0 && scale > 0.0 && y_trial &&
                  y_trial != y && lin_out, "revs_op_dual_tree_select_model_step: bad argument");

@@ -293,7 +293,7 @@ extern "C" int revs_plan_newton_solve(revs_plan_t *plan, revs_newton_state_t *st
     REVS_REQUIRE(o.k_slabs && d.cand_idx1 && d.cand_cnt1 && d.cand_val1 && d.stats && d.stats_host && d.stats1 && d.stats1_host && d.yhat && d.k_full &&
                  d.info && d.max_pivots > 0 && d.eps > 0, "revs_plan_newton_solve: revs_plan_set_newton / the chain's buffers are missing");
     const int T = d.T, A = REVS_DUAL_AMAX;
-    REVS_REQUIRE(T <= 256, "revs_plan_newton_solve: T = %d", T);
+    REVS_REQUIRE(T <= REVS_ENS_MAX_COLS, "revs_plan_newton_solve: T = %d", T);
     // the blocks the caller refers to still hold the evaluations it saw (every slot's record carries the evaluation's tag)
     for (int blk = 0; blk < 2; ++blk) {
         const double want = blk ? st->pre_tag : st->first_tag;

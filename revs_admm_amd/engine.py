@@ -1102,11 +1102,14 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if iteration is not None:
             self.iteration = int(iteration)
 
+    def _zero_state(self):
+        z = np.zeros((self.n, self.T), np.float32)
+        self.set_state(z, z, z, iteration=0)
+
     def reset(self):
         """Back to iteration 0 of lpsolver.py:244-246 (P_est = P_sch = G = 0, no multipliers, cold operator):
         the same engine -- buffers, plan, loaded code objects -- for another run of the same problem."""
-        z = np.zeros((self.n, self.T), np.float32)
-        self.set_state(z, z, z, iteration=0)
+        self._zero_state()
         for y in self.yd:
             y.zero_()
         if self.pdhg_dual is not None:

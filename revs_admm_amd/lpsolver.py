@@ -20,7 +20,7 @@ import numpy as np
 from . import _lib
 from .engine import AdmmEngine, OperatorOptions, pack_homes, residence_solve
 
-__all__ = ["compute_Rmat", "solve_ADMM", "solve_residence", "solve_residences",
+__all__ = ["compute_Rmat", "solve_ADMM", "solve_ADMM_many", "split_scenarios", "solve_residence", "solve_residences",
            "solve_central", "homes_to_arrays", "feeder_arrays", "feeder_of"]
 
 
@@ -139,6 +139,57 @@ def solve_ADMM(homes, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.
            {h: S[i].tolist() for i, h in enumerate(res)},
            {h: C[i].tolist() for i, h in enumerate(res)})
     return out + (eng,) if return_engine else out
+
+
+def split_scenarios(S: int, T: int):
+    """How solve_ADMM_many cuts S scenarios of T slots into ensembles -> [(first, end), ...]: as few ensembles as
+    hold them at REVS_ENS_MAX_COLS // T scenarios each, of sizes that differ by at most one."""
+    if S < 0 or not 1 <= T <= _lib.MAX_T:
+        raise ValueError(f"split_scenarios: S = {S}, T = {T} (T outside 1..{_lib.MAX_T})")
+    cap = _lib.ENS_MAX_COLS // T
+    parts = -(-S // cap)
+    bounds = [S * i // parts for i in range(parts + 1)] if parts else [0]
+    return list(zip(bounds[:-1], bounds[1:]))
+
+
+def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
+                    vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None):
+    """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
+    `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
+    DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
+    Every dict must hold every residence of the graph (KeyError) with LOADs of len(cost) slots (ValueError)."""
+    from .ensemble import AdmmEnsemble
+    res = [n for n in graph if graph.nodes[n]["label"] == "H"]
+    T = len(cost)
+    loads, recs = [], []
+    for s, homes in enumerate(homes_list):
+        missing = [h for h in res if h not in homes]
+        if missing:
+            raise KeyError(f"scenario {s}: homes lacks residence {missing[0]} of the network")
+        load, rec = homes_to_arrays(homes, res)
+        if load.shape != (len(res), T):
+            raise ValueError(f"scenario {s}: LOAD and cost must have the same number of slots")
+        loads.append(load)
+        recs.append(rec)
+    parts = split_scenarios(len(recs), T)
+    if not parts:
+        return []
+    R_res, feeder = feeder if feeder is not None else feeder_of(graph)
+    out = []
+    for a, b in parts:
+        shared = all(np.array_equal(loads[a], l) for l in loads[a + 1:b])
+        eng = AdmmEnsemble(np.asarray(cost, float), recs[a:b], loads[a] if shared else np.stack(loads[a:b]),
+                           np.arange(len(res)), R_res, kappa=kappa, vset=vset, vlow=vlow, vhigh=vhigh, mode=mode,
+                           device=device, op=operator, feeder=feeder)
+        d = eng.run(iter_max)
+        P_sch, S, C = eng.result()
+        for s in range(b - a):
+            out.append(({k + 1: {h: float(d[s, k, i]) for i, h in enumerate(res)} for k in range(iter_max)},
+                        {h: P_sch[s, i].tolist() for i, h in enumerate(res)},
+                        {h: S[s, i].tolist() for i, h in enumerate(res)},
+                        {h: C[s, i].tolist() for i, h in enumerate(res)}))
+        del eng
+    return out
 
 
 def solve_residences(tariff, homes, device="cuda:0"):

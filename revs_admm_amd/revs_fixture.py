@@ -14,7 +14,7 @@ import numpy as np
 
 from .extract import (GetCommunity, GetDistNet, GetHomeLoad, GetTariff, combine_result,
                       get_homes_ev_param)
-from .lpsolver import solve_ADMM, solve_central, solve_residences
+from .lpsolver import solve_ADMM, solve_ADMM_many, solve_central, solve_residences
 
 
 class REVS:
@@ -104,7 +104,7 @@ class REVS:
         return Pres, Pev, soc
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
-              methods=("distributed", "individual"), group_by="method", **opt):
+              methods=("distributed", "individual"), group_by="method", ensemble=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -120,7 +120,10 @@ class REVS:
         **opt: read_inputs' capacity, initial_soc, start_time, end_time; get_distributed_optimal's kappa,
         max_iterations, v0, vlow, vhigh, mode; the report's bands, vmin, vmax, arrays, report_vset (default 1.0, as
         drawing.compute_voltage) and line_rating ({line type: kVA}; default: the edges' `rating` attribute; without
-        either the loading records are empty).  The feeder's matrix and tree are formed once."""
+        either the loading records are empty).  The feeder's matrix and tree are formed once.
+        ensemble=True: the distributed scenarios of the grid are solved side by side (lpsolver.solve_ADMM_many, DESIGN.md
+        section 3.9) instead of one engine after the other -- the same schedules to the operator's tolerance, not bit
+        for bit."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -138,7 +141,7 @@ class REVS:
         edges = list(dist.edges)
         if opt.get("line_rating") is not None or (edges and all("rating" in dist.edges[e] for e in edges)):
             node_rating = line_nodes(dist, opt.get("line_rating"), parent, nonsub)[0]
-        labels, profiles = [], []
+        labels, profiles, deferred = [], [], []      # deferred: (position in profiles, homes) of the ensemble's scenarios
         for adoption in adoptions:
             for rating in ratings:
                 for seed in seeds:
@@ -148,12 +151,23 @@ class REVS:
                                                opt.get("initial_soc", 0.2), opt.get("start_time", 11),
                                                opt.get("end_time", 23))
                     for method in methods:
+                        labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
+                        if method == "distributed" and ensemble:
+                            deferred.append((len(profiles), homes))
+                            profiles.append(None)
+                            continue
                         if method == "distributed":
                             P_res = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[0]
                         else:
                             P_res = self.get_individual_optimal(tariff, homes)[0]
-                        labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
                         profiles.append(np.array([P_res[h] for h in res], np.float64))
+        if deferred:
+            sols = solve_ADMM_many([h for _, h in deferred], dist, tariff, None, kappa=opt.get("kappa", 5.0),
+                                   iter_max=opt.get("max_iterations", 15), vset=opt.get("v0", 1.03),
+                                   vlow=opt.get("vlow", 0.95), vhigh=opt.get("vhigh", 1.05),
+                                   mode=opt.get("mode", "binary"), device=self.device, feeder=feeder)
+            for (i, _), sol in zip(deferred, sols):
+                profiles[i] = np.array([sol[1][h] for h in res], np.float64)
         combos = [tuple(lab[k] for k in keys) for lab in labels]
         order = list(dict.fromkeys(combos))
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
