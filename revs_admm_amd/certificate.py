@@ -53,12 +53,12 @@ class CertificateMixin:
         of LOAD (this rank's: the LOAD term is additive over ranks), scratch."""
         if self._bd is not None:
             return self._bd
-        lib, M, T, n = self.lib, self.M, self.T, self.n
+        lib, M, T, n = self.lib, self.M, self.T, self.sweep_n
         f64 = dict(dtype=torch.float64, device=self.dev)
         bd = SimpleNamespace()
         counts = np.diff(self.node_ptr.cpu().numpy())
         bd.node_of = torch.from_numpy(np.repeat(np.arange(M, dtype=np.int32), counts)).to(self.dev)
-        bd.scratch = torch.zeros(max(1, int(lib.revs_dual_bound_scratch(n, T))), **f64)
+        bd.scratch = torch.zeros(max(1, int(lib.revs_dual_bound_scratch(n, self.sweep_T))), **f64)
         bd.out = torch.zeros(4, **f64)
         bd.lsum = torch.zeros(M, T, **f64)
         if n:
@@ -86,8 +86,8 @@ class CertificateMixin:
     def _bound_launch(self, d, y, scale, integral, p_node=None):
         """Enqueue one evaluation of L(scale y) (d = R y) into self._bd.out -- no synchronisation."""
         bd = self._bd
-        check(self.lib.revs_dual_bound(self.n, self.T, ptr(self.cost), ptr(self.homes), ptr(bd.node_of), self.M,
-                                       ptr(d), ptr(y), ptr(bd.lsum), float(scale), self.vlo, self.vhi, int(integral),
+        check(self.lib.revs_dual_bound(self.sweep_n, self.sweep_T, ptr(self.cost), ptr(self.homes), ptr(bd.node_of),
+                                       self.M, ptr(d), ptr(y), ptr(bd.lsum), float(scale), self.vlo, self.vhi, int(integral),
                                        ptr(bd.scratch), ptr(p_node), ptr(bd.out), self.stream), "revs_dual_bound")
 
     def _bound_eval(self, d, y, scale, integral, p_node=None):

@@ -321,24 +321,36 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self.node_counts = counts
         return load, node_of, Rn, node_ptr
 
+    def _sweep_layout(self, homes, load):
+        """The records and the load as the sweep reads them, in the engine's residence order: one record per row of load."""
+        return homes[self.perm], load[self.perm]
+
     def _init_residences(self, cost, homes, load, node_ptr, pdhg, pdhg_warm):
         """The residences' records and state on the device, and the options of their PDHG solves."""
-        n, T = self.n, self.T
+        homes, load = self._sweep_layout(homes, load)
+        # The engine has two shapes.  (n, T), with M, are the rows and columns of the state arrays P_est / P_est_new /
+        # P_sch / G and of everything node-side (M x T).  (sweep_n, sweep_T) is the residence-side launch shape: a call
+        # takes its extents from it if it passes any of homes, load, S, Csoc, diff, dsq, status, res_scratch, pdhg_dual;
+        # every other call takes them from n, T (with M) -- the node sums over node_ptr among them, which read a
+        # residence-side array as n rows of T columns.  Here the two are equal; an ensemble sweeps (n S, T / S) over the
+        # same memory (ensemble.py).  Set here and nowhere else.
+        self.sweep_n, self.sweep_T = load.shape
+        n, T, sn, sT = self.n, self.T, self.sweep_n, self.sweep_T
         f32 = dict(dtype=torch.float32, device=self.dev)
         self.cost = self._up(np.asarray(cost, np.float32))
-        self.homes = self._up(homes[self.perm].view(np.uint8).reshape(n, HOME_DTYPE.itemsize))
-        self.load = self._up(load[self.perm])
+        self.homes = self._up(homes.view(np.uint8).reshape(sn, HOME_DTYPE.itemsize))
+        self.load = self._up(load)
         self.node_ptr = self._up(node_ptr)
         self.P_est = torch.zeros(n, T, **f32)          # lpsolver.py:244
         self.P_est_new = torch.zeros(n, T, **f32)
         self.P_sch = torch.zeros(n, T, **f32)          # lpsolver.py:245
         self.G = torch.zeros(n, T, **f32)              # lpsolver.py:246
-        self.S = torch.zeros(n, T, **f32)
-        self.Csoc = torch.zeros(n, T + 1, **f32)
-        self.diff = torch.zeros(n, **f32)
-        self.status = torch.zeros(n, dtype=torch.int32, device=self.dev)
-        self.dsq = torch.zeros(n, **f32)
-        self.res_scratch = torch.zeros(3 * int(self.lib.revs_residual_num_chunks(n)),
+        self.S = torch.zeros(sn, sT, **f32)
+        self.Csoc = torch.zeros(sn, sT + 1, **f32)
+        self.diff = torch.zeros(sn, **f32)
+        self.status = torch.zeros(sn, dtype=torch.int32, device=self.dev)
+        self.dsq = torch.zeros(sn, **f32)
+        self.res_scratch = torch.zeros(3 * int(self.lib.revs_residual_num_chunks(sn)),
                                        dtype=torch.float64, device=self.dev)
         self.resid = torch.zeros(4, **f32)
         # PDHG multipliers carried across ADMM iterations (warm start), relaxed PDHG only
@@ -350,7 +362,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
             for k, v in pdhg.items():
                 setattr(self.pdhg, k, v)
         if self._pdhg_warm:      # one scalar per home, or one per SOC row with full_rows
-            self.pdhg_dual = torch.zeros((n, T) if self.pdhg.full_rows else (n,), **f32)
+            self.pdhg_dual = torch.zeros((sn, sT) if self.pdhg.full_rows else (sn,), **f32)
 
     def _init_newton(self, Rn):
         """The operator's state: the ADMM forms' (solver="admm") and the dual Newton path's buffers."""
@@ -453,7 +465,8 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                                                 self.op.newton_delta, self.op.newton_pivots,
                                                 ptr(self.k_full), ptr(self.yhat), self.info_dev,
                                                 self.stream), "revs_op_dual_model_small")
-        self._gemm1(self.R64, self.yd[0], self.d_sl)
+        if self.T <= _lib.MAX_T:         # (the dense product holds no more columns, and is never used beyond them)
+            self._gemm1(self.R64, self.yd[0], self.d_sl)
         torch.cuda.synchronize(self.dev)
 
     def _init_plan(self, node_of, native):
@@ -831,7 +844,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self._fold_resume = False
         ps_out, g_out = (self.P_sch_alt, self.G_alt) if to_alt else (self.P_sch, self.G)
         check(self.lib.revs_agent_step_out(
-            self.n, self.T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(self.P_est),
+            self.sweep_n, self.sweep_T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(self.P_est),
             ptr(self.P_est_new), ptr(self.P_sch), ptr(self.G), ptr(ps_out), ptr(g_out),
             ptr(self.S) if write_sc else None, ptr(self.Csoc) if write_sc else None,
             ptr(self.diff), ptr(self.dsq), ptr(self.status), ptr(self.pdhg_dual),
@@ -843,7 +856,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         (|P_est - P_sch|_2, kappa |dP_sch|_2, max_h diff[h], converged) where converged
         means max_h diff[h] <= eps -- diff (lpsolver.py:284) is the reference's only
         convergence measure."""
-        check(self.lib.revs_residual_finalize(ptr(self.diff), ptr(self.dsq), self.n, self.T,
+        check(self.lib.revs_residual_finalize(ptr(self.diff), ptr(self.dsq), self.sweep_n, self.sweep_T,
                                               self.kappa, eps, ptr(self.res_scratch),
                                               ptr(self.resid), self.stream),
               "revs_residual_finalize")
@@ -914,21 +927,21 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         launch_only / deferred (one GPU, no group): the reduction of the status words is enqueued now and read by a
         second call with deferred=True -- run() puts the next iteration between the two, so that the report that
         follows the first iteration (as the reference's does) costs the host no wait for that iteration's sweep."""
-        if deferred and not (self.n and self._flag_dev is not None and self.group is None):
+        if deferred and not (self.sweep_n and self._flag_dev is not None and self.group is None):
             return
-        if launch_only and not (self.n and self._flag_dev is not None and self.group is None):
+        if launch_only and not (self.sweep_n and self._flag_dev is not None and self.group is None):
             launch_only = False
         if self._plan is not None and not deferred:
             f = int(self.lib.revs_plan_status_flags(self._plan, 1))
         else:
             f = 0
-        if self.n and self._flag_dev is not None:
+        if self.sweep_n and self._flag_dev is not None:
             # bits 0-2 of the last sweep's per-residence status words, OR-ed on the device into a pinned word: one
             # small launch and a stream synchronise (as six torch reductions and a read-back this check was 0.3 ms
             # of host time in front of the second iteration of every run -- tools/transient_hostgaps.py, r05)
             if not deferred:
                 self._flag_np[0] = 0
-                check(self.lib.revs_status_or(self.n, ptr(self.status), self._flag_dev, self.stream), "revs_status_or")
+                check(self.lib.revs_status_or(self.sweep_n, ptr(self.status), self._flag_dev, self.stream), "revs_status_or")
                 if launch_only:          # (read by check_status(deferred=True) behind the next iteration's own wait)
                     self._flag_np[1] = f
                     return
@@ -936,7 +949,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                 f |= int(self._flag_np[1])
             torch.cuda.current_stream(self.dev).synchronize()
             f |= int(self._flag_np[0]) & 7
-        elif self.n:    # (host stand-in of the kernels: one read-back)
+        elif self.sweep_n:    # (host stand-in of the kernels: one read-back)
             st = self.status
             f |= sum(int(v) for v in torch.stack([(st & b).max() for b in (1, 2, 4)]).cpu().tolist())
         if self.group is not None:
@@ -981,7 +994,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         loop's records are global already: each rank's partial maxima travel with the all-reduce).
         run(eps=) decides on it when to stop, and a rank that stopped on its own residences' maximum
         alone would leave the others waiting in their next all-reduce."""
-        mx = torch.tensor([float(self.diff.max().item()) if self.n else 0.0], dtype=torch.float64,
+        mx = torch.tensor([float(self.diff.max().item()) if self.sweep_n else 0.0], dtype=torch.float64,
                           device=self.dev)
         if self.group is not None:
             self._allreduce(mx, torch.distributed.ReduceOp.MAX)
@@ -1047,16 +1060,16 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                     if eps is not None and self.iteration not in self.max_diff:
                         # (max_h diff of an iteration outside the streaming loop: reduced on the device now, fetched with
                         # the others' when the stopping rule is next evaluated -- no host wait per iteration)
-                        if self._dmx_dev is not None and self.group is None and self.n:
+                        if self._dmx_dev is not None and self.group is None and self.sweep_n:
                             # (one GPU: the residual kernels write their record into a slot of pinned memory -- no
                             # torch reduction per iteration, no stack-and-copy when the records are wanted)
                             slot = len(pending)
-                            check(self.lib.revs_residual_finalize(ptr(self.diff), ptr(self.dsq), self.n, self.T, self.kappa,
+                            check(self.lib.revs_residual_finalize(ptr(self.diff), ptr(self.dsq), self.sweep_n, self.sweep_T, self.kappa,
                                                                   eps, ptr(self.res_scratch), self._dmx_dev + 16 * slot,
                                                                   self.stream), "revs_residual_finalize")
                             pending.append((self.iteration, slot))
                         else:
-                            pending.append((self.iteration, self.diff.max() if self.n else torch.zeros((), dtype=torch.float32, device=self.dev)))
+                            pending.append((self.iteration, self.diff.max() if self.sweep_n else torch.zeros((), dtype=torch.float32, device=self.dev)))
                 k += done
                 r += done
                 if status_pending and k >= 2:

@@ -8,21 +8,21 @@ Their state is kept as float[n][S][T] and read two ways, without a copy:
   the residences' view   n S residences x T slots, one 32-byte record per (residence, scenario): the sweep
                          (revs_agent_step_out), the residuals and the status reduction as they are, with n' = n S.
 
-`AdmmEnsemble` is an `AdmmEngine` built over the operator's view whose residence-side calls run in the residences'
-view.  Its options keep `step()` on the general branch -- `operator_solve()` then `agent_step()` -- because the
-steady-state and chained launches carry one T for both sides.
+`AdmmEngine` names both shapes: (n, T) for the state arrays and everything node-side, (sweep_n, sweep_T) for the calls
+that pass residence-side buffers (engine.py, _init_residences).  `AdmmEnsemble` is an `AdmmEngine` with (n, T) = (n, S T)
+and a sweep shape of (n S, T): all it adds to the construction is how records and load are laid out for the sweep.  Its
+options keep `step()` on the general branch -- `operator_solve()` then `agent_step()` -- because the steady-state and
+chained launches carry one T for both sides.
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 import dataclasses
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import HOME_DTYPE, PDHG
+from ._lib import HOME_DTYPE
 from .engine import AdmmEngine, OperatorOptions, _on_current_stream
 
 # the ADMM forms of the operator QP (operator_admm.py) multiply by the dense factors of R: the dense products' column limit
@@ -80,92 +80,27 @@ class AdmmEnsemble(AdmmEngine):
         # (... and the Newton solve as the plan's native call: the Python loop's evaluations may take the dense products)
         o = dataclasses.replace(o, speculate=False, chain=False, fuse_home_pass=False, stream_block=1, preallocate=False,
                                 native_plan=True, native_newton=True)
-        self._in_res_view = False
-        self._warming_up = False         # set only inside _warm_up: the one dense product that may be skipped
-        self._ens_load = load
-        super().__init__(cost, homes_list, None, node_of, Rn, kappa=kappa, vset=vset, vlow=vlow, vhigh=vhigh, mode=mode,
-                         device=device, pdhg=pdhg, op=o, pdhg_warm=pdhg_warm, feeder=feeder, _kernels=_kernels)
-        del self._ens_load
+        # (the load goes in as the operator sees it, (n, S T): its shape is the engine's (n, T))
+        super().__init__(cost, homes_list, load.reshape(self.n_res, -1), node_of, Rn, kappa=kappa, vset=vset, vlow=vlow,
+                         vhigh=vhigh, mode=mode, device=device, pdhg=pdhg, op=o, pdhg_warm=pdhg_warm, feeder=feeder,
+                         _kernels=_kernels)
         if self._tree is None and self.T > _lib.MAX_T and _kernels is None:
             raise ValueError(f"AdmmEnsemble: {self.T} columns need the feeder as a tree (feeder=): the dense products "
                              f"R p and R^T y hold {_lib.MAX_T} columns")
 
     # ---------------------------------------------------------------- the two views
-    @contextlib.contextmanager
-    def _residences(self):
-        """Inside: self.n, self.T are the residences' view (n S, T) -- what the sweep, the residuals and the status
-        reduction of AdmmEngine are called with.  Outside: the operator's view (n, S T).
-        The invariant this rests on: the ONLY inherited methods that read self.n / self.T for residence-side buffers
-        (homes, load, S, Csoc, diff, dsq, status, res_scratch, pdhg_dual) are agent_step, residuals and check_status,
-        and each is overridden below to run inside this context; every fast path that would launch a sweep on its own
-        (speculation, chain, streaming, preallocated pools) is switched off by the constructor's options.  A new
-        inherited method that touches those buffers must be overridden the same way."""
-        if self._in_res_view:
-            yield
-            return
-        n, T = self.n, self.T
-        self.n, self.T, self._in_res_view = self.n_res * self.S_count, self.T_slot, True
-        try:
-            yield
-        finally:
-            self.n, self.T, self._in_res_view = n, T, False
-
     def _by_scenario(self, t, width):
         """A state tensor as (n, S, width)."""
         return t.view(self.n_res, self.S_count, width)
 
     # ---------------------------------------------------------------- construction stages
-    def _init_problem(self, homes_list, load, node_of, Rn, kappa, vset, vlow, vhigh, mode, op, group, node_counts, native):
+    def _init_problem(self, homes_list, *args):
         # (records without an EV everywhere: the residences are sorted by node only -- the scenarios disagree on who owns one)
-        n, cols = self.n_res, self.S_count * self.T_slot
-        _, node_of, Rn, node_ptr = super()._init_problem(np.zeros(n, HOME_DTYPE), np.zeros((n, cols), np.float32), node_of, Rn,
-                                                         kappa, vset, vlow, vhigh, mode, op, group, node_counts, native)
-        return self._ens_load, node_of, Rn, node_ptr
+        return super()._init_problem(np.zeros(self.n_res, HOME_DTYPE), *args)
 
-    def _init_residences(self, cost, homes_list, load, node_ptr, pdhg, pdhg_warm):
-        """The residences' view: records [n][S], load and outputs (n S, T), one diff / status word per (residence, scenario);
-        the state itself (n, S T): both views of the same memory."""
-        n, S, T = self.n_res, self.S_count, self.T_slot
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        self.cost = self._up(np.asarray(cost, np.float32))
-        rec = np.ascontiguousarray(np.stack(homes_list, axis=1)[self.perm])            # (n, S)
-        self.homes = self._up(rec.view(np.uint8).reshape(n * S, HOME_DTYPE.itemsize))
-        self.load = self._up(np.ascontiguousarray(load[self.perm]).reshape(n * S, T))
-        self.node_ptr = self._up(node_ptr)
-        self.P_est = torch.zeros(n, S * T, **f32)
-        self.P_est_new = torch.zeros(n, S * T, **f32)
-        self.P_sch = torch.zeros(n, S * T, **f32)
-        self.G = torch.zeros(n, S * T, **f32)
-        self.S = torch.zeros(n * S, T, **f32)
-        self.Csoc = torch.zeros(n * S, T + 1, **f32)
-        self.diff = torch.zeros(n * S, **f32)
-        self.status = torch.zeros(n * S, dtype=torch.int32, device=self.dev)
-        self.dsq = torch.zeros(n * S, **f32)
-        self.res_scratch = torch.zeros(3 * int(self.lib.revs_residual_num_chunks(n * S)), dtype=torch.float64, device=self.dev)
-        self.resid = torch.zeros(4, **f32)
-        self._pdhg_warm = bool(pdhg_warm) and self.mode == _lib.MODE_RELAXED_PDHG
-        self.pdhg_dual = None
-        self.pdhg = PDHG()
-        self.lib.revs_pdhg_defaults(C.byref(self.pdhg))
-        if pdhg:
-            for k, v in pdhg.items():
-                setattr(self.pdhg, k, v)
-        if self._pdhg_warm:
-            self.pdhg_dual = torch.zeros((n * S, T) if self.pdhg.full_rows else (n * S,), **f32)
-
-    def _warm_up(self, native):
-        self._warming_up = True
-        try:
-            super()._warm_up(native)
-        finally:
-            self._warming_up = False
-
-    def _gemm1(self, At, B, Cslabs):
-        # the constructor's warm-up touches the dense product, which does not hold more than 192 columns and is never used
-        # beyond them; any other dense product beyond them goes to the library, which refuses it
-        if self._warming_up and self.T > _lib.MAX_T:
-            return
-        super()._gemm1(At, B, Cslabs)
+    def _sweep_layout(self, homes_list, load):
+        """Records [n][S] and load (n S, T): one sweep row per (residence, scenario)."""
+        return np.stack(homes_list, axis=1)[self.perm].reshape(-1), load[self.perm].reshape(-1, self.T_slot)
 
     # ---------------------------------------------------------------- operator side
     def _column_name(self, col):
@@ -206,19 +141,6 @@ class AdmmEnsemble(AdmmEngine):
         return self.yd[0].view(self.M, self.S_count, self.T_slot)[:, s, :].cpu().numpy()
 
     # ---------------------------------------------------------------- residence side
-    def agent_step(self, write_sc=True, to_alt=False):
-        with self._residences():
-            super().agent_step(write_sc, to_alt)
-
-    def residuals(self, eps=1e-4):
-        """As AdmmEngine.residuals, over every scenario's residences."""
-        with self._residences():
-            return super().residuals(eps)
-
-    def check_status(self, launch_only=False, deferred=False):
-        with self._residences():
-            super().check_status(launch_only, deferred)
-
     def scenario_max_diff(self):
         """max_h diff[h] of the iteration just finished, per scenario (S,)."""
         return self.diff.view(self.n_res, self.S_count).amax(0).cpu().numpy().astype(np.float64)

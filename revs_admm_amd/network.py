@@ -167,7 +167,7 @@ class NetworkMixin:
             if prof.dtype != torch.float32 or tuple(prof.shape) != (self.n, self.T) or not prof.is_contiguous():
                 raise ValueError(f"network_report: profile must be a contiguous float32 ({self.n}, {self.T}) array")
         node_g = torch.zeros(self.M, self.T, dtype=torch.float64, device=self.dev)
-        if self.n:
+        if self.sweep_n:     # (node sums over node_ptr: load and profile read as n rows of T columns)
             check(self.lib.revs_net_node_sums(self.M, self.T, ptr(self.node_ptr), ptr(load), ptr(prof), ptr(node_g),
                                               self.stream), "revs_net_node_sums")
         self._allreduce(node_g)

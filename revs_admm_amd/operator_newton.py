@@ -426,7 +426,7 @@ class DualNewtonMixin:
         self._dual_phase(2 | 4, ytrial, True, 1)  # product and rows; selection: in the sweep
         self._chain_seq -= 1.0
         check(lib.revs_agent_step_select(
-            self.n, T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(self.P_est),
+            self.sweep_n, self.sweep_T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(self.P_est),
             ptr(self.P_est_new), ptr(self.P_sch), ptr(self.G), ptr(self.P_sch_alt), ptr(self.G_alt),
             ptr(self.S) if write_sc else None, ptr(self.Csoc) if write_sc else None,
             ptr(self.diff), ptr(self.dsq), ptr(self.status), ptr(self.pdhg_dual), self.kappa,

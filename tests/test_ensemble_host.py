@@ -203,6 +203,69 @@ def test_the_driver_on_the_host_stand_in_follows_the_oracle():
     assert np.array_equal(e.run(iters), d) and all(np.array_equal(a, b) for a, b in zip(e.result(), (P, Sc, Cs)))
 
 
+class _Recorder:
+    """FakeKernels behind a note of every call: (entry, its row count -- the argument named n or m -- and its T, None
+    where the entry has none, (engine.n, engine.T) at the time of the call)."""
+
+    def __init__(self, kernels):
+        self._kernels, self.engine, self.calls = kernels, None, []
+
+    def __getattr__(self, name):
+        import inspect
+        fn = getattr(self._kernels, name)
+        sig = inspect.signature(fn)
+
+        def entry(*a, **k):
+            b = sig.bind(*a, **k).arguments
+            e = self.engine
+            self.calls.append((name, (b.get("n", b.get("m")), b.get("T")), (getattr(e, "n", None), getattr(e, "T", None))))
+            return fn(*a, **k)
+        return entry
+
+
+def test_every_call_carries_its_own_shape_and_nothing_swaps():
+    """The engine's two named shapes (engine.py, _init_residences) on the host stand-in: the calls that pass residence-side
+    buffers carry the sweep shape, the operator's and the node sums' calls (M, T), and (e.n, e.T) is the same at every
+    call -- for an ensemble of S = 3 and for a plain engine on its scenario 0."""
+    from fake_kernels import FakeKernels
+    from helpers import f32
+    from revs_admm_amd.engine import AdmmEngine, pack_homes
+    from revs_admm_amd.ensemble import AdmmEnsemble
+    from revs_admm_amd.synthetic import make_workload
+    n, T, S, M = 150, 24, 3, 15
+    w = make_workload(n, T, n_nodes=M, seed=11, binary_feasible=False, stress=1.4)
+    w.load, w.cost = f32(w.load), f32(w.cost)
+    rng = np.random.default_rng(5)
+    homes = [pack_homes(rng.random(n) < share, 4.8, 20.0, 0.2, 11, 23) for share in (0.3, 0.5, 0.7)]
+    kw = dict(kappa=w.kappa, vset=w.vset, vlow=w.vlow, vhigh=w.vhigh, mode="relaxed_exact", device="cpu")
+
+    def recorded(make, sweep, state):
+        rec = _Recorder(FakeKernels())
+        e = rec.engine = make(rec)
+        assert (e.sweep_n, e.sweep_T) == sweep and (e.n, e.T) == state
+        e.run(3)
+        e.residuals()
+        e.result()
+        e.reset()
+        e.run(2)
+        assert (e.sweep_n, e.sweep_T) == sweep and (e.n, e.T) == state
+        by = lambda *prefixes: [c for c in rec.calls if c[0].startswith(prefixes)]
+        sweeps, finals = by("revs_agent_step"), by("revs_residual_finalize")
+        assert len(sweeps) >= 5 and len(by("revs_agent_step_out")) >= 1 and len(finals) >= 1
+        assert all(c[1] == sweep for c in sweeps + finals)
+        assert [c[1] for c in by("revs_residual_num_chunks")] == [(sweep[0], None)]
+        node_side = by("revs_op_dual_", "revs_aggregate_")
+        assert by("revs_op_dual_") and all(c[1][0] in (None, M) and c[1][1] in (None, state[1]) and c[1] != (None, None)
+                                           for c in node_side)
+        # every call of the constructed engine, the sweeps among them: nothing swaps n and T
+        after = [c for c in rec.calls if c[2] != (None, None)]
+        assert all(c in after for c in sweeps + finals) and all(c[2] == state for c in after)
+        return rec
+
+    recorded(lambda k: AdmmEnsemble(w.cost, homes, w.load, w.node_of, w.Rn, _kernels=k, **kw), (n * S, T), (n, S * T))
+    recorded(lambda k: AdmmEngine(w.cost, homes[0], w.load, w.node_of, w.Rn, _kernels=k, **kw), (n, T), (n, T))
+
+
 @pytest.mark.parametrize("S", [10, 12])
 def test_a_newton_failure_beyond_the_admm_forms_columns_is_a_named_error(S):
     """240 and 288 columns (S = 10, 12 at T = 24), the Newton path made to give up (newton_max = 0) once rows bind: the
