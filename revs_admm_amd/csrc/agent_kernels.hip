@@ -1183,55 +1183,36 @@ static Shape pick_shape(int T, int lanes = 0) {
     return {64, 3};
 }
 
+// f(integral_constant<int, MODE>, bool_constant<FULL_ROWS>) for the sweep's runtime mode (as for_tree_shape,
+// tree_body.h); full_rows is a form of the PDHG mode only
+template <typename F>
+static void for_mode(int mode, bool full_rows, F &&f) {
+    switch (mode) {
+        case REVS_MODE_BINARY: f(std::integral_constant<int, REVS_MODE_BINARY>{}, std::false_type{}); break;
+        case REVS_MODE_RELAXED_PDHG:
+            if (full_rows) f(std::integral_constant<int, REVS_MODE_RELAXED_PDHG>{}, std::true_type{});
+            else f(std::integral_constant<int, REVS_MODE_RELAXED_PDHG>{}, std::false_type{});
+            break;
+        default: f(std::integral_constant<int, REVS_MODE_RELAXED_EXACT>{}, std::false_type{}); break;
+    }
+}
+
 template <int LPA, int SPL>
 static void launch_agent(const AgentArgs &a, int mode, dim3 grid, hipStream_t s) {
     // dynamic LDS: only a launch whose first workgroups run the tree form of R p needs any
     const size_t lds = a.tree.n > 0 ? tree_lds_bytes(a.tree.n) : 0;
-    if (a.sh_a) {        // the folded chain's sweep
-        switch (mode) {
-            case REVS_MODE_BINARY:
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_BINARY, false, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-            case REVS_MODE_RELAXED_PDHG:
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_PDHG, false, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-            default:
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_EXACT, false, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-        }
-        return;
-    }
-    if (a.kin > 1) {     // several iterations per launch (no verdict workgroups in these launches)
-        switch (mode) {
-            case REVS_MODE_BINARY:
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_BINARY, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-            case REVS_MODE_RELAXED_PDHG:
-                if (a.pd.full_rows)
-                    hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_PDHG, true, true>), grid, dim3(kBlock), 0, s, a);
-                else
-                    hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_PDHG, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-            default:
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_EXACT, false, true>), grid, dim3(kBlock), 0, s, a);
-                break;
-        }
-        return;
-    }
-    switch (mode) {
-        case REVS_MODE_BINARY:
-            hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_BINARY>), grid, dim3(kBlock), lds, s, a);
-            break;
-        case REVS_MODE_RELAXED_PDHG:
-            if (a.pd.full_rows)
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_PDHG, true>), grid, dim3(kBlock), lds, s, a);
-            else
-                hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_PDHG, false>), grid, dim3(kBlock), lds, s, a);
-            break;
-        default:
-            hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, REVS_MODE_RELAXED_EXACT>), grid, dim3(kBlock), lds, s, a);
-            break;
-    }
+    if (a.sh_a)          // the folded chain's sweep (it has no full_rows form: agent_step_impl refuses the request)
+        for_mode(mode, false, [&](auto md, auto) {
+            hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, md(), false, false, true>), grid, dim3(kBlock), 0, s, a);
+        });
+    else if (a.kin > 1)  // several iterations per launch (no verdict workgroups in these launches)
+        for_mode(mode, a.pd.full_rows != 0, [&](auto md, auto fr) {
+            hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, md(), fr(), true>), grid, dim3(kBlock), 0, s, a);
+        });
+    else
+        for_mode(mode, a.pd.full_rows != 0, [&](auto md, auto fr) {
+            hipLaunchKernelGGL((agent_step_kernel<LPA, SPL, md(), fr()>), grid, dim3(kBlock), lds, s, a);
+        });
 }
 
 #define REVS_FOR_SHAPE(sh, CALL)                                   \
@@ -1456,44 +1437,37 @@ extern "C" int32_t revs_residual_num_chunks(int64_t n_homes) {
     return (int32_t)(c < 256 ? c : 256);
 }
 
-static int agent_step_impl(int64_t n_homes, int32_t T, const float *cost,
-                           const revs_home_t *homes, const float *load,
-                           const float *p_est_old, const float *p_est_new,
-                           const float *p_sch, const float *gamma, float *p_sch_out,
-                           float *gamma_out, float *s_out, float *c_out, float *diff,
-                           float *dsq, int32_t *status, float *pdhg_dual,
-                           float kappa, int32_t mode, const revs_pdhg_t *pdhg_host,
-                           const SelectArgs *sel, const int32_t *node_of, double *p_next,
-                           float *pe2_out, void *stream, const StreamExtra *sx = nullptr,
-                           unsigned int *flags = nullptr, const ChainFold *cf = nullptr) {
-    REVS_REQUIRE(n_homes > 0, "revs_agent_step: n_homes=%lld", (long long)n_homes);
+static int agent_step_impl(const SweepCall &c, const SelectArgs *sel = nullptr, const StreamExtra *sx = nullptr,
+                           const ChainFold *cf = nullptr) {
+    const int32_t T = c.T;
+    REVS_REQUIRE(c.n_homes > 0, "revs_agent_step: n_homes=%lld", (long long)c.n_homes);
     REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_agent_step: T=%d outside 1..%d", T, REVS_MAX_T);
-    REVS_REQUIRE(cost && homes && load && p_est_old && p_sch && gamma && p_sch_out &&
-                 gamma_out && diff && dsq, "revs_agent_step: null pointer argument");
-    REVS_REQUIRE(mode >= 0 && mode <= 2, "revs_agent_step: mode=%d", mode);
-    REVS_REQUIRE(kappa > 0.f, "revs_agent_step: kappa=%g must be positive", (double)kappa);
+    REVS_REQUIRE(c.cost && c.homes && c.load && c.p_est_old && c.p_sch && c.gamma && c.p_sch_out &&
+                 c.gamma_out && c.diff && c.dsq, "revs_agent_step: null pointer argument");
+    REVS_REQUIRE(c.mode >= 0 && c.mode <= 2, "revs_agent_step: mode=%d", c.mode);
+    REVS_REQUIRE(c.kappa > 0.f, "revs_agent_step: kappa=%g must be positive", (double)c.kappa);
     AgentArgs a;
-    a.n = n_homes; a.T = T; a.cost = cost; a.homes = homes; a.load = load;
-    a.pe_old = p_est_old; a.pe_new = p_est_new;
-    a.ps = const_cast<float *>(p_sch); a.gam = const_cast<float *>(gamma);
-    a.ps_out = p_sch_out; a.gam_out = gamma_out;
-    a.s_out = s_out; a.c_out = c_out; a.diff = diff; a.dsq = dsq;
-    a.status = status; a.y_state = pdhg_dual; a.kappa = kappa;
+    a.n = c.n_homes; a.T = T; a.cost = c.cost; a.homes = c.homes; a.load = c.load;
+    a.pe_old = c.p_est_old; a.pe_new = c.p_est_new;
+    a.ps = const_cast<float *>(c.p_sch); a.gam = const_cast<float *>(c.gamma);
+    a.ps_out = c.p_sch_out; a.gam_out = c.gamma_out;
+    a.s_out = c.s_out; a.c_out = c.c_out; a.diff = c.diff; a.dsq = c.dsq;
+    a.status = c.status; a.y_state = c.pdhg_dual; a.kappa = c.kappa;
     a.nsel = 0;
     a.sel = SelectArgs{};
     if (sel) { a.nsel = sel->T; a.sel = *sel; }
-    a.node_of = node_of; a.p_next = p_next; a.pe2_out = pe2_out;
-    REVS_REQUIRE(!p_next || (node_of && (pe2_out || (sx && !sx->verdict))), "revs_agent_step: node_of / pe2_out missing");
+    a.node_of = c.node_of; a.p_next = c.p_next; a.pe2_out = c.pe2_out;
+    REVS_REQUIRE(!c.p_next || (c.node_of && (c.pe2_out || (sx && !sx->verdict))), "revs_agent_step: node_of / pe2_out missing");
     a.ctl = nullptr; a.seq = 0; a.base_seq = 0; a.tree = TreeArgs{}; a.p_in = nullptr; a.p_zero = nullptr;
-    a.vtol = 0.0; a.rec = nullptr; a.flags = flags; a.m = 0;
-    a.kin = 1; a.pe_out = nullptr; a.y_out = pdhg_dual; a.slice_stride = 0; a.diff_stride = 0; a.dmax_out = nullptr;
+    a.vtol = 0.0; a.rec = nullptr; a.flags = c.flags; a.m = 0;
+    a.kin = 1; a.pe_out = nullptr; a.y_out = c.pdhg_dual; a.slice_stride = 0; a.diff_stride = 0; a.dmax_out = nullptr;
     a.sh_a = nullptr; a.sh_b = nullptr; a.sh_m = 0; a.sh_kappa = 0.0;
     a.fold_a = nullptr; a.fold_b = nullptr;
     a.wg_order = nullptr;
     if (cf) {
         REVS_REQUIRE(cf->sh_a && cf->sh_b && cf->m > 0 && cf->kappa > 0 && cf->fold_a && cf->fold_b &&
-                     cf->fold_a != cf->fold_b && cf->pe_out && node_of && !p_est_new && !p_next && !sel && !sx &&
-                     !(pdhg_host && pdhg_host->full_rows),
+                     cf->fold_a != cf->fold_b && cf->pe_out && c.node_of && !c.p_est_new && !c.p_next && !sel && !sx &&
+                     !(c.pdhg && c.pdhg->full_rows),
                      "revs_agent_step: bad argument of the folded chain's sweep");
         a.sh_a = cf->sh_a; a.sh_b = cf->sh_b; a.sh_m = cf->m; a.sh_kappa = cf->kappa;
         a.fold_a = cf->fold_a; a.fold_b = cf->fold_b; a.pe_out = cf->pe_out;
@@ -1503,10 +1477,10 @@ static int agent_step_impl(int64_t n_homes, int32_t T, const float *cost,
     if (sx && !sx->verdict) {         // judged by blocks (stream_block_verdict): silencing only
         REVS_REQUIRE(!sel, "revs_agent_step: bad streaming argument");      // (ctl == NULL: never silenced)
         a.ctl = sx->ctl; a.seq = sx->seq; a.base_seq = sx->base_seq; a.flags = sx->flags;
-        const int lanes_ = pdhg_host ? pdhg_host->lanes : 0;
+        const int lanes_ = c.pdhg ? c.pdhg->lanes : 0;
         REVS_REQUIRE(sx->kin >= 1 && sx->kin <= revs_agent_max_inner(T, lanes_) && sx->slice_stride >= 0 && sx->diff_stride >= 0,
                      "revs_agent_step: kin=%d outside 1..%d (T = %d)", sx->kin, revs_agent_max_inner(T, lanes_), T);
-        REVS_REQUIRE(sx->kin == 1 || (!p_est_new && p_next && sx->pe_out && !s_out && !c_out &&
+        REVS_REQUIRE(sx->kin == 1 || (!c.p_est_new && c.p_next && sx->pe_out && !c.s_out && !c.c_out &&
                                       sx->slice_stride >= (int64_t)0),
                      "revs_agent_step: several iterations per launch need the recomputed estimate, node sums "
                      "and pe_out, and write no S / C");
@@ -1515,8 +1489,7 @@ static int agent_step_impl(int64_t n_homes, int32_t T, const float *cost,
         if (sx->y_out) a.y_out = sx->y_out;
         a.wg_order = sx->wg_order;          // (as many entries as this launch has workgroups: plan_wg_order)
     } else if (sx) {
-        REVS_REQUIRE(sx->ctl && sx->rec && sx->p_in && sx->tree.n > 0 && sx->tree.n <= REVS_TREE_SWEEP_MAX && sx->tree.n % 8 == 0 &&
-                     sx->tree.pack && sx->tree.w &&
+        REVS_REQUIRE(sx->ctl && sx->rec && sx->p_in && tree_sweep_ok(sx->tree) &&
                      sx->m > 0 && sx->vlo <= sx->vhi && sx->vtol >= 0.0 && !sel,
                      "revs_agent_step: bad streaming argument");
         a.ctl = sx->ctl; a.seq = sx->seq; a.base_seq = sx->base_seq; a.tree = sx->tree; a.p_in = sx->p_in; a.p_zero = sx->p_zero;
@@ -1524,15 +1497,15 @@ static int agent_step_impl(int64_t n_homes, int32_t T, const float *cost,
         a.nsel = T;
         a.sel.vlo = sx->vlo; a.sel.vhi = sx->vhi;
     }
-    if (pdhg_host) a.pd = *pdhg_host; else revs_pdhg_defaults(&a.pd);
+    if (c.pdhg) a.pd = *c.pdhg; else revs_pdhg_defaults(&a.pd);
     REVS_REQUIRE(a.pd.max_iter > 0 && a.pd.check > 0 && a.pd.tau_scale >= 0 && a.pd.sigma_scale >= 0,
                  "revs_agent_step: bad PDHG parameters");
     const Shape sh = pick_shape(T, a.pd.lanes);
-    const int64_t nblk = agent_num_blocks(n_homes, T, a.pd.lanes);
+    const int64_t nblk = agent_num_blocks(c.n_homes, T, a.pd.lanes);
     REVS_REQUIRE(nblk < (1ll << 31), "revs_agent_step: too many homes for one launch");
     const dim3 grid((unsigned)(nblk + a.nsel));
-    hipStream_t s = (hipStream_t)stream;
-#define CALL(LPA, SPL) launch_agent<LPA, SPL>(a, mode, grid, s)
+    hipStream_t s = (hipStream_t)c.stream;
+#define CALL(LPA, SPL) launch_agent<LPA, SPL>(a, c.mode, grid, s)
     REVS_FOR_SHAPE(sh, CALL);
 #undef CALL
     REVS_CHECK_LAUNCH("revs_agent_step");
@@ -1545,26 +1518,8 @@ int64_t agent_homes_per_block(int32_t T, int32_t lanes) {
     return kBlock / pick_shape(T, lanes).lpa;
 }
 
-int agent_step_stream(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes,
-                      const float *load, const float *p_est_old, const float *p_est_new,
-                      const float *p_sch, const float *gamma, float *p_sch_out, float *gamma_out,
-                      float *diff, float *dsq, int32_t *status, float *pdhg_dual, float kappa,
-                      int32_t mode, const revs_pdhg_t *pdhg_host, const int32_t *node_of,
-                      double *p_next, float *p_est_next, const StreamExtra &sx, void *stream) {
-    return agent_step_impl(n_homes, T, cost, homes, load, p_est_old, p_est_new, p_sch, gamma,
-                           p_sch_out, gamma_out, nullptr, nullptr, diff, dsq, status, pdhg_dual,
-                           kappa, mode, pdhg_host, nullptr, node_of, p_next, p_est_next, stream, &sx);
-}
-
-int agent_step_chain(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes,
-                     const float *load, const float *p_est, const float *p_sch, const float *gamma,
-                     float *p_sch_out, float *gamma_out, float *s_out, float *c_out, float *diff, float *dsq,
-                     int32_t *status, float *pdhg_dual, float kappa, int32_t mode, const revs_pdhg_t *pdhg_host,
-                     const int32_t *node_of, const ChainFold &cf, unsigned int *flags, void *stream) {
-    return agent_step_impl(n_homes, T, cost, homes, load, p_est, nullptr, p_sch, gamma, p_sch_out, gamma_out,
-                           s_out, c_out, diff, dsq, status, pdhg_dual, kappa, mode, pdhg_host, nullptr,
-                           node_of, nullptr, nullptr, stream, nullptr, flags, &cf);
-}
+int agent_step_stream(const SweepCall &c, const StreamExtra &sx) { return agent_step_impl(c, nullptr, &sx); }
+int agent_step_chain(const SweepCall &c, const ChainFold &cf) { return agent_step_impl(c, nullptr, nullptr, &cf); }
 
 // ---- verdicts by blocks (sharded streaming steady state, plan_stream.cpp) ----------------
 // With residences sharded the node sums of an iteration are only known after an all-reduce, and
@@ -1575,12 +1530,6 @@ int agent_step_chain(int64_t n_homes, int32_t T, const float *cost, const revs_h
 // did run worked from an estimate that is not the operator's answer: the state a block starts
 // from is never overwritten while its verdicts are pending (the sweeps of a block rotate through
 // the other sets of buffers, plan_stream.cpp), and the host goes back to it.
-// more than 64 KB of dynamic LDS (the big tree shapes) has to be granted per kernel, once
-template <int NT, int IPT, typename K>
-static bool tree_big_lds(K kernel, size_t lds) {
-    return grant_lds(reinterpret_cast<const void *>(kernel), lds, "tree form");
-}
-
 struct BlockVerdict {
     StreamCtl *ctl;
     unsigned int base_seq, gate_seq;      // no-op when a launch numbered base_seq..gate_seq failed
@@ -1758,35 +1707,24 @@ int stream_block_verdict(StreamCtl *ctl, unsigned int base_seq, unsigned int gat
                          const double *pre, double *ring, int64_t stride, int32_t mt, int32_t ntail,
                          double *hand_over, double vlo, double vhi, double vtol,
                          unsigned long long *grp_bits, double *grp_dmax, double *rec, void *stream) {
-    REVS_REQUIRE(ctl && nb >= 0 && nb < kRecRing && (nb > 0 || hand_over) && T > 0 && tree.n > 0 &&
-                 tree.n <= REVS_TREE_MAX && tree.n % tree_shape(tree.n).ipt == 0 && tree.pack && tree.w && ring && stride >= mt + ntail &&
+    REVS_REQUIRE(ctl && nb >= 0 && nb < kRecRing && (nb > 0 || hand_over) && T > 0 && tree_form_ok(tree) && ring && stride >= mt + ntail &&
                  mt > 0 && ntail >= 0 && vlo <= vhi && vtol >= 0.0 && grp_bits && grp_dmax && rec &&
-                 (!pre || nb >= 1), "stream_block_verdict: bad argument");
+                 (!pre || nb >= 1), "stream_block_verdict: bad argument (" REVS_TREE_FORM_MSG ")", REVS_TREE_FORM_ARGS(tree, REVS_TREE_MAX));
     // (the arrival words follow the maxima: revs_plan_set_stream_block allocates both halves)
     const BlockVerdict b{ctl, base_seq, gate_seq, first_seq, nb, T, nb + (hand_over ? 1 : 0), tree, pre, ring,
                          (long long)stride, mt, ntail, hand_over, vlo, vhi, vtol, grp_bits, grp_bits + kGrpWords, grp_dmax, rec};
     const size_t lds = tree_lds_bytes(tree.n);
-    const TreeShape sh = tree_shape(tree.n);
     // two slots per workgroup where a 16-byte request can fetch them (the 256 x 8 shape: registers)
-    const bool pair = sh.nt == 256 && T % 2 == 0 && stride % 2 == 0 && ((uintptr_t)ring & 15u) == 0 && (!pre || ((uintptr_t)pre & 15u) == 0);
+    const bool pair = tree_shape(tree.n).nt == 256 && T % 2 == 0 && stride % 2 == 0 && ((uintptr_t)ring & 15u) == 0 && (!pre || ((uintptr_t)pre & 15u) == 0);
     const dim3 grid((unsigned)(nb * (pair ? T / 2 : T) + (hand_over ? kHandOverGroups : 0)));
     if (pair) {
         hipLaunchKernelGGL((stream_block_verdict_kernel<256, 8, true>), grid, dim3(256), lds, (hipStream_t)stream, b);
         REVS_CHECK_LAUNCH("stream_block_verdict");
         return REVS_OK;
     }
-#define VK(NT, IPT)                                                                                            \
-    do {                                                                                                       \
-        if (!tree_big_lds<NT, IPT>(stream_block_verdict_kernel<NT, IPT>, lds)) return REVS_ELAUNCH;            \
-        hipLaunchKernelGGL((stream_block_verdict_kernel<NT, IPT>), grid, dim3(NT), lds, (hipStream_t)stream, b); \
-    } while (0)
-    if (sh.nt == 256) VK(256, 8);
-    else if (sh.nt == 512) VK(512, 8);
-    else if (sh.ipt == 8) VK(1024, 8);
-    else VK(1024, 16);
-#undef VK
-    REVS_CHECK_LAUNCH("stream_block_verdict");
-    return REVS_OK;
+    return for_tree_shape(tree.n, [&](auto nt, auto ipt) {
+        return launch_lds(stream_block_verdict_kernel<nt(), ipt()>, grid, dim3(nt()), lds, (hipStream_t)stream, "stream_block_verdict", b);
+    });
 }
 
 template <int NT, int IPT>
@@ -1802,25 +1740,13 @@ __global__ __launch_bounds__(NT) void tree_voltage_kernel(TreeArgs tr, const dou
 extern "C" int revs_tree_voltage(int32_t m, int32_t T, const revs_tree_t *tree, const double *p,
                                  double vlo, double vhi, double *v_out, double *rmax_out,
                                  void *stream) {
-    REVS_REQUIRE(m > 0 && T > 0 && tree && p && tree->n > 0 && tree->n <= REVS_TREE_MAX &&
-                 tree->n % tree_shape(tree->n).ipt == 0 && tree->pack && tree->w && vlo <= vhi,
-                 "revs_tree_voltage: bad argument (tree nodes <= %d, a multiple of 8; of 16 beyond 8192)", REVS_TREE_MAX);
-    const TreeArgs tr{tree->n, (const unsigned long long *)tree->pack, tree->w};
-    const size_t lds = tree_lds_bytes(tree->n);
-    const TreeShape sh = tree_shape(tree->n);
-#define VK(NT, IPT)                                                                                    \
-    do {                                                                                               \
-        if (!tree_big_lds<NT, IPT>(tree_voltage_kernel<NT, IPT>, lds)) return REVS_ELAUNCH;            \
-        hipLaunchKernelGGL((tree_voltage_kernel<NT, IPT>), dim3(T), dim3(NT), lds, (hipStream_t)stream, \
-                           tr, p, T, vlo, vhi, v_out, rmax_out);                                       \
-    } while (0)
-    if (sh.nt == 256) VK(256, 8);
-    else if (sh.nt == 512) VK(512, 8);
-    else if (sh.ipt == 8) VK(1024, 8);
-    else VK(1024, 16);
-#undef VK
-    REVS_CHECK_LAUNCH("revs_tree_voltage");
-    return REVS_OK;
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(m > 0 && T > 0 && p && tree_form_ok(tr) && vlo <= vhi,
+                 "revs_tree_voltage: bad argument (" REVS_TREE_FORM_MSG ")", REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
+    return for_tree_shape(tr.n, [&](auto nt, auto ipt) {
+        return launch_lds(tree_voltage_kernel<nt(), ipt()>, dim3(T), dim3(nt()), tree_lds_bytes(tr.n), (hipStream_t)stream,
+                          "revs_tree_voltage", tr, p, T, vlo, vhi, v_out, rmax_out);
+    });
 }
 
 extern "C" int revs_agent_step_out(int64_t n_homes, int32_t T, const float *cost,
@@ -1831,9 +1757,13 @@ extern "C" int revs_agent_step_out(int64_t n_homes, int32_t T, const float *cost
                                    float *dsq, int32_t *status, float *pdhg_dual,
                                    float kappa, int32_t mode, const revs_pdhg_t *pdhg_host,
                                    void *stream) {
-    return agent_step_impl(n_homes, T, cost, homes, load, p_est_old, p_est_new, p_sch, gamma,
-                           p_sch_out, gamma_out, s_out, c_out, diff, dsq, status, pdhg_dual,
-                           kappa, mode, pdhg_host, nullptr, nullptr, nullptr, nullptr, stream);
+    SweepCall c;
+    c.n_homes = n_homes; c.T = T; c.cost = cost; c.homes = homes; c.load = load;
+    c.p_est_old = p_est_old; c.p_est_new = p_est_new;
+    c.p_sch = p_sch; c.gamma = gamma; c.p_sch_out = p_sch_out; c.gamma_out = gamma_out;
+    c.s_out = s_out; c.c_out = c_out; c.diff = diff; c.dsq = dsq; c.status = status;
+    c.pdhg_dual = pdhg_dual; c.kappa = kappa; c.mode = mode; c.pdhg = pdhg_host; c.stream = stream;
+    return agent_step_impl(c);
 }
 
 extern "C" int32_t revs_agent_max_inner(int32_t T, int32_t lanes) {
@@ -1863,9 +1793,14 @@ extern "C" int revs_agent_step_multi(int64_t n_homes, int32_t T, const float *co
     sx.slice_stride = slice_stride;
     sx.diff_stride = diff_stride;
     sx.dmax_out = dmax_out;
-    return agent_step_impl(n_homes, T, cost, homes, load, p_est, nullptr, p_sch, gamma, p_sch_out, gamma_out,
-                           nullptr, nullptr, diff, dsq, status, pdhg_dual, kappa, mode, pdhg_host, nullptr,
-                           node_of, p_next, p_est_next, stream, &sx);
+    SweepCall c;
+    c.n_homes = n_homes; c.T = T; c.cost = cost; c.homes = homes; c.load = load;
+    c.p_est_old = p_est;
+    c.p_sch = p_sch; c.gamma = gamma; c.p_sch_out = p_sch_out; c.gamma_out = gamma_out;
+    c.diff = diff; c.dsq = dsq; c.status = status;
+    c.pdhg_dual = pdhg_dual; c.kappa = kappa; c.mode = mode; c.pdhg = pdhg_host; c.stream = stream;
+    c.node_of = node_of; c.p_next = p_next; c.pe2_out = p_est_next;
+    return agent_step_impl(c, nullptr, &sx);
 }
 
 extern "C" int revs_agent_step_select(int64_t n_homes, int32_t T, const float *cost,
@@ -1887,9 +1822,14 @@ extern "C" int revs_agent_step_select(int64_t n_homes, int32_t T, const float *c
     REVS_REQUIRE(sel_nblk >= 0 && sel_nblk <= 256, "revs_agent_step_select: sel_nblk=%d", sel_nblk);
     const SelectArgs sa{m, T, sel_nblk ? sel_nblk : revs_op_dual_blocks(m), kadd, sel_partial, y, vfull, viol, vlo, vhi,
                         seq, cand_idx, cand_cnt, cand_val, stats};
-    return agent_step_impl(n_homes, T, cost, homes, load, p_est_old, p_est_new, p_sch, gamma,
-                           p_sch_out, gamma_out, s_out, c_out, diff, dsq, status, pdhg_dual,
-                           kappa, mode, pdhg_host, &sa, node_of, p_next, p_est_next, stream);
+    SweepCall c;
+    c.n_homes = n_homes; c.T = T; c.cost = cost; c.homes = homes; c.load = load;
+    c.p_est_old = p_est_old; c.p_est_new = p_est_new;
+    c.p_sch = p_sch; c.gamma = gamma; c.p_sch_out = p_sch_out; c.gamma_out = gamma_out;
+    c.s_out = s_out; c.c_out = c_out; c.diff = diff; c.dsq = dsq; c.status = status;
+    c.pdhg_dual = pdhg_dual; c.kappa = kappa; c.mode = mode; c.pdhg = pdhg_host; c.stream = stream;
+    c.node_of = node_of; c.p_next = p_next; c.pe2_out = p_est_next;
+    return agent_step_impl(c, &sa);
 }
 
 extern "C" int revs_agent_step(int64_t n_homes, int32_t T, const float *cost,

@@ -28,13 +28,31 @@ struct StreamExtra {
 };
 int64_t agent_homes_per_block(int32_t T, int32_t lanes);     // residences per workgroup of the sweep's launch
 
-// revs_agent_step_select's sweep with the next home pass folded in, plus `sx` (see above).
-int agent_step_stream(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes,
-                      const float *load, const float *p_est_old, const float *p_est_new,
-                      const float *p_sch, const float *gamma, float *p_sch_out, float *gamma_out,
-                      float *diff, float *dsq, int32_t *status, float *pdhg_dual, float kappa,
-                      int32_t mode, const revs_pdhg_t *pdhg_host, const int32_t *node_of,
-                      double *p_next, float *p_est_next, const StreamExtra &sx, void *stream);
+// One launch of the residences' sweep, by name (the arguments of revs_agent_step_select, revs_admm.h, without the
+// selection's).  StreamExtra / ChainFold add what the streaming steady state / the folded chain need.
+struct SweepCall {
+    int64_t n_homes = 0;
+    int32_t T = 0;
+    const float *cost = nullptr;
+    const revs_home_t *homes = nullptr;
+    const float *load = nullptr;
+    const float *p_est_old = nullptr, *p_est_new = nullptr;     // (p_est_new NULL: recomputed)
+    const float *p_sch = nullptr, *gamma = nullptr;             // state in
+    float *p_sch_out = nullptr, *gamma_out = nullptr;           // state out
+    float *s_out = nullptr, *c_out = nullptr;
+    float *diff = nullptr, *dsq = nullptr;                      // residual outputs
+    int32_t *status = nullptr;
+    float *pdhg_dual = nullptr;
+    float kappa = 0.f;
+    int32_t mode = 0;
+    const revs_pdhg_t *pdhg = nullptr;
+    const int32_t *node_of = nullptr;
+    double *p_next = nullptr;                                   // node sums for the next iteration
+    float *pe2_out = nullptr;                                   // its estimate
+    unsigned int *flags = nullptr;                              // status bits (device address of pinned memory)
+    void *stream = nullptr;
+};
+int agent_step_stream(const SweepCall &c, const StreamExtra &sx);
 
 // The folded chain's sweep (AgentArgs::sh_a in agent_kernels.hip): the residences' iteration with
 // the operator's answer formed inside, pen = max(g0 - d[node], 0), d = sh_a (double[m][T]: the shifts
@@ -51,11 +69,7 @@ struct ChainFold {
     float *y_out = nullptr;     // the carried PDHG multipliers after this sweep (NULL: in place)
     const int32_t *wg_order = nullptr;   // as StreamExtra::wg_order
 };
-int agent_step_chain(int64_t n_homes, int32_t T, const float *cost, const revs_home_t *homes,
-                     const float *load, const float *p_est, const float *p_sch, const float *gamma,
-                     float *p_sch_out, float *gamma_out, float *s_out, float *c_out, float *diff, float *dsq,
-                     int32_t *status, float *pdhg_dual, float kappa, int32_t mode, const revs_pdhg_t *pdhg_host,
-                     const int32_t *node_of, const ChainFold &cf, unsigned int *flags, void *stream);
+int agent_step_chain(const SweepCall &c, const ChainFold &cf);
 
 // The folded chain's operator launch (newton_kernels.hip: op_chain_kv_kernel).  One side = one
 // evaluation judged by the tree form: its node sums pnq (p | N | q), the multipliers, scratch for

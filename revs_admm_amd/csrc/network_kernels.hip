@@ -776,11 +776,10 @@ static int net_report_check(const char *who, int32_t m, int32_t T, const revs_tr
                             int32_t n_out, double vset, double vmin, double vmax) {
     REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
     REVS_REQUIRE(m > 0 && m <= 0xFFFF, "%s: m=%d outside 1..65535", who, (int)m);
-    REVS_REQUIRE(tree && node_g && tree->pack && tree->w, "%s: null pointer argument", who);
-    REVS_REQUIRE(tree->n > 0 && tree->n <= REVS_TREE_MAX && tree->n % tree_shape(tree->n).ipt == 0,
-                 "%s: tree of %d nodes (at most %d, a multiple of 8; of 16 beyond 8192)", who, (int)tree->n,
-                 REVS_TREE_MAX);
-    REVS_REQUIRE(n_out > 0 && n_out <= tree->n, "%s: n_out=%d outside 1..tree nodes", who, (int)n_out);
+    REVS_REQUIRE(node_g, "%s: null pointer argument", who);
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(tree_form_ok(tr), "%s: " REVS_TREE_FORM_MSG, who, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
+    REVS_REQUIRE(n_out > 0 && n_out <= tr.n, "%s: n_out=%d outside 1..tree nodes", who, (int)n_out);
     REVS_REQUIRE(vset == vset && vset >= 0.0 && vset < INFINITY, "%s: vset must be finite and >= 0", who);
     REVS_REQUIRE(vmin <= vmax, "%s: vmin > vmax", who);                 // (also rejects NaN)
     return REVS_OK;
@@ -792,7 +791,7 @@ static int net_report_launch(const char *who, int32_t S, int32_t m, int32_t T, c
                              double *loading_out, double *volt_out, revs_net_summary_t *summary_out,
                              int32_t *band_count_out, void *stage, void *stream) {
     NetArgs A;
-    A.tr = TreeArgs{tree->n, (const unsigned long long *)tree->pack, tree->w};
+    A.tr = tree_args(tree);
     A.g = node_g; A.rating = rating; A.mask = node_mask; A.nop = node_of_pos;
     A.m = m; A.T = T; A.n_out = n_out;
     A.vset2 = vset * vset; A.vmin = vmin; A.vmax = vmax;
@@ -800,21 +799,9 @@ static int net_report_launch(const char *who, int32_t S, int32_t m, int32_t T, c
     for (int b = 0; b < REVS_STUDY_MAX_BANDS; ++b) A.band[b] = b < B ? band[b] : -INFINITY;
     A.bandc = B > 0 ? band_count_out : nullptr; A.nband = B;
     A.stage = (unsigned long long *)stage;
-    const size_t lds = net_lds_bytes(tree->n);
-    const TreeShape sh = tree_shape(tree->n);
-#define NK(NT, IPT)                                                                                              \
-    do {                                                                                                         \
-        if (!grant_lds(reinterpret_cast<const void *>(net_report_kernel<NT, IPT>), lds, "network report"))       \
-            return REVS_ELAUNCH;                                                                                 \
-        hipLaunchKernelGGL((net_report_kernel<NT, IPT>), dim3(T, S), dim3(NT), lds, (hipStream_t)stream, A);     \
-    } while (0)
-    if (sh.nt == 256) NK(256, 8);
-    else if (sh.nt == 512) NK(512, 8);
-    else if (sh.ipt == 8) NK(1024, 8);
-    else NK(1024, 16);
-#undef NK
-    REVS_CHECK_LAUNCH(who);
-    return REVS_OK;
+    return for_tree_shape(tree->n, [&](auto nt, auto ipt) {
+        return launch_lds(net_report_kernel<nt(), ipt()>, dim3(T, S), dim3(nt()), net_lds_bytes(tree->n), (hipStream_t)stream, who, A);
+    });
 }
 
 extern "C" int revs_net_report(int32_t m, int32_t T, const revs_tree_t *tree, const double *node_g, const double *rating,

@@ -1974,7 +1974,7 @@ int chain_kv_launch(const ChainKv &c, void *stream) {
     k.clr0 = c.clr0; k.clr1 = c.clr1; k.clr_count = 4 * mt;      // (the folded sweep's arrays: {p, N, q, 0} per node and slot)
     k.sh_a = c.sh_a; k.sh_b = c.sh_b;
     k.prev_ci = c.prev_cidx; k.prev_cc = c.prev_cidx ? c.prev_ccnt : nullptr;
-    const size_t lds = ((tree_lds_bytes(c.tree.n) / sizeof(double) + 1) / 2 * 2 + 4 * (size_t)c.m + 4) * sizeof(double);
+    const size_t lds = (tree_lds_doubles_even(c.tree.n) + 4 * (size_t)c.m + 4) * sizeof(double);
     // (a slot's rows are staged in LDS: 4 m doubles beside the tree's scan buffer and ~30 KB of static LDS)
     REVS_REQUIRE(c.m <= REVS_CHAIN_FOLD_MAX_M && lds <= 128 * 1024,
                  "chain_kv_launch: m = %d rows do not fit the operator launch's LDS (at most %d)", c.m, REVS_CHAIN_FOLD_MAX_M);
@@ -2174,35 +2174,14 @@ extern "C" int revs_op_dual_step_pending(int32_t T, const int64_t *cand_idx, con
     return REVS_OK;
 }
 
-static bool tree_ok(const revs_tree_t *tree) {       // the fused launches: one workgroup of 256 x 8 positions per slot
-    return tree && tree->n > 0 && tree->n <= REVS_TREE_SWEEP_MAX && tree->n % 8 == 0 && tree->pack && tree->w;
-}
-static bool tree_ok_big(const revs_tree_t *tree) {   // the evaluations' row launches: every shape of tree_body.h
-    return tree && tree->n > 0 && tree->n <= REVS_TREE_MAX && tree->n % tree_shape(tree->n).ipt == 0 && tree->pack && tree->w;
-}
-template <int NT, int IPT, typename K>
-static bool rows_big_lds(K kernel, size_t lds) {     // more than 64 KB of dynamic LDS is granted per kernel and device
-    return grant_lds(reinterpret_cast<const void *>(kernel), lds, "revs_op_dual_rows_tree");
-}
-
 static int dual_shift_tree(int32_t m, int32_t T, const revs_tree_t *tree, const double *y, double *d_out, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok_big(tree) && y && d_out, "revs_op_dual_evaluate_tree: bad argument");
-    const TreeArgs tr{tree->n, (const unsigned long long *)tree->pack, tree->w};
-    const size_t lds = tree_lds_bytes(tree->n);
-    const TreeShape sh = tree_shape(tree->n);
-#define SK(NT, IPT)                                                                                                       \
-    do {                                                                                                                  \
-        if (!grant_lds(reinterpret_cast<const void *>(&op_tree_shift_kernel<NT, IPT>), lds, "revs_op_dual_evaluate_tree")) \
-            return REVS_ELAUNCH;                                                                                          \
-        hipLaunchKernelGGL((op_tree_shift_kernel<NT, IPT>), dim3(T), dim3(NT), lds, S_(stream), tr, T, y, d_out);         \
-    } while (0)
-    if (sh.nt == 256) SK(256, 8);
-    else if (sh.nt == 512) SK(512, 8);
-    else if (sh.ipt == 8) SK(1024, 8);
-    else SK(1024, 16);
-#undef SK
-    REVS_CHECK_LAUNCH("revs_op_dual_evaluate_tree");
-    return REVS_OK;
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_form_ok(tr) && y && d_out,
+                 "revs_op_dual_evaluate_tree: bad argument (" REVS_TREE_FORM_MSG ")", REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
+    return for_tree_shape(tr.n, [&](auto nt, auto ipt) {
+        return launch_lds(op_tree_shift_kernel<nt(), ipt()>, dim3(T), dim3(nt()), tree_lds_bytes(tr.n), S_(stream),
+                          "revs_op_dual_evaluate_tree", tr, T, y, d_out);
+    });
 }
 
 extern "C" int revs_op_dual_rows_tree(int32_t m, int32_t T, const revs_tree_t *tree, const double *pnq,
@@ -2210,27 +2189,21 @@ extern "C" int revs_op_dual_rows_tree(int32_t m, int32_t T, const revs_tree_t *t
                                       double *viol, double *partial, double *zero_out, int64_t *cand_idx,
                                       int32_t *cand_cnt, double *cand_val, double *stats, double seq,
                                       int32_t with_select, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok_big(tree) && pnq && y && vfull && viol &&
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_form_ok(tr) && pnq && y && vfull && viol &&
                  partial && vlo <= vhi && kadd >= 0 && zero_out != pnq &&
                  (!with_select || (cand_idx && cand_cnt && cand_val && stats)),
-                 "revs_op_dual_rows_tree: bad argument (tree nodes <= %d, a multiple of 8; of 16 beyond 8192)", REVS_TREE_MAX);
-    const TreeArgs tr{tree->n, (const unsigned long long *)tree->pack, tree->w};
+                 "revs_op_dual_rows_tree: bad argument (" REVS_TREE_FORM_MSG ")", REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
     const TreeRowsArgs ta{tr, m, T, pnq, pnq + 2 * (int64_t)m * T, y, vlo, vhi, vfull, viol, partial, zero_out};
     const SelectArgs sa{m, T, 1, kadd, partial, y, vfull, viol, vlo, vhi, seq, cand_idx, cand_cnt, cand_val, stats};
-    if (tree->n > REVS_TREE_SWEEP_MAX) {
+    if (tr.n > REVS_TREE_SWEEP_MAX) {
         // more than 2048 nodes: the rows by a workgroup of 512 or 1024 threads per slot, the selection behind it
-        const size_t lds = tree_lds_bytes(tree->n);
-        const TreeShape sh = tree_shape(tree->n);
-#define RK(NT, IPT)                                                                                           \
-        do {                                                                                                  \
-            if (!rows_big_lds<NT, IPT>(op_tree_rows_big_kernel<NT, IPT>, lds)) return REVS_ELAUNCH;           \
-            hipLaunchKernelGGL((op_tree_rows_big_kernel<NT, IPT>), dim3(T), dim3(NT), lds, S_(stream), ta);   \
-        } while (0)
-        if (sh.nt == 512) RK(512, 8);
-        else if (sh.ipt == 8) RK(1024, 8);
-        else RK(1024, 16);
-#undef RK
-        REVS_CHECK_LAUNCH("revs_op_dual_rows_tree");
+        const int rc = for_tree_shape(tr.n, [&](auto nt, auto ipt) {
+            if constexpr (nt() == 256) return REVS_EINVAL;      // (never taken: that shape is op_tree_rows_kernel's, below)
+            else return launch_lds(op_tree_rows_big_kernel<nt(), ipt()>, dim3(T), dim3(nt()), tree_lds_bytes(tr.n), S_(stream),
+                                   "revs_op_dual_rows_tree", ta);
+        });
+        if (rc != REVS_OK) return rc;
         if (with_select) {
             hipLaunchKernelGGL(op_dual_select_kernel, dim3(T), dim3(256), 0, S_(stream), sa);
             REVS_CHECK_LAUNCH("revs_op_dual_rows_tree (selection)");
@@ -2239,15 +2212,15 @@ extern "C" int revs_op_dual_rows_tree(int32_t m, int32_t T, const revs_tree_t *t
     }
     if (with_select) {
         // (the rows go to the selection through LDS where they fit: vfull / viol are scratch of this call then)
-        const size_t staged_lds = ((tree_lds_bytes(tree->n) / sizeof(double) + 1) / 2 * 2 + 3 * (size_t)m + 4) * sizeof(double);
+        const size_t staged_lds = (tree_lds_doubles_even(tr.n) + 3 * (size_t)m + 4) * sizeof(double);
         const bool staged = staged_lds <= 120 * 1024;
         if (staged && !grant_lds(reinterpret_cast<const void *>(&op_tree_rows_kernel<true>), staged_lds > 64 * 1024 ? 120 * 1024 : staged_lds,
                                  "revs_op_dual_rows_tree"))
             return REVS_ELAUNCH;
-        hipLaunchKernelGGL((op_tree_rows_kernel<true>), dim3(T), dim3(256), staged ? staged_lds : tree_lds_bytes(tree->n), S_(stream),
+        hipLaunchKernelGGL((op_tree_rows_kernel<true>), dim3(T), dim3(256), staged ? staged_lds : tree_lds_bytes(tr.n), S_(stream),
                            ta, sa, staged ? 1 : 0);
     } else {
-        hipLaunchKernelGGL((op_tree_rows_kernel<false>), dim3(T), dim3(256), tree_lds_bytes(tree->n), S_(stream), ta, sa, 0);
+        hipLaunchKernelGGL((op_tree_rows_kernel<false>), dim3(T), dim3(256), tree_lds_bytes(tr.n), S_(stream), ta, sa, 0);
     }
     REVS_CHECK_LAUNCH("revs_op_dual_rows_tree");
     return REVS_OK;
@@ -2259,16 +2232,17 @@ extern "C" int revs_op_dual_tree_select_model_step(
         int32_t *cand_cnt, double *cand_val, double *stats, double seq, const double *R, double kappa,
         double delta, int32_t max_pivots, double *k_full, double *yhat, int32_t *info, double scale,
         double eps, double *y_trial, double *lin_out, void *stream) {
-    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_ok(tree) && pnq && y && vfull && viol &&
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && T <= REVS_ENS_MAX_COLS && tree_sweep_ok(tr) && pnq && y && vfull && viol &&
                  partial && cand_idx && cand_cnt && cand_val && stats && vlo <= vhi && kadd >= 0 && R && k_full &&
                  yhat && info && kappa > 0 && delta >= 0 && max_pivots > 0 && scale > 0.0 && y_trial &&
-                 y_trial != y && lin_out, "revs_op_dual_tree_select_model_step: bad argument");
-    const TreeArgs tr{tree->n, (const unsigned long long *)tree->pack, tree->w};
+                 y_trial != y && lin_out, "revs_op_dual_tree_select_model_step: bad argument (" REVS_TREE_FORM_MSG ")",
+                 REVS_TREE_FORM_ARGS(tr, REVS_TREE_SWEEP_MAX));
     const TreeRowsArgs ta{tr, m, T, pnq, pnq + 2 * (int64_t)m * T, y, vlo, vhi, vfull, viol, partial, nullptr};
     const SelectArgs sa{m, T, 1, kadd, partial, y, vfull, viol, vlo, vhi, seq, cand_idx, cand_cnt, cand_val, stats};
     const FusedArgs fa{R, pnq + (int64_t)m * T, y, 1.0 / kappa, delta, scale, eps, max_pivots, k_full, yhat,
                        y_trial, lin_out, info};
-    hipLaunchKernelGGL(op_tree_select_model_step_kernel, dim3(T), dim3(256), tree_lds_bytes(tree->n), S_(stream),
+    hipLaunchKernelGGL(op_tree_select_model_step_kernel, dim3(T), dim3(256), tree_lds_bytes(tr.n), S_(stream),
                        ta, sa, fa);
     REVS_CHECK_LAUNCH("revs_op_dual_tree_select_model_step");
     return REVS_OK;
@@ -2363,8 +2337,8 @@ extern "C" int revs_op_dual_evaluate_tree(int32_t phase, int32_t m, int32_t T, c
                                           float *p_est_new, double *vfull, double *viol, double *partial,
                                           int64_t *cand_idx, int32_t *cand_cnt, double *cand_val,
                                           double *stats, double seq, void *stream) {
-    REVS_REQUIRE(tree_ok_big(tree), "revs_op_dual_evaluate_tree: bad tree (at most %d nodes, a multiple of 8; of 16 beyond 8192)",
-                 REVS_TREE_MAX);
+    const TreeArgs tr = tree_args(tree);
+    REVS_REQUIRE(tree_form_ok(tr), "revs_op_dual_evaluate_tree: " REVS_TREE_FORM_MSG, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
     return dual_evaluate_impl(phase, m, T, node_ptr, p_est, p_sch, gamma, R, nullptr, y, use_y, kappa, vlo, vhi,
                               kadd, ksplit, d_slabs, nullptr, pnq, p_est_new, vfull, viol, partial, cand_idx,
                               cand_cnt, cand_val, stats, seq, nullptr, tree, stream);

@@ -94,6 +94,18 @@ static inline revs_tree_t plan_tree(const revs_plan *plan) {
     return revs_tree_t{plan->tree.n, (const uint64_t *)plan->tree.pack, plan->tree.w};
 }
 
+// The part of a sweep's call that no launch of a run changes; the loops set the rotating buffers per launch.
+static inline revs::SweepCall plan_sweep_call(const revs_plan_desc_t &d, void *stream) {
+    revs::SweepCall c;
+    c.n_homes = d.n_homes; c.T = d.T;
+    c.cost = d.cost; c.homes = d.homes; c.load = d.load;
+    c.dsq = d.dsq; c.status = d.status;
+    c.kappa = (float)d.kappa; c.mode = d.mode; c.pdhg = &d.pdhg;
+    c.node_of = d.node_of;
+    c.stream = stream;
+    return c;
+}
+
 // Candidate set k (0 or 1) of the plan's descriptor: the lists, the stats block and its pinned host side.
 struct PlanSet {
     int64_t *ci;

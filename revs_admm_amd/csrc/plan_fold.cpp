@@ -119,15 +119,21 @@ extern "C" int revs_plan_chain_fold_run(revs_plan_t *plan, int32_t max_steps, re
                                                                 st->pdhg_dual_3 != st->pdhg_dual_new))),
                  "revs_plan_chain_fold_run: pdhg_dual must be the plan's, with distinct spares");
     const bool ybuf = warm && st->pdhg_dual != nullptr;      // (else: updated in place, as before round 4)
+    revs::SweepCall call = plan_sweep_call(d, stream);       // (what no launch of this run changes)
+    call.diff = d.diff;
     auto sweep = [&](int parity, const float *pe, const float *ps, const float *gm, float *pe_out, float *ps_out, float *gm_out,
                      float *s_out, float *c_out, float *y_in, float *y_out) -> int {
         revs::ChainFold cf{plan->fold_sh[0], plan->fold_sh[1], d.m, d.kappa, plan->fold_e2[parity],
                            plan->fold_e1[parity ^ 1], pe_out};
         cf.y_out = ybuf ? y_out : nullptr;
         cf.wg_order = plan_wg_order(plan);
-        int r = revs::agent_step_chain(d.n_homes, d.T, d.cost, d.homes, d.load, pe, ps, gm, ps_out, gm_out, s_out, c_out, d.diff,
-                                       d.dsq, d.status, ybuf ? y_in : d.pdhg_dual, (float)d.kappa, d.mode, &d.pdhg, d.node_of, cf,
-                                       plan->flags_dev ? plan->flags_dev + 1 + sweep_no % 3u : nullptr, stream);
+        call.p_est_old = pe;
+        call.p_sch = ps; call.gamma = gm;
+        call.p_sch_out = ps_out; call.gamma_out = gm_out;
+        call.s_out = s_out; call.c_out = c_out;
+        call.pdhg_dual = ybuf ? y_in : d.pdhg_dual;
+        call.flags = plan->flags_dev ? plan->flags_dev + 1 + sweep_no % 3u : nullptr;
+        int r = revs::agent_step_chain(call, cf);
         ++sweep_no;
         // Residences sharded: every rank's sweep has folded its own residences' addends -- exact and order-independent
         // (revs_q36 / revs_q32), so the all-reduced sums are the one-process sums bit for bit.  Both arrays in ONE

@@ -161,6 +161,7 @@ extern "C" int revs_plan_stream_run_blocks(revs_plan_t *plan, int32_t max_steps,
     // One launch: iterations k .. k + kin - 1 from set `in` to set `out`; their node sums and diff
     // tails to slices (k - k0) .. of `ring` (replay: one scratch region, no tails).
     const int32_t *const wg_order = plan_wg_order(plan);
+    revs::SweepCall call = plan_sweep_call(d, stream);       // (what no launch of this run changes)
     auto sweep = [&](int k, int kin, int in, int out, double *slice0, bool replay, float *pe_next,
                      bool y_in_place) -> int {
         revs::StreamExtra sx{};
@@ -176,11 +177,13 @@ extern "C" int revs_plan_stream_run_blocks(revs_plan_t *plan, int32_t max_steps,
         sx.diff_stride = st->diff_hist ? d.n_homes : 0;
         sx.dmax_out = replay ? nullptr : slice0 + mt + (int64_t)rank * REVS_DMAX_SLOTS;
         sx.wg_order = wg_order;
-        return revs::agent_step_stream(
-            d.n_homes, d.T, d.cost, d.homes, d.load, st->p_est[in], nullptr, st->p_sch[in], st->gamma[in],
-            st->p_sch[out], st->gamma[out],
-            st->diff_hist ? st->diff_hist + (int64_t)k * d.n_homes : d.diff, d.dsq, d.status,
-            warm ? st->pdhg_dual[in] : nullptr, (float)d.kappa, d.mode, &d.pdhg, d.node_of, slice0, pe_next, sx, s);
+        call.p_est_old = st->p_est[in];
+        call.p_sch = st->p_sch[in]; call.gamma = st->gamma[in];
+        call.p_sch_out = st->p_sch[out]; call.gamma_out = st->gamma[out];
+        call.diff = st->diff_hist ? st->diff_hist + (int64_t)k * d.n_homes : d.diff;
+        call.pdhg_dual = warm ? st->pdhg_dual[in] : nullptr;
+        call.p_next = slice0; call.pe2_out = pe_next;
+        return revs::agent_step_stream(call, sx);
     };
     // events of the overlapped form: [2 b] = block b's sweeps are done, [2 b + 1] = its verdicts are
     // in, [2 nblocks] = the side stream has finished this call
@@ -383,6 +386,8 @@ extern "C" int revs_plan_stream_run(revs_plan_t *plan, int32_t max_steps, revs_s
     const unsigned int seq0 = plan->stream_seq + 1;
     const int64_t mt = (int64_t)d.m * d.T;
     REVS_REQUIRE(plan->block <= 1, "revs_plan_stream_run: verdicts by blocks go through revs_plan_stream_run_blocks");
+    revs::SweepCall call = plan_sweep_call(d, stream);       // (what no launch of this run changes)
+    call.pdhg_dual = d.pdhg_dual;
     auto launch = [&](int k) -> int {               // step k of this call (roles by rotation)
         revs::StreamExtra sx;
         sx.ctl = plan->ctl;
@@ -396,15 +401,15 @@ extern "C" int revs_plan_stream_run(revs_plan_t *plan, int32_t max_steps, revs_s
         sx.rec = plan->rec_dev + 4 * (sx.seq % revs::kRecRing);
         sx.flags = plan->flags_dev;
         sx.m = d.m;
-        double *p_next = st->p[(k + 1) % 3];
-        int rc = revs::agent_step_stream(
-            d.n_homes, d.T, d.cost, d.homes, d.load, st->p_est[k % 3],
-            d.recompute_pe_new ? nullptr : st->p_est[(k + 1) % 3], st->p_sch[k % 2], st->gamma[k % 2],
-            st->p_sch[(k + 1) % 2], st->gamma[(k + 1) % 2],
-            st->diff_hist ? st->diff_hist + (int64_t)k * d.n_homes : d.diff, d.dsq, d.status, d.pdhg_dual,
-            (float)d.kappa, d.mode, &d.pdhg, d.node_of, p_next, st->p_est[(k + 2) % 3], sx, stream);
+        call.p_est_old = st->p_est[k % 3];
+        call.p_est_new = d.recompute_pe_new ? nullptr : st->p_est[(k + 1) % 3];
+        call.p_sch = st->p_sch[k % 2]; call.gamma = st->gamma[k % 2];
+        call.p_sch_out = st->p_sch[(k + 1) % 2]; call.gamma_out = st->gamma[(k + 1) % 2];
+        call.diff = st->diff_hist ? st->diff_hist + (int64_t)k * d.n_homes : d.diff;
+        call.p_next = st->p[(k + 1) % 3]; call.pe2_out = st->p_est[(k + 2) % 3];
+        int rc = revs::agent_step_stream(call, sx);
         if (rc != REVS_OK) return rc;
-        if (plan->comm) rc = revs_comm_allreduce_f64(plan->comm, p_next, mt, 0, stream);
+        if (plan->comm) rc = revs_comm_allreduce_f64(plan->comm, call.p_next, mt, 0, stream);
         return rc;
     };
     // All max_steps launches (and, sharded, their collectives) are enqueued in ONE burst, then

@@ -160,9 +160,9 @@ extern "C" void revs_plan_destroy(revs_plan_t *plan) {
 extern "C" int revs_plan_set_tree(revs_plan_t *plan, const revs_tree_t *t) {
     REVS_REQUIRE(plan, "revs_plan_set_tree: null plan");
     if (!t || t->n == 0) { plan->tree = revs::TreeArgs{}; return REVS_OK; }
-    REVS_REQUIRE(t->n > 0 && t->n <= REVS_TREE_MAX && t->n % revs::tree_shape(t->n).ipt == 0 && t->pack && t->w,
-                 "revs_plan_set_tree: bad tree (at most %d nodes, a multiple of 8; of 16 beyond 8192)", REVS_TREE_MAX);
-    plan->tree = revs::TreeArgs{t->n, (const unsigned long long *)t->pack, t->w};
+    const revs::TreeArgs tr = revs::tree_args(t);
+    REVS_REQUIRE(revs::tree_form_ok(tr), "revs_plan_set_tree: " REVS_TREE_FORM_MSG, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
+    plan->tree = tr;
     return REVS_OK;
 }
 

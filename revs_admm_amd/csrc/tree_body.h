@@ -7,6 +7,8 @@
 // the sweep's occupancy), 512 x 8, 1024 x 8 and 1024 x 16 up to REVS_TREE_MAX = 16 384 in the
 // stand-alone launches.
 #pragma once
+#include <type_traits>
+#include <utility>
 #include "common.h"
 
 namespace revs {
@@ -25,6 +27,10 @@ __host__ __device__ inline TreeShape tree_shape(int n) {
 __host__ __device__ inline size_t tree_lds_bytes(int n) {
     const TreeShape sh = tree_shape(n);
     return sizeof(double) * (2 + (size_t)sh.nt * sh.ipt + 2 * (sh.nt / 64));
+}
+// doubles from the start of that LDS to whatever a kernel keeps behind it (rounded up to an even count: 16-byte aligned)
+__host__ __device__ inline size_t tree_lds_doubles_even(int n) {
+    return (tree_lds_bytes(n) / sizeof(double) + 1) / 2 * 2;
 }
 
 // Inclusive prefix sum over the 64 lanes of a wavefront, doubles, on the DPP network: four
@@ -325,5 +331,39 @@ struct StreamCtl {
     unsigned long long rmax_bits;         // max over their slots (bit pattern of a double >= 0)
 };
 constexpr int kRecRing = 1024;             // records double[kRecRing][4] in pinned host memory
+
+// ---- the host side of the tree form: every entry point validates, converts and launches through these ----------
+inline TreeArgs tree_args(const revs_tree_t *t) {       // (a NULL tree: n = 0, which no predicate accepts)
+    return t ? TreeArgs{t->n, (const unsigned long long *)t->pack, t->w} : TreeArgs{};
+}
+// every shape above: the stand-alone launches
+inline bool tree_form_ok(const TreeArgs &t) {
+    return t.n > 0 && t.n <= REVS_TREE_MAX && t.n % tree_shape(t.n).ipt == 0 && t.pack && t.w;
+}
+// the 256 x 8 shape only: a sweep's launch and the fused operator launches
+inline bool tree_sweep_ok(const TreeArgs &t) {
+    return t.n > 0 && t.n <= kTreeSweepMax && t.n % 8 == 0 && t.pack && t.w;
+}
+// what a refused tree is told: REVS_REQUIRE(tree_form_ok(tr), "who: " REVS_TREE_FORM_MSG, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX))
+#define REVS_TREE_FORM_MSG "tree of %d nodes (at most %d, a multiple of 8; of 16 beyond 8192), or a null pointer in it"
+#define REVS_TREE_FORM_ARGS(tr, most) (int)(tr).n, (int)(most)
+
+// f(integral_constant<int, NT>, integral_constant<int, IPT>) for the shape that holds n nodes; returns f's int
+template <typename F>
+int for_tree_shape(int n, F &&f) {
+    const TreeShape sh = tree_shape(n);
+    if (sh.nt == 256) return f(std::integral_constant<int, 256>{}, std::integral_constant<int, 8>{});
+    if (sh.nt == 512) return f(std::integral_constant<int, 512>{}, std::integral_constant<int, 8>{});
+    if (sh.ipt == 8) return f(std::integral_constant<int, 1024>{}, std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 1024>{}, std::integral_constant<int, 16>{});
+}
+// One launch with `bytes` of dynamic LDS (granted first where that is more than 64 KB: grant_lds in common.h).
+template <typename... P, typename... A>
+int launch_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t bytes, hipStream_t stream, const char *who, A &&...args) {
+    if (!grant_lds(reinterpret_cast<const void *>(kernel), bytes, who)) return REVS_ELAUNCH;
+    hipLaunchKernelGGL(kernel, grid, block, bytes, stream, std::forward<A>(args)...);
+    REVS_CHECK_LAUNCH(who);
+    return REVS_OK;
+}
 
 }  // namespace revs
