@@ -313,7 +313,8 @@ void agent_step_kernel(const AgentArgs a) {
     // 74 at 125 000 x 96, where a wavefront holds 4 residences and the memory-side f64 atomics
     // quadruple.)
     constexpr int kSlots = LPA * SPL, kNodeLoc = shape_node_loc(kSlots);
-    // (at most 24 KB of accumulators per workgroup: 16 iterations up to 32 slots per group, 8 up to 96, 4 beyond)
+    // (at most 24 KB of accumulators per workgroup, shape_max_inner: 32 iterations up to 24 slots per group, 16 up to 96
+    // -- beyond 48 slots with two node accumulators instead of four --, 8 beyond)
     constexpr int kAcc = MULTI ? shape_max_inner(kSlots) : 1;
     __shared__ double nacc[kAcc][kNodeLoc][kSlots];
     __shared__ unsigned int dmx[kAcc];

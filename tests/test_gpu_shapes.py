@@ -1,0 +1,635 @@
+"""Every lane shape of the residence kernels in every launch form.
+
+pick_shape(T) (revs_admm_amd/csrc/agent_kernels.hip) maps the horizon onto nine (lanes per residence x slots per
+lane) shapes -- 8x1, 8x2, 8x3, 8x4, 16x3, 16x4, 16x6, 32x4, 64x3 -- and every shape is its own instantiation of every
+kernel: other scan widths, other dead lanes, 32 / 16 / 8 / 4 residences per workgroup, 4 or 2 node accumulators in LDS,
+32 / 16 / 8 inner iterations per launch.  Here each of them is held to the oracle (oracle/revs_oracle.py) and to the
+other launch forms: one iteration per launch (revs_agent_step), several in registers (revs_agent_step_multi), the dual
+bound and the individual mode; then the engine's loops (block verdicts with their roll-back, the folded chain, the
+certificate's bound) at horizons other than 24 and 96.
+
+n = 777 residences leave a partly filled last workgroup at all four workgroup sizes (777 mod 32 = 9, mod 16 = 9,
+mod 8 = 1, mod 4 = 1).  Inputs are float32-representable, so the kernel and the oracle see the same numbers."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+N = 777
+# first and last horizon of every shape's band that tests/test_gpu_agent.py does not run (27: an odd row stride under
+# four-slot lanes)
+EDGES = [8, 9, 16, 17, 25, 27, 32, 48, 49, 64, 65, 97, 128, 129, 191]
+# one horizon per shape that leaves dead lanes and a partly filled lane
+RAGGED = [7, 13, 19, 29, 41, 57, 83, 113, 171]
+# one full horizon per (inner-iteration cap, LDS node accumulators) class, and the slots > 48 boundary
+FULL = [24, 48, 64, 192]
+# inner iterations a launch may hold (24 KB of LDS accumulators, 4 nodes up to 48 slots per
+# lane group and 2 beyond)
+MAX_INNER = {"8x1": 32, "8x2": 32, "8x3": 32, "8x4": 16, "16x3": 16, "16x4": 16, "16x6": 16, "32x4": 8, "64x3": 8}
+REVS_EINVAL = -1
+DMAX_SLOTS = 64        # REVS_DMAX_SLOTS
+
+
+def shape_of(T):
+    """The lane shape of horizon T (lanes == 0), as DESIGN.md section 3.1 lists the bands."""
+    for top, name in ((8, "8x1"), (16, "8x2"), (24, "8x3"), (32, "8x4"), (48, "16x3"), (64, "16x4"), (96, "16x6"),
+                      (128, "32x4"), (192, "64x3")):
+        if T <= top:
+            return name
+    raise ValueError(T)
+
+
+def _ids(Ts):
+    return [pytest.param(T, id=f"T{T}-{shape_of(T)}") for T in Ts]
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(_bits(a), _bits(b))
+
+
+def _note(part, **kw):
+    """One line per case with the largest error against each bar (how much room the bars leave)."""
+    print(f"SHAPES part={part} " + " ".join(f"{k}={v:.3e}" if isinstance(v, float) else f"{k}={v}" for k, v in kw.items()))
+
+
+def test_every_shape_is_named():
+    """The horizon sets reach all nine shapes (parts 1-3 name them in their ids)."""
+    assert {shape_of(T) for T in RAGGED} == set(MAX_INNER) and len(RAGGED) == 9
+    assert {shape_of(T) for T in EDGES} == set(MAX_INNER)
+
+
+# ---- 1. one iteration per launch at every band edge ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def relaxed_oracle():
+    """ro.home_solve_relaxed of a horizon's workload, once for the three solvers that are held to it."""
+    return {}
+
+
+@pytest.mark.parametrize("keys64", [1, 0])
+@pytest.mark.parametrize("T", _ids(EDGES))
+def test_one_iteration_on_off_at_band_edges(gpu_lib, T, keys64):
+    """revs_agent_step, on/off chargers, from the zero state and from a mid-run state, at test_binary_matches_oracle's
+    bars: keys64 = 1 the oracle's schedule for EVERY residence; keys64 = 0 objective within 2e-5, identical slot
+    counts, nothing outside the window, more than 99.5 % of the residences identical; status the oracle's."""
+    from oracle import revs_oracle as ro
+    from test_gpu_agent import _prep, _run_agent, _state
+    w, oh = _prep(N, T, seed=T)
+    rates = np.concatenate([[0.0], np.unique(w.homes["rating"]).astype(np.float64)])
+    for zero_state in (True, False):
+        if zero_state:
+            pe_old = pe_new = ps = gm = np.zeros((N, T))
+        else:
+            pe_old, pe_new, ps, gm = _state(w, T)
+        r = _run_agent(gpu_lib, w, pe_old, pe_new, ps, gm, "binary", dict(keys64=keys64))
+        p, s, g, st = ro.home_solve_binary(w.cost, oh, pe_old, ps, gm, w.kappa)
+        assert ((r["status"] & 0xFF) == st).all()
+        assert (st == 0).mean() > 0.9
+        obj_gpu = ro.home_objective(w.cost, oh, r["S"], pe_old, ps, gm, w.kappa)
+        obj_ref = ro.home_objective(w.cost, oh, p, pe_old, ps, gm, w.kappa)
+        obj_err = float(np.max(np.abs(obj_gpu - obj_ref) / np.maximum(1.0, np.abs(obj_ref))))
+        same = (np.abs(r["S"] - p).max(axis=1) == 0)
+        _note(1, T=T, shape=shape_of(T), mode="binary", keys64=keys64, zero=int(zero_state), obj=obj_err,
+              differ=int((~same).sum()), feasible=float((st == 0).mean()))
+        assert obj_err < 2e-5
+        if keys64:
+            assert same.all(), (int((~same).sum()), N)
+        else:
+            assert same.mean() > 0.995
+        assert ((r["S"] > 0).sum(1) == (p > 0).sum(1)).all()
+        assert (r["S"][~oh.window()] == 0).all()
+        assert np.isin(r["S"], rates).all()
+        chk = pe_new - g
+        G = gm + 0.5 * w.kappa * chk
+        np.testing.assert_allclose(r["P_sch"][same], g[same], rtol=2e-6, atol=2e-6)
+        np.testing.assert_allclose(r["C"][same], s[same], rtol=2e-6, atol=2e-6)
+        np.testing.assert_allclose(r["G"][same], G[same], rtol=1e-5, atol=1e-5)
+        np.testing.assert_allclose(r["diff"][same], np.linalg.norm(chk, axis=1)[same] / T, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("mode", ["relaxed_exact", "pdhg", "pdhg_presolve"])
+@pytest.mark.parametrize("T", _ids(EDGES))
+def test_one_iteration_relaxed_at_band_edges(gpu_lib, relaxed_oracle, T, mode):
+    """revs_agent_step, continuous chargers (closed form, PDHG, PDHG behind the KKT steps: polish = 3), at
+    test_relaxed_matches_oracle's bars: 5e-5 kW x max(1, rating), C 2e-4, its G / diff / dsq bars; no residence flagged."""
+    from oracle import revs_oracle as ro
+    from test_gpu_agent import _prep, _run_agent, _state
+    w, oh = _prep(N, T, seed=100 + T, binary_feasible=False)
+    pe_old, pe_new, ps, gm = _state(w, T + 1)
+    name, pdhg = mode, None
+    if mode == "pdhg_presolve":
+        mode, pdhg = "pdhg", dict(polish=3)
+    r = _run_agent(gpu_lib, w, pe_old, pe_new, ps, gm, mode, pdhg)
+    if T not in relaxed_oracle:
+        relaxed_oracle[T] = ro.home_solve_relaxed(w.cost, oh, pe_old, ps, gm, w.kappa)
+    p, s, g, st = relaxed_oracle[T]
+    chk = pe_new - g
+    _note(1, T=T, shape=shape_of(T), mode=name, S=float(np.abs(r["S"] - p).max()), C=float(np.abs(r["C"] - s).max()),
+          G=float(np.abs(r["G"] - (gm + 0.5 * w.kappa * chk)).max()),
+          diff=float(np.abs(r["diff"] - np.linalg.norm(chk, axis=1) / T).max()))
+    assert (st == 0).all() and ((r["status"] & 0xFF) == st).all()
+    assert np.abs(r["S"] - p).max() < 5e-5 * max(1.0, w.homes["rating"].max())
+    np.testing.assert_allclose(r["C"], s, atol=2e-4)
+    np.testing.assert_allclose(r["G"], gm + 0.5 * w.kappa * chk, atol=2e-3, rtol=1e-5)
+    np.testing.assert_allclose(r["diff"], np.linalg.norm(chk, axis=1) / T, atol=1e-4, rtol=1e-4)
+    np.testing.assert_allclose(r["dsq"], ((g - ps) ** 2).sum(axis=1), rtol=2e-3, atol=1e-6)
+
+
+# ---- 2. revs_agent_step_multi against a chain of custody -----------------------------------------------------------
+class _Sweep:
+    """The arguments of revs_agent_step_multi that do not change between launches, on the device."""
+
+    def __init__(self, lib, w, node_of, M, mode):
+        import torch
+        from revs_admm_amd import _lib
+        from revs_admm_amd._lib import HOME_DTYPE, PDHG
+        self.torch, self.lib = torch, lib
+        self.dev = torch.device("cuda:0")
+        self.n, self.T = w.load.shape
+        self.M, self.mt = M, M * self.T
+        self.stride = self.mt + DMAX_SLOTS          # a slice: the node sums, then the partial maxima of diff
+        self.kappa, self.mode, self.pdhg_mode = w.kappa, _lib.MODES[mode], mode == "pdhg"
+        self.cost, self.load = self.up(w.cost), self.up(w.load)
+        self.homes = torch.from_numpy(w.homes.view(np.uint8).reshape(self.n, HOME_DTYPE.itemsize).copy()).to(self.dev)
+        self.node_of = torch.from_numpy(np.ascontiguousarray(node_of, np.int32)).to(self.dev)
+        self.pd = PDHG()
+        lib.revs_pdhg_defaults(C.byref(self.pd))
+        if mode == "binary":
+            self.pd.keys64 = 1                       # the oracle's decision for every residence
+        self.stream = torch.cuda.current_stream().cuda_stream
+
+    def up(self, a, dt=np.float32):
+        return self.torch.from_numpy(np.ascontiguousarray(a, dt)).to(self.dev)
+
+    def call(self, src, dst, y_in, y_out, pen2, diff, dsq, status, ring_row, kin):
+        """One launch; returns the entry point's code."""
+        from revs_admm_amd._lib import ptr
+        return self.lib.revs_agent_step_multi(
+            self.n, self.T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(src[0]), ptr(src[1]), ptr(src[2]),
+            ptr(dst[0]), ptr(dst[1]), ptr(dst[2]), ptr(pen2), ptr(diff), self.n, ptr(dsq), ptr(status), ptr(y_in),
+            ptr(y_out), self.kappa, self.mode, C.byref(self.pd), ptr(self.node_of), ptr(ring_row), self.stride,
+            ring_row.data_ptr() + 8 * self.mt, kin, self.stream)
+
+    def run(self, state, kins, rotate_y):
+        """Launches of kins[0], kins[1], ... iterations from `state` = (P_est, P_sch, G), buffers rotating.  Returns
+        the snapshot after every launch (numpy), every iteration's diff row and every iteration's ring slice."""
+        torch = self.torch
+        from revs_admm_amd._lib import check
+        cur = [self.up(a) for a in state]
+        nxt = [torch.empty_like(t) for t in cur]
+        y = torch.zeros(self.n, dtype=torch.float32, device=self.dev) if self.pdhg_mode else None
+        y2 = torch.zeros_like(y) if (self.pdhg_mode and rotate_y) else y
+        tot = sum(kins)
+        ring = torch.zeros(tot, self.stride, dtype=torch.float64, device=self.dev)
+        diff = torch.zeros(tot, self.n, dtype=torch.float32, device=self.dev)
+        pen2 = torch.zeros_like(cur[0])
+        dsq = torch.zeros(self.n, dtype=torch.float32, device=self.dev)
+        status = torch.zeros(self.n, dtype=torch.int32, device=self.dev)
+        snaps, k = [], 0
+        for kin in kins:
+            check(self.call(cur, nxt, y, y2, pen2, diff[k], dsq, status, ring[k], kin), "revs_agent_step_multi")
+            cur, nxt = nxt, cur
+            y, y2 = y2, y
+            k += kin
+            snaps.append(dict(P_est=cur[0].clone(), P_sch=cur[1].clone(), G=cur[2].clone(), pen2=pen2.clone(),
+                              dsq=dsq.clone(), status=status.clone(), y=None if y is None else y.clone()))
+        torch.cuda.synchronize()
+        snaps = [{k_: (None if v is None else v.cpu().numpy()) for k_, v in s.items()} for s in snaps]
+        return snaps, diff.cpu().numpy(), ring.cpu().numpy()
+
+
+# the last (T, mode)'s chain and its float64 links: the work saved depends on the order of the cases, the result does not
+_LINKS = {}
+
+
+def _oracle_links(key, w, oh, state, chain, mode):
+    """The float64 link in front of every step of the chain (tests/sweep_ref.py).  Nothing in the residences' state
+    depends on the node layout, so the second layout of a (T, mode) reuses the links -- after checking that its chain
+    is the first one's, bit for bit."""
+    from sweep_ref import link
+    if key in _LINKS:
+        prev, links = _LINKS[key]
+        if all(_same_bits(a[k], b[k]) for a, b in zip(prev, chain) for k in ("P_est", "P_sch", "G")):
+            return links
+    links, st = [], tuple(np.asarray(a, np.float64) for a in state)
+    for s in chain:
+        links.append(link(w.cost, oh, st[0], st[1], st[2], w.kappa, "binary" if mode == "binary" else "relaxed"))
+        st = tuple(s[k].astype(np.float64) for k in ("P_est", "P_sch", "G"))
+    _LINKS.clear()                     # (one entry: the two layouts of a case run back to back)
+    _LINKS[key] = (chain, links)
+    return links
+
+
+def _entry_point_rejects(sw, state, kmax):
+    """kin beyond revs_agent_max_inner and a state updated in place: REVS_EINVAL on the host, nothing launched."""
+    import torch
+    src = [sw.up(a) for a in state]
+    dst = [torch.empty_like(t) for t in src]
+    scratch = dict(pen2=torch.zeros_like(src[0]), diff=torch.zeros(sw.n, dtype=torch.float32, device=sw.dev),
+                   dsq=torch.zeros(sw.n, dtype=torch.float32, device=sw.dev),
+                   status=torch.zeros(sw.n, dtype=torch.int32, device=sw.dev))
+    ring1 = torch.zeros((kmax + 1) * sw.stride, dtype=torch.float64, device=sw.dev)
+    assert sw.call(src, dst, None, None, ring_row=ring1, kin=kmax + 1, **scratch) == REVS_EINVAL
+    for j in range(3):                       # each array of the state in place
+        alias = list(dst)
+        alias[j] = src[j]
+        assert sw.call(src, alias, None, None, ring_row=ring1, kin=1, **scratch) == REVS_EINVAL
+    torch.cuda.synchronize()
+    assert float(ring1.abs().max()) == 0.0
+
+
+# horizons whose entry-point checks have run: they need no particular mode or layout, so whichever case reaches a
+# horizon first runs them (any order of the cases, or a selection of them, runs them once per horizon it touches)
+_ENTRY_CHECKED = set()
+
+
+@pytest.mark.parametrize("layout", ["dense", "sparse"])
+@pytest.mark.parametrize("mode", ["binary", "relaxed_exact", "pdhg"])
+@pytest.mark.parametrize("T", _ids(RAGGED + FULL))
+def test_multi_iteration_launch_equals_a_chain_of_single_launches(gpu_lib, T, mode, layout):
+    """revs_agent_step_multi called directly: kin = 3, then kin = revs_agent_max_inner(T, 0) from the state the first
+    launch left, against the same 3 + max iterations as launches of kin = 1 -- bit for bit (state, carried PDHG
+    multipliers, the prepared estimate, every diff row, dsq, status with the sticky low bits of a launch's inner
+    iterations, the node-sum slices, the partial maxima of diff) -- and every link of that chain against the float64
+    recurrence of tests/sweep_ref.py at the one-iteration bars: so all 3 + max inner iterations of every shape hang
+    on the oracle without a closed-loop tolerance.
+
+    dense: 16 nodes, the workgroups' LDS accumulators.  sparse: one residence per node -- every workgroup of every
+    shape spans more nodes than it has accumulators (at 64x3: 4 residences against 2) and sends the rest straight to
+    global f64 atomics.
+
+    Node sums ("exact, order-independent"): every slice of the multi-iteration launch equals
+    the chain's bit for bit, and the float64 np.add.at within 1e-12 of the slice's largest entry (bit for bit too
+    wherever no rounding can occur in any order: addends zero or >= 2^-20 kW in a sum below 2^10 kW)."""
+    from test_gpu_agent import _prep, _state
+    from sweep_ref import node_sums
+    lib = gpu_lib
+    shape = shape_of(T)
+    kmax = int(lib.revs_agent_max_inner(T, 0))
+    assert kmax == MAX_INNER[shape], (T, shape, kmax)
+    w, oh = _prep(N, T, seed=200 + T, binary_feasible=(mode == "binary"))
+    node_of, M = (w.node_of, 16) if layout == "dense" else (np.arange(N), N)
+    pe_old, _, ps, gm = _state(w, T + 2)
+    state = (pe_old, ps, gm)
+    sw = _Sweep(lib, w, node_of, M, mode)
+    mt, tot = sw.mt, 3 + kmax
+
+    if T not in _ENTRY_CHECKED:              # the entry point's own checks: once per horizon
+        _ENTRY_CHECKED.add(T)
+        _entry_point_rejects(sw, state, kmax)
+
+    # ---- the two runs ----
+    multi, m_diff, m_ring = sw.run(state, [3, kmax], rotate_y=True)
+    chain, c_diff, c_ring = sw.run(state, [1] * tot, rotate_y=False)
+
+    # bit for bit: the state after 3 and after 3 + max iterations, the prepared estimate, multipliers, dsq
+    for snap, at in ((multi[0], 2), (multi[1], tot - 1)):
+        for k in ("P_est", "P_sch", "G", "pen2", "dsq") + (("y",) if mode == "pdhg" else ()):
+            assert _same_bits(snap[k], chain[at][k]), (k, at)
+    # status: a launch reports its last iteration's word OR the low three bits of every inner iteration's
+    cst = np.stack([s["status"] for s in chain])
+    for snap, lo, hi in ((multi[0], 0, 3), (multi[1], 3, tot)):
+        want = cst[hi - 1] | np.bitwise_or.reduce(cst[lo:hi] & 7, axis=0)
+        assert np.array_equal(snap["status"], want), (lo, hi)
+    assert _same_bits(m_diff, c_diff)
+    # the estimate a launch prepares is the one the next launch recomputes
+    for i in range(tot - 1):
+        assert _same_bits(chain[i]["pen2"], chain[i + 1]["P_est"]), i
+    # partial maxima of diff: the maximum over the REVS_DMAX_SLOTS words of iteration i is that iteration's max diff
+    for name, ring, diff in (("multi", m_ring, m_diff), ("chain", c_ring, c_diff)):
+        got = ring[:, mt:].max(axis=1)
+        assert _same_bits(got, diff.max(axis=1).astype(np.float64)), name
+        assert (ring[:, mt:] >= 0).all()
+
+    # node-sum slices: slice i = node sums of P_est[g + i + 2] = the estimate step i prepared
+    slice_err, tiny = 0.0, 0
+    for i in range(tot):
+        pen2 = chain[i]["pen2"]
+        ref = node_sums(node_of, M, pen2).ravel()
+        big = max(np.abs(ref).max(), np.finfo(np.float64).tiny)
+        for ring in (m_ring, c_ring):
+            err = float(np.abs(ring[i, :mt] - ref).max() / big)
+            slice_err = max(slice_err, err)
+            assert err <= 1e-12, (i, err)
+        small = (pen2 > 0) & (pen2 < 2.0 ** -20)
+        tiny += int(small.sum())
+        cols = np.zeros((M, T), bool)                # (node, slot) sums that hold an addend below 2^-20 kW
+        np.logical_or.at(cols, np.asarray(node_of, np.int64), small)
+        sure = ~cols.ravel() & (ref < 2.0 ** 10)     # exact in any order
+        same = _bits(m_ring[i, :mt]) == _bits(c_ring[i, :mt])
+        assert same.all(), (i, int((~same).sum()))          # bit for bit, every (node, slot) sum
+        assert _same_bits(m_ring[i, :mt][sure], ref[sure]) and _same_bits(c_ring[i, :mt][sure], ref[sure]), i
+
+    # ---- every link of the chain against float64 ----
+    links = _oracle_links((T, mode), w, oh, state, chain, mode)
+    rate = max(1.0, float(w.homes["rating"].max()))
+    st = tuple(np.asarray(a, np.float64) for a in state)
+    worst = dict(pen=0.0, sch=0.0, G=0.0, diff=0.0)
+    for i, (s, lk) in enumerate(zip(chain, links)):
+        pe, p_s, G0 = st
+        pen_gpu, sch, Gn = (s[k].astype(np.float64) for k in ("P_est", "P_sch", "G"))
+        # the recomputed estimate: three float operations with a rounded 1 / kappa, 2^-23 of the sum; the bar is twice that
+        bar = 2.0 ** -22 * (0.5 * (np.abs(pe) + np.abs(p_s)) + np.abs(G0) / w.kappa)
+        excess = np.abs(pen_gpu - lk.pen) - bar
+        worst["pen"] = max(worst["pen"], float((np.abs(pen_gpu - lk.pen) / np.maximum(bar, 1e-300)).max()))
+        assert (excess <= 0).all(), (i, float(excess.max()))
+        assert np.array_equal(cst[i] & 0xFF, lk.status), i
+        chk = pen_gpu - lk.g
+        Gref = G0 + 0.5 * w.kappa * chk
+        dref = np.linalg.norm(chk, axis=1) / T
+        if mode == "binary":
+            on = (sch - oh.LOAD) > 0.5 * oh.rating[:, None]
+            assert np.array_equal(on & oh.ev[:, None], lk.p > 0), i      # keys64 = 1: the oracle's schedule, every residence
+            np.testing.assert_allclose(sch, lk.g, rtol=2e-6, atol=2e-6)
+            np.testing.assert_allclose(Gn, Gref, rtol=1e-5, atol=1e-5)
+            np.testing.assert_allclose(c_diff[i], dref, rtol=1e-5, atol=1e-6)
+        else:
+            assert np.abs(sch - lk.g).max() < 5e-5 * rate, i
+            np.testing.assert_allclose(Gn, Gref, atol=2e-3, rtol=1e-5)
+            np.testing.assert_allclose(c_diff[i], dref, atol=1e-4, rtol=1e-4)
+            np.testing.assert_allclose(s["dsq"], ((lk.g - p_s) ** 2).sum(axis=1), rtol=2e-3, atol=1e-6)
+        worst["sch"] = max(worst["sch"], float(np.abs(sch - lk.g).max()))
+        worst["G"] = max(worst["G"], float(np.abs(Gn - Gref).max()))
+        worst["diff"] = max(worst["diff"], float(np.abs(c_diff[i] - dref).max()))
+        st = (pen_gpu, sch, Gn)
+    _note(2, T=T, shape=shape, mode=mode, layout=layout, kin=f"3+{kmax}", slice=slice_err, tiny_addends=tiny,
+          pen_over_bar=worst["pen"], sch=worst["sch"], G=worst["G"], diff=worst["diff"])
+
+
+# ---- 3. dual bound and individual mode at every shape --------------------------------------------------------------
+@pytest.mark.parametrize("layout", ["dense", "sparse"])
+@pytest.mark.parametrize("T", _ids(RAGGED + [192]))
+def test_dual_bound_equals_the_float64_restatement(gpu_lib, T, layout):
+    """test_gpu_bound.test_kernel_equals_the_float64_restatement's cases and bars (relaxed and on/off, s in
+    {0, 0.5, 1, 3}, random signed y, five residences with empty rows; 1e-11 relative per part and on p_node,
+    bit-identical from call to call, empty residences counted exactly) at one horizon per lane shape; sparse: one
+    residence per node, so the minimiser's node sums leave the four LDS nodes for the global atomics."""
+    import torch
+    from bound_ref import dual_bound
+    from helpers import f32
+    from revs_admm_amd._lib import check, ptr
+    from revs_admm_amd.synthetic import make_workload
+    from test_gpu_bound import _sparse_y, _with_empty_rows
+    lib = gpu_lib
+    w = make_workload(N, T, n_nodes=60 if layout == "dense" else N, seed=7, binary_feasible=False, stress=1.0)
+    w.load, w.cost = f32(w.load), f32(w.cost)
+    node_np = w.node_of if layout == "dense" else np.arange(N)
+    homes, n_empty = _with_empty_rows(w.homes)
+    vlo, vhi = w.vlow ** 2 - w.vset ** 2, w.vhigh ** 2 - w.vset ** 2
+    rng = np.random.default_rng(T)
+    y = _sparse_y(rng, w.M, T)
+    d = w.Rn.T @ y
+    dev = torch.device("cuda:0")
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    cost, hd = up(w.cost.astype(np.float32)), up(homes.view(np.uint8).reshape(len(homes), 32))
+    node_of = up(node_np.astype(np.int32))
+    lsum = np.zeros((w.M, T))
+    np.add.at(lsum, node_np, w.load)
+    d_d, y_d, l_d = up(d), up(y), up(lsum)
+    scratch = torch.zeros(int(lib.revs_dual_bound_scratch(N, T)), dtype=torch.float64, device=dev)
+    out = torch.zeros(4, dtype=torch.float64, device=dev)
+    pn = torch.zeros(w.M, T, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    worst = dict(total=0.0, per_part=0.0, p_node=0.0)
+    for integral in (False, True):
+        for s in (0.0, 0.5, 1.0, 3.0):
+            got = []
+            for rep in range(2):
+                pn.zero_()
+                check(lib.revs_dual_bound(N, T, ptr(cost), ptr(hd), ptr(node_of), w.M, ptr(d_d), ptr(y_d), ptr(l_d),
+                                          s, vlo, vhi, int(integral), ptr(scratch), ptr(pn), ptr(out), st),
+                      "revs_dual_bound")
+                got.append((out.cpu().numpy().copy(), pn.cpu().numpy()))
+            (o1, p1), (o2, p2) = got
+            assert np.array_equal(o1, o2), (integral, s, o1, o2)       # bit-identical from call to call
+            ref, parts, empty, _, pref = dual_bound(w.cost, homes, w.load, node_np, w.Rn, y, s, vlo, vhi,
+                                                    integral=integral, d=d)
+            tot = (o1[0] + o1[1]) + o1[2]
+            worst["total"] = max(worst["total"], abs(tot - ref) / abs(ref))
+            assert abs(tot - ref) <= 1e-11 * abs(ref), (integral, s, tot, ref)
+            for k, v in zip(("home", "load", "row"), o1[:3]):
+                worst["per_part"] = max(worst["per_part"], abs(v - parts[k]) / max(abs(parts[k]), abs(ref)))
+                assert abs(v - parts[k]) <= 1e-11 * max(abs(parts[k]), abs(ref)), (k, v, parts[k])
+            assert o1[3] == empty >= n_empty
+            worst["p_node"] = max(worst["p_node"], float(np.abs(p1 - pref).max() / max(1.0, np.abs(pref).max())))
+            assert np.abs(p1 - pref).max() <= 1e-11 * max(1.0, np.abs(pref).max())
+            assert pref.max() > 0
+    _note(3, T=T, shape=shape_of(T), kernel="dual_bound", layout=layout, **worst)
+
+
+@pytest.mark.parametrize("T", _ids(RAGGED))
+def test_individual_mode_at_every_shape(gpu_lib, T):
+    """revs_residence_solve against ro.solve_residence on test_edge_parameters' residences (charged past 90 %, windows
+    reaching outside the horizon, one-slot windows, residences without an EV) at the golden test's bars: the oracle's
+    on/off pattern (ranked in double, ties to the earlier slot), SOC within 1e-6, g = p + LOAD exactly.
+
+    A slot is worth switching on while 0.01 c_t rating < 0.99 rating / capacity, i.e. c_t < 99 / capacity: 4.95 and
+    1.65 for the capacities 20 and 60 kW-slots here.  The tariff (five price levels in (0.05, 0.3), so that slots tie)
+    runs as it is (every slot pays: nmax decides), x 20 (levels in (1, 6): both thresholds inside its range, "while
+    negative" decides) and x 100 (no slot pays)."""
+    from helpers import f32, oracle_homes
+    from oracle import revs_oracle as ro
+    from revs_admm_amd.engine import pack_homes, residence_solve
+    from revs_admm_amd.synthetic import Workload
+    rng = np.random.default_rng(500 + T)
+    n = N
+    ev = np.ones(n, bool)
+    ev[::7] = False
+    rating = rng.choice([3.6, 7.2], n)
+    cap = rng.choice([20.0, 60.0], n)
+    init = rng.choice([0.05, 0.5, 0.91, 0.97], n)
+    start = rng.integers(-3, max(T - 1, 1), n)
+    end = start + rng.integers(1, T + 6, n)
+    homes = pack_homes(ev, rating, cap, init, start, end)
+    load = f32(rng.uniform(0.2, 5, (n, T)))
+    levels = rng.uniform(0.05, 0.3, 5)
+    base = levels[rng.integers(0, 5, T)]
+    w = Workload(f32(base), load, homes, np.zeros(n, np.int64), np.eye(1), None, None, 1.0, 0.95, 1.05, 5.0)
+    oh = oracle_homes(w)
+    assert (oh.window().sum(1)[oh.ev] == 1).any() and (oh.end > T).any() and (oh.start < 0).any()
+    stats, soc_err = {}, 0.0
+    for factor in (1.0, 20.0, 100.0):
+        tariff = f32(base * factor)
+        p, soc, g = residence_solve(tariff, homes, load)
+        p_or, s_or, g_or = ro.solve_residence(tariff, oh)
+        delta = 0.01 * tariff[None, :] * oh.rating[:, None] - 0.99 * (oh.rating / oh.capacity)[:, None]
+        pays = (delta < 0) & oh.window()
+        stats[factor] = float(pays.sum() / max(1, oh.window().sum()))
+        assert ((p > 0) == (p_or > 0)).all(), factor
+        assert np.array_equal(p[p > 0], oh.rating[:, None].repeat(T, 1)[p > 0].astype(np.float32))
+        soc_err = max(soc_err, float(np.abs(soc - s_or).max()))
+        np.testing.assert_allclose(soc, s_or, atol=1e-6)
+        assert np.array_equal(g, p + load.astype(np.float32)), factor
+    # the three regimes are what the docstring says
+    assert stats[1.0] == 1.0 and 0.05 < stats[20.0] < 0.95 and stats[100.0] == 0.0, stats
+    _note(3, T=T, shape=shape_of(T), kernel="residence", slots_that_pay_x20=stats[20.0], soc=soc_err)
+
+
+# ---- 4. the loops at other horizons (engine level) ------------------------------------------------------------------
+_CHUNKS = (1, 7, 30, 2, 50, 64, 11)          # test_gpu_admm._RAGGED
+_BLOCK = 5
+_ORACLE_RUNS = {}
+
+
+def _workload(n, T, nodes, seed, stress, binary=False, kappa=5.0, day_tariff=False):
+    """make_workload with float32-representable inputs.  day_tariff: the generator's day tariff read at every slot's
+    hour (slot 0 = 06:00) -- what make_workload itself uses where T is a multiple of 24; elsewhere it cuts or wraps the
+    24 hourly prices, which is no day."""
+    from helpers import f32
+    from revs_admm_amd.synthetic import DVP_TARIFF, make_workload
+    w = make_workload(n, T, n_nodes=nodes, seed=seed, binary_feasible=binary, stress=stress, kappa=kappa)
+    if day_tariff:
+        hour = np.floor((np.arange(T) + 0.5) * 24.0 / T).astype(np.int64)
+        cost = np.asarray(DVP_TARIFF, np.float64)[(6 + hour) % 24]
+        assert T % 24 or np.array_equal(cost, w.cost)
+        w.cost = cost
+    w.load, w.cost = f32(w.load), f32(w.cost)
+    return w
+
+
+def _oracle_run(key, w, iters):
+    """ro.solve_ADMM of a workload (continuous chargers), once for the cases that are held to it."""
+    from helpers import oracle_homes
+    from oracle import revs_oracle as ro
+    if key not in _ORACLE_RUNS:
+        _ORACLE_RUNS[key] = ro.solve_ADMM(oracle_homes(w), w.Rn, w.node_of, w.cost, w.kappa, iters, w.vset, w.vlow, w.vhigh,
+                                          mode="relaxed", util_method="dual")
+    return _ORACLE_RUNS[key]
+
+
+def _held_to_oracle(e, ref, last):
+    """test_wide_lane_shapes_in_the_engine's bars: S within 5e-4 kW, the last diff within 1e-3 x max(1, max diff)."""
+    d_ref, _, S_ref, _ = ref
+    S_err = float(np.abs(e.result()[1] - S_ref).max())
+    d_err = float(np.abs(e.diff.cpu().numpy()[e.inv_perm] - d_ref[last]).max())
+    return S_err, d_err, 1e-3 * max(1.0, float(d_ref.max()))
+
+
+# (T, seed, stress, kappa, onset): 600 residences on 100 nodes, chosen on the CPU from the oracle's run (continuous
+# chargers, 166 iterations).  In every such run the rows bind through the first 8 to 12 iterations -- iteration 2, the
+# first launch of the first streaming call, always fails -- and then rest with 3 to 12 % of the limit to spare.  From
+# there the estimate the operator would return without multipliers climbs by about 3e-4 of the limit per iteration as the
+# chargers move to the cheap slots, and leaves the limit a second time at iteration `onset` (counted from 0).  The
+# chunks put the first launch of a streaming call at iterations 40, 90 and 154, so `onset` is no first iteration of a
+# block of 5 (onset - 40 or - 90 is no multiple of 5), and neither is the iteration next to it wherever the margin
+# at `onset` is below 1e-4 of the limit (the float sweeps move the estimate by 1e-6 of it).
+#   The margin after the first iterations depends on the seed; the climb needs a tariff with cheap hours.  Where T is no
+# multiple of 24 make_workload's cut-and-wrapped tariff gives none: 24 seeds at T = 7, 31 at T = 33 and 25 at T = 60
+# (stress 1.1, and 1.001 to 1.06 at T = 7, 600 and 3000 residences, 100 and 200 nodes) ended 5 to 12 % inside the limit,
+# most of them moving away from it.  These horizons get the day tariff read per slot.  At T = 7 (slots of 3.4 hours, a
+# window of five at the most) the climb from -9 % takes 300 iterations at kappa = 5; at kappa = 1 it takes 65.
+_BLOCK_CASES = [
+    # T, seed, stress, kappa, onset      margin at onset - 1 / onset, relative to the limit
+    (7, 0, 1.05, 1.0, 77),             # -5.0e-4 / +8.7e-4
+    (33, 8, 1.1, 5.0, 108),            # -7.8e-6 / +3.3e-4 (106: -3.4e-4; failing at 107 it is its block's third verdict)
+    (48, 5, 1.1, 5.0, 126),            # -3.1e-4 / +1.1e-5
+    (60, 2, 1.098, 5.0, 146),          # -1.6e-4 / +1.4e-4
+    (120, 9, 1.098, 5.0, 146),         # -1.5e-4 / +1.8e-4
+    (144, 2, 1.1, 5.0, 144),           # -1.0e-4 / +2.2e-4
+]
+
+
+@pytest.mark.parametrize("overlap", [False, True])
+@pytest.mark.parametrize("inner", [3, "max"])
+@pytest.mark.parametrize("T,seed,stress,kappa,onset", _BLOCK_CASES, ids=[f"T{c[0]}-{shape_of(c[0])}" for c in _BLOCK_CASES])
+def test_block_verdicts_at_other_horizons(gpu_lib, T, seed, stress, kappa, onset, inner, overlap):
+    """test_gpu_admm.test_block_verdicts_equal_per_launch_verdicts' small cases (ragged chunks, stream_burst = 16,
+    stream_burst_max = 64; PDHG residences, blocks of 5, 3 or the most inner iterations per launch, verdicts beside or
+    behind the next block's sweeps) at odd horizons, which take the un-paired verdict kernel, and on the shapes with
+    16 and 8 inner iterations: same stream_calls, same memory bit for bit after every chunk, same results -- through a
+    verdict that fails INSIDE a block, so that the sweeps behind it had run and are rolled back.  The final state is
+    also the oracle's run (S within 5e-4 kW, last diff within 1e-3 x max)."""
+    from revs_admm_amd.engine import OperatorOptions
+    from test_gpu_admm import _engine, torch_equal
+    w = _workload(600, T, 100, seed, stress, kappa=kappa, day_tariff=True)
+    kmax = MAX_INNER[shape_of(T)]
+    kin = kmax if inner == "max" else inner
+    kw = dict(stream_burst=16, stream_burst_max=64)
+    a = _engine(w, "pdhg", op=OperatorOptions(stream_block_single=False, **kw))
+    b = _engine(w, "pdhg", op=OperatorOptions(stream_block=_BLOCK, stream_block_single=True, stream_overlap=overlap,
+                                              stream_inner=kin, **kw))
+    assert a._block == 0 and b._block == _BLOCK and b._inner == kin
+    for chunk in _CHUNKS:
+        a.run_steps(chunk)
+        b.run_steps(chunk)
+        assert a.iteration == b.iteration
+        assert a.stream_calls == b.stream_calls
+        for name in ("P_est", "P_sch", "G", "diff", "pdhg_dual"):
+            assert torch_equal(getattr(a, name), getattr(b, name)), (name, a.iteration)
+        if a._fused_ready:
+            assert b._fused_ready and torch_equal(a._fused_p, b._fused_p)
+            assert torch_equal(a.P_est_new, b.P_est_new)
+    assert a.spec_hist == b.spec_hist and a.chain_hist == b.chain_hist
+    assert a.op_iters_hist == b.op_iters_hist and a.newton_hist == b.newton_hist
+    failed = [(c, k) for c, k in b.stream_calls if k < c]
+    inside = [(c, k) for c, k in failed if k % _BLOCK]
+    print(f"SHAPES part=4 T={T} shape={shape_of(T)} inner={kin} overlap={int(overlap)} onset={onset} "
+          f"stream_calls={b.stream_calls} spec={b.spec_hist} chain={b.chain_hist}")
+    assert inside, b.stream_calls             # a verdict failed inside a block: iterations behind it were undone
+    a.step(write_sc=True); b.step(write_sc=True)
+    for x, y in zip(a.result(), b.result()):
+        np.testing.assert_array_equal(x, y)
+    iters = sum(_CHUNKS) + 1
+    S_err, d_err, d_bar = _held_to_oracle(b, _oracle_run(("block", T), w, iters), iters - 1)
+    _note(4, T=T, shape=shape_of(T), loop="block", S=S_err, diff=d_err, diff_bar=d_bar)
+    assert S_err < 5e-4 and d_err < d_bar
+
+
+@pytest.mark.parametrize("mode,stress", [("relaxed_exact", 1.3), ("binary", 1.0)])
+@pytest.mark.parametrize("T", _ids([33, 48, 120]))
+def test_folded_chain_at_other_horizons(gpu_lib, T, mode, stress):
+    """test_gpu_admm.test_chained_newton_iteration_changes_nothing (T = 24, the 8x3 instantiation of the CHAIN sweep) on
+    the shapes 16x3 and 32x4, at a stress where rows keep binding (on the CPU: the oracle's rows bind in 45 to 59 of the 60
+    iterations): chain = True against chain = False bit for bit (diff history, results, multipliers), the chain did
+    run, and the continuous run is the oracle's (S within 5e-4 kW, last diff within 1e-3 x max)."""
+    from revs_admm_amd.engine import OperatorOptions
+    from test_gpu_admm import _engine
+    iters = 60
+    w = _workload(600, T, 100, 5, stress, binary=(mode == "binary"))
+    runs = []
+    for chain in (True, False):
+        e = _engine(w, mode, op=OperatorOptions(chain=chain, fold_redo=2))
+        d = e.run(iters)
+        runs.append((d, e.result(), e.yd[0].cpu().numpy(), e))
+    (d1, r1, y1, e1), (d0, r0, y0, e0) = runs
+    print(f"SHAPES part=4 T={T} shape={shape_of(T)} loop=chain mode={mode} chain_hist={e1.chain_hist} spec={e1.spec_hist}")
+    assert e1.chain_hist[0] > 0 and e0.chain_hist == [0, 0], (e1.chain_hist, e1.newton_hist[-20:])
+    np.testing.assert_array_equal(d1, d0)
+    for x, y in zip(r1, r0):
+        np.testing.assert_array_equal(x, y)
+    np.testing.assert_array_equal(y1, y0)
+    if mode != "binary":
+        S_err, d_err, d_bar = _held_to_oracle(e1, _oracle_run(("chain", T), w, iters), iters - 1)
+        _note(4, T=T, shape=shape_of(T), loop="chain", S=S_err, diff=d_err, diff_bar=d_bar)
+        assert S_err < 5e-4 and d_err < d_bar
+
+
+@pytest.mark.parametrize("T", _ids([48, 144]))
+def test_lower_bound_at_other_horizons(gpu_lib, T):
+    """AdmmEngine.lower_bound (the certificate's evaluation: R y on the device, then dual_bound_kernel) against
+    tests/bound_ref.py at 1e-11 relative."""
+    from bound_ref import dual_bound
+    from test_gpu_admm import _engine
+    from test_gpu_bound import _sparse_y
+    w = _workload(600, T, 100, 11, 1.0)
+    vlo, vhi = w.vlow ** 2 - w.vset ** 2, w.vhigh ** 2 - w.vset ** 2
+    e = _engine(w, "pdhg")
+    y = _sparse_y(np.random.default_rng(T), w.M, T)
+    worst = 0.0
+    for s in (0.0, 1.0, 3.0):
+        got = e.lower_bound(y, s)
+        ref = dual_bound(w.cost, w.homes, w.load, w.node_of, w.Rn, y, s, vlo, vhi, integral=False)[0]
+        worst = max(worst, abs(got - ref) / abs(ref))
+        assert abs(got - ref) <= 1e-11 * abs(ref), (s, got, ref)
+    _note(4, T=T, shape=shape_of(T), loop="lower_bound", rel=worst)
