@@ -224,7 +224,9 @@ int revs_op_export(int64_t n_homes, int32_t T, const double *sb, float *p_est, v
  *   revs_op_dual_select  v = sum of the nslab slabs of R p; per slot t: candidate rows
  *                        (cand_idx int64[T][AMAX], cand_cnt int32[T], -1 when more than AMAX
  *                        rows carry a multiplier), cand_val double[T][3][AMAX] = sign (+1
- *                        upper row, -1 lower row), gradient v - b, current y;
+ *                        upper row, -1 lower row), gradient v - b, current y; every entry behind the
+ *                        list (all AMAX of a slot flagged -1) is padding: index 0, sign 1, gradient 0,
+ *                        y 0 -- here and in revs_op_dual_select_big; kadd beyond the room: what fits;
  *                        stats double[T][8]: [0] largest |v - b| over rows with y != 0 and
  *                        bound violation over the others, [1] D_t, [2] rows with y != 0,
  *                        [3] violated rows with y = 0 ([4] is left to revs_op_dual_step),

@@ -58,8 +58,9 @@ __global__ __launch_bounds__(256) void op_big_select_kernel(
     int pos = incl - nsup;
     for (int w = 0; w < (tid >> 6); ++w) pos += cnt_s[w];
     const int ns = cnt_s[0] + cnt_s[1] + cnt_s[2] + cnt_s[3], nv = nv_s[0] + nv_s[1] + nv_s[2] + nv_s[3];
-    if (ns > kBig) {                                  // (uniform) more multipliers than even this path holds
-        if (tid == 0) ccnt[t] = -1;
+    if (ns > kBig) {                                  // (uniform) more multipliers than even this path holds: flagged,
+        if (tid == 0) ccnt[t] = -1;                   // and the whole list padding, as the 128-row selection leaves it
+        for (int i = tid; i < kBig; i += 256) { ci[i] = 0; cs[i] = 1.0; cg[i] = 0.0; cy[i] = 0.0; }
         return;
     }
     for (int r = r0; r < r1 && nsup > 0; ++r) {
@@ -97,14 +98,14 @@ __global__ __launch_bounds__(256) void op_big_select_kernel(
         __syncthreads();
     }
     __syncthreads();
-    if (tid < added) {
-        const int bi = chosen[tid];
+    for (int i = tid; i < added; i += 256) {          // (up to kBig added rows: more than the workgroup has threads)
+        const int bi = chosen[i];
         const double v = vfull[(int64_t)bi * T + t];
         const bool up = v > vhi;
-        ci[ns + tid] = bi;
-        cs[ns + tid] = up ? 1.0 : -1.0;
-        cg[ns + tid] = v - (up ? vhi : vlo);
-        cy[ns + tid] = 0.0;
+        ci[ns + i] = bi;
+        cs[ns + i] = up ? 1.0 : -1.0;
+        cg[ns + i] = v - (up ? vhi : vlo);
+        cy[ns + i] = 0.0;
     }
     const int cnt = ns + added;
     if (tid == 0) ccnt[t] = cnt;
@@ -460,7 +461,7 @@ extern "C" int revs_op_dual_select_big(int32_t m, int32_t T, const double *y, co
                                        double vlo, double vhi, int32_t kadd, int64_t *cand_idx, int32_t *cand_cnt,
                                        double *cand_val, void *stream) {
     REVS_REQUIRE(m > 0 && m <= 16384 && T > 0 && y && vfull && viol && cand_idx && cand_cnt && cand_val && vlo <= vhi &&
-                 kadd >= 0 && kadd <= REVS_DUAL_AMAX_BIG, "revs_op_dual_select_big: bad argument");
+                 kadd >= 0, "revs_op_dual_select_big: bad argument");       // (kadd beyond the list's room: what fits, as revs_op_dual_select)
     hipLaunchKernelGGL(op_big_select_kernel, dim3(T), dim3(256), 0, S_(stream), m, T, y, vfull, viol, vlo, vhi, kadd,
                        cand_idx, cand_cnt, cand_val);
     REVS_CHECK_LAUNCH("revs_op_dual_select_big");

@@ -363,6 +363,7 @@ class FakeKernels:
 
     def revs_op_dual_select(self, m, T, nslab, vsl, pnq, y, vlo, vhi, kadd, vfull, viol, partial,
                             cidx, ccnt, cval, stats, seq, stream):
+        """(held against tests/select_ref.py's lexsort restatement of the same rule in tests/test_select_ref.py)"""
         A = DUAL_AMAX
         v = view(vsl, (nslab, m, T), np.float64).sum(axis=0)
         view(vfull, (m, T), np.float64)[:] = v
