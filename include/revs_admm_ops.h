@@ -74,6 +74,26 @@ int revs_aggregate_f32(int32_t m, int32_t T, const int64_t *node_ptr,
 /* Doubles of scratch revs_dual_bound (revs_admm.h) needs for n_homes residences (0: bad size). */
 int64_t revs_dual_bound_scratch(int64_t n_homes, int32_t T);
 
+/* revs_dual_bound for the S scenarios of an ensemble (revs_admm_amd/ensemble.py) in ONE launch plus a
+ * finalize, on the ensemble's own layout: homes revs_home_t[n_res][S] (record res S + s), node_of int32[n_res] shared by
+ * the scenarios, d / y / load_node double[m][S T] (scenario s: columns s T + t), scale DEVICE double[S] (one scale per
+ * scenario; the host cannot see its sign: the caller keeps it >= 0), out device double[S][4].  out[s] = what
+ * revs_dual_bound writes for scenario s alone -- {residences' part, LOAD part, row part, residences with empty rows}
+ * of L_s(scale[s] y_s), d_s = R y_s, relaxed or integral -- BIT FOR BIT what that call gives on contiguous copies of the
+ * scenario's records and columns with the same scale, and the same bits from call to call: grid (T + nhb) x S, column
+ * s of the grid being the single call's workgroups over the same residences, their partials in scratch[s], summed per
+ * scenario in the single call's order.  d and y: both or neither (NULL: no multipliers); load_node may be NULL;
+ * n_res == 0: the slot-wise terms only (out[s][1] = sum c . load_node_s).  No p_node output.  Enqueues only.
+ * REVS_EINVAL before any launch: T outside 1..REVS_MAX_T, S < 1, S T > REVS_ENS_MAX_COLS, n_res < 0, m <= 0, a null
+ * cost / scale / scratch / out, null homes / node_of with n_res > 0, d without y or y without d, vlo > vhi, more than
+ * 2^31 workgroups per scenario.  scratch: double[revs_dual_bound_many_scratch] = S revs_dual_bound_scratch(n_res, T)
+ * (0: bad size). */
+int64_t revs_dual_bound_many_scratch(int64_t n_res, int32_t S, int32_t T);
+int revs_dual_bound_many(int64_t n_res, int32_t S, int32_t T, const float *cost, const revs_home_t *homes,
+                         const int32_t *node_of, int32_t m, const double *d, const double *y, const double *load_node,
+                         const double *scale, double vlo, double vhi, int32_t integral, double *scratch, double *out,
+                         void *stream);
+
 /* g0 = (P_est + P_sch)/2 - G/kappa : the unconstrained minimiser of the Utility
  * objective (lpsolver.py:196-207).  float in, double out. */
 int revs_op_g0(int64_t n_homes, int32_t T, const float *p_est, const float *p_sch,

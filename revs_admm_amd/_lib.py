@@ -167,6 +167,8 @@ SIGNATURES = {
     "revs_residence_solve": (C.c_int, [_i64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "revs_dual_bound": (C.c_int, [_i64, _i32, _p, _p, _p, _i32, _p, _p, _p, _f64, _f64, _f64, _i32, _p, _p, _p, _p]),
     "revs_dual_bound_scratch": (_i64, [_i64, _i32]),
+    "revs_dual_bound_many": (C.c_int, [_i64, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p, _f64, _f64, _i32, _p, _p, _p]),
+    "revs_dual_bound_many_scratch": (_i64, [_i64, _i32, _i32]),
     "revs_gemm_tn_f64": (C.c_int, [_i32, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _p]),
     "revs_gemm_tn_f32": (C.c_int, [_i32, _i32, _i32, _p, _i32, _p, _i32, _p, _i32, _i32, _p]),
     "revs_gemm_tn_f64_split": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _i32, _p]),

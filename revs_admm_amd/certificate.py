@@ -25,6 +25,84 @@ from ._lib import check, ptr
 _GOLD = (math.sqrt(5.0) - 1.0) / 2.0
 
 
+def _ray_search_steps():
+    """The search of certificate(search=True) along a ray, written once as a generator: it yields every scale it wants
+    evaluated (each distinct scale once: the memo is here), is sent (value, empty) for it, and returns
+    (s, value, empty) of the best scale seen -- ties to the smaller scale.  L(s y) is concave in s >= 0: the value at 0
+    and 1, doubling while the value rises, then 24 golden-section steps on the bracket."""
+    seen = {}
+
+    def phi(x):
+        if x not in seen:
+            seen[x] = yield x
+        return seen[x][0]
+    f0, f1 = (yield from phi(0.0)), (yield from phi(1.0))
+    if math.isinf(f0):
+        a = b = 0.0
+    elif f1 <= f0:
+        a, b = 0.0, 1.0
+    else:
+        x = 1.0
+        for _ in range(60):
+            if (yield from phi(2.0 * x)) <= (yield from phi(x)):
+                break
+            x *= 2.0
+        a, b = (x / 2.0 if x > 1.0 else 0.0), 2.0 * x
+    if b > a:
+        x1, x2 = b - _GOLD * (b - a), a + _GOLD * (b - a)
+        for _ in range(24):
+            if (yield from phi(x1)) < (yield from phi(x2)):
+                a, x1, x2 = x1, x2, x1 + _GOLD * (b - x1)
+            else:
+                b, x2, x1 = x2, x1, x2 - _GOLD * (x2 - a)
+    s = max(seen, key=lambda k: (seen[k][0], -k))
+    return (s, *seen[s])
+
+
+def ray_search(phi):
+    """Maximise a concave phi over s >= 0: phi(x) -> (value, empty) is one evaluation; -> (s, value, empty)."""
+    steps = _ray_search_steps()
+    try:
+        x = next(steps)
+        while True:
+            x = steps.send(phi(x))
+    except StopIteration as done:
+        return done.value
+
+
+def ray_search_many(phi_many, S, skip=None):
+    """ray_search for S rays in lock-step: phi_many(scales (S,)) -> (values (S,), empties (S,)) is ONE batched
+    evaluation.  Every scenario keeps its own bracket, memo and phase (its own _ray_search_steps), so the distinct
+    scales it has evaluated, its chosen s and its value are exactly ray_search's on its phi alone; a scenario with
+    nothing new to ask in a round resubmits the last scale it asked for and the answer is ignored.  skip[s]: the
+    scenario takes s = 0 (its multipliers are zero: the ray is a point).
+    -> (s (S,), values (S,), empties (S,) int, batched evaluations)."""
+    skip = np.zeros(S, bool) if skip is None else np.asarray(skip, bool)
+    steps = [None if skip[s] else _ray_search_steps() for s in range(S)]
+    ask = np.zeros(S)                       # (a skipped scenario asks for 0 once)
+    done = [None] * S
+    for s, st in enumerate(steps):
+        if st is not None:
+            ask[s] = next(st)
+    rounds = 0
+    while any(d is None for d in done):
+        values, empties = phi_many(ask.copy())
+        rounds += 1
+        for s, st in enumerate(steps):
+            if done[s] is not None:
+                continue
+            got = (float(values[s]), int(empties[s]))
+            if st is None:
+                done[s] = (0.0, *got)
+                continue
+            try:
+                ask[s] = st.send(got)
+            except StopIteration as end:
+                done[s] = end.value
+    return (np.array([d[0] for d in done]), np.array([d[1] for d in done]),
+            np.array([d[2] for d in done], np.int64), rounds)
+
+
 @dataclass
 class Certificate:
     """lower <= optimum of the centralized problem (the MILP with on/off chargers, the LP otherwise); upper = the
@@ -186,33 +264,7 @@ class CertificateMixin:
             s = 1.0
             best, empty = self._bound_eval(d, y, s, integral)
         else:
-            seen = {}
-
-            def phi(x):
-                if x not in seen:
-                    seen[x] = self._bound_eval(d, y, x, integral)
-                return seen[x][0]
-            f0, f1 = phi(0.0), phi(1.0)
-            if math.isinf(f0):
-                a = b = 0.0
-            elif f1 <= f0:
-                a, b = 0.0, 1.0
-            else:
-                x = 1.0
-                for _ in range(60):
-                    if phi(2.0 * x) <= phi(x):
-                        break
-                    x *= 2.0
-                a, b = (x / 2.0 if x > 1.0 else 0.0), 2.0 * x
-            if b > a:
-                x1, x2 = b - _GOLD * (b - a), a + _GOLD * (b - a)
-                for _ in range(24):
-                    if phi(x1) < phi(x2):
-                        a, x1, x2 = x1, x2, x1 + _GOLD * (b - x1)
-                    else:
-                        b, x2, x1 = x2, x1, x2 - _GOLD * (x2 - a)
-            s = max(seen, key=lambda k: (seen[k][0], -k))
-            best, empty = seen[s]
+            s, best, empty = ray_search(lambda x: self._bound_eval(d, y, x, integral))
         # ---- supergradient ascent on lambda from s y ----
         # Polyak steps theta (upper - L) / |g|^2 along a supergradient g; upper overestimates the optimum (the
         # schedules are not optimal), so a step that does not raise the bound is taken back and theta halved

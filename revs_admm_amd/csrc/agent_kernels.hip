@@ -1280,36 +1280,47 @@ __device__ __forceinline__ int group_count(int v) {
     return v;
 }
 
+// Where one evaluation's data lie.  A single call reads contiguous arrays; scenario s of a batched call
+// (revs_dual_bound_many) reads record res S + s and columns s T + t of rows S T long.  Both kernels run the two bodies
+// below on such a view, so a scenario's arithmetic is the single call's, operation for operation.
+struct BoundView {
+    int64_t rec_stride, rec_off;       // record of residence i: homes[i rec_stride + rec_off]
+    int64_t col0, ld;                  // entry (row, t) of d, y, load_node: [row ld + col0 + t]
+    double scale;
+    double *scratch;                   // this evaluation's double[2 (T + nhb)]
+};
+
+// slot-wise terms (LOAD, rows) of slot t: one workgroup
+__device__ __forceinline__ void bound_slot_terms(const BoundArgs &a, const BoundView &v, int t) {
+    const int tid = threadIdx.x;
+    const double c = (double)a.cost[t];
+    double ld = 0.0, rw = 0.0;
+    for (int nn = tid; nn < a.m; nn += kBlock) {
+#pragma clang fp contract(off)
+        const int64_t o = (int64_t)nn * v.ld + v.col0 + t;
+        if (a.load_node) ld += (c + v.scale * (a.d ? a.d[o] : 0.0)) * a.load_node[o];
+        if (a.y) rw += fmax(a.vhi * a.y[o], a.vlo * a.y[o]);
+    }
+    block_sum2(ld, rw);
+    if (tid == 0) {
+        v.scratch[2 * t] = ld;
+        v.scratch[2 * t + 1] = -v.scale * rw;
+    }
+}
+
+// the minima of residence workgroup `bid` (residences bid (256 / LPA) ...): one workgroup
 template <int LPA, int SPL, bool INTEGRAL>
-__global__ __launch_bounds__(kBlock) void dual_bound_kernel(const BoundArgs a) {
+__device__ __forceinline__ void bound_residence_terms(const BoundArgs &a, const BoundView &v, int bid) {
     const int tid = threadIdx.x;
     const int T = a.T;
-    if ((int)blockIdx.x < T) {                     // slot-wise terms of slot t (uniform per workgroup)
-        const int t = (int)blockIdx.x;
-        const double c = (double)a.cost[t];
-        double ld = 0.0, rw = 0.0;
-        for (int nn = tid; nn < a.m; nn += kBlock) {
-#pragma clang fp contract(off)
-            const int64_t o = (int64_t)nn * T + t;
-            if (a.load_node) ld += (c + a.scale * (a.d ? a.d[o] : 0.0)) * a.load_node[o];
-            if (a.y) rw += fmax(a.vhi * a.y[o], a.vlo * a.y[o]);
-        }
-        block_sum2(ld, rw);
-        if (tid == 0) {
-            a.scratch[2 * t] = ld;
-            a.scratch[2 * t + 1] = -a.scale * rw;
-        }
-        return;
-    }
     constexpr int kHomesPerBlock = kBlock / LPA, kSlots = LPA * SPL, kNodeLoc = 4;
-    const int bid = (int)blockIdx.x - T;
     const int lig = tid & (LPA - 1);
     const int t0 = lig * SPL;
     const int64_t first = (int64_t)bid * kHomesPerBlock;
     const int64_t agent = first + tid / LPA;
     const bool live = agent < a.n;
     revs_home_t h;
-    if (live) h = a.homes[agent];
+    if (live) h = a.homes[agent * v.rec_stride + v.rec_off];
     else { h.ev = 0; h.start = 0; h.end = 0; h.nmin = 0; h.nmax = 0; h.rating = 0.f; h.capacity = 1.f; h.initial = 0.f; }
     const int node = live ? a.node_of[agent] : 0;
     const bool ev = live && h.ev != 0;
@@ -1323,8 +1334,8 @@ __global__ __launch_bounds__(kBlock) void dual_bound_kernel(const BoundArgs a) {
         const bool tv = t < T;
         win[j] = ev && tv && t >= h.start && t < h.end;
         const double c = tv ? (double)a.cost[t] : 0.0;
-        const double dn = (a.d && win[j]) ? a.d[(int64_t)node * T + t] : 0.0;
-        r[j] = (c + a.scale * dn) + 0.0;          // (+ 0.0: no -0 among the keys)
+        const double dn = (a.d && win[j]) ? a.d[(int64_t)node * v.ld + v.col0 + t] : 0.0;
+        r[j] = (c + v.scale * dn) + 0.0;          // (+ 0.0: no -0 among the keys)
         key[j] = win[j] ? r[j] : (double)INFINITY;
         nw += win[j] ? 1 : 0;
         nneg += (win[j] && r[j] < 0.0) ? 1 : 0;
@@ -1373,21 +1384,27 @@ __global__ __launch_bounds__(kBlock) void dual_bound_kernel(const BoundArgs a) {
         __syncthreads();
         for (int i = tid; i < kNodeLoc * kSlots; i += kBlock) {
             const int l = i / kSlots, t = i - l * kSlots;
-            const double v = nacc[l][t];
-            if (v != 0.0 && t < T && base + l < a.m) unsafeAtomicAdd(&a.p_node[(int64_t)(base + l) * T + t], v);
+            const double sum = nacc[l][t];
+            if (sum != 0.0 && t < T && base + l < a.m) unsafeAtomicAdd(&a.p_node[(int64_t)(base + l) * T + t], sum);
         }
     }
     block_sum2(val, cnt);
     if (tid == 0) {
-        a.scratch[2 * (T + bid)] = val;
-        a.scratch[2 * (T + bid) + 1] = cnt;
+        v.scratch[2 * (T + bid)] = val;
+        v.scratch[2 * (T + bid) + 1] = cnt;
     }
+}
+
+template <int LPA, int SPL, bool INTEGRAL>
+__global__ __launch_bounds__(kBlock) void dual_bound_kernel(const BoundArgs a) {
+    const BoundView v{1, 0, 0, a.T, a.scale, a.scratch};
+    if ((int)blockIdx.x < a.T) bound_slot_terms(a, v, (int)blockIdx.x);      // (uniform per workgroup)
+    else bound_residence_terms<LPA, SPL, INTEGRAL>(a, v, (int)blockIdx.x - a.T);
 }
 
 // out = {sum of the residences' minima, LOAD term, row term, residences with empty rows}: 256 threads, each folding a
 // fixed strided subset in order, then block_sum2 -- a fixed order whatever the number of workgroups.
-__global__ __launch_bounds__(kBlock) void dual_bound_finalize_kernel(const double *__restrict__ scratch, int32_t T,
-                                                                      int64_t nhb, double *out) {
+__device__ __forceinline__ void bound_finalize(const double *__restrict__ scratch, int32_t T, int64_t nhb, double *out) {
     double ld = 0.0, rw = 0.0, hv = 0.0, ec = 0.0;
     for (int t = threadIdx.x; t < T; t += kBlock) {
         ld += scratch[2 * t];
@@ -1407,6 +1424,39 @@ __global__ __launch_bounds__(kBlock) void dual_bound_finalize_kernel(const doubl
         out[2] = rw;
         out[3] = ec;
     }
+}
+
+__global__ __launch_bounds__(kBlock) void dual_bound_finalize_kernel(const double *__restrict__ scratch, int32_t T,
+                                                                      int64_t nhb, double *out) {
+    bound_finalize(scratch, T, nhb, out);
+}
+
+// ---- the bound of S scenarios of one feeder in one launch (revs_dual_bound_many) ------------------
+// Grid (T + nhb) x S: column s of the grid is revs_dual_bound's launch for scenario s -- the same workgroups over the
+// same residences, the same two partials each, in scratch[s] -- on the ensemble's layout: records [n][S], columns s T + t
+// of double[m][S T], one scale per scenario read from the device.  out[s] is therefore bit for bit what the single call
+// gives on contiguous copies of that scenario.  (a.scale and a.scratch are unused: the scenario's own are in the view;
+// a.p_node is NULL.)
+struct BoundManyArgs {
+    BoundArgs a;
+    int32_t S;
+    const double *scale;               // device double[S]
+};
+
+template <int LPA, int SPL, bool INTEGRAL>
+__global__ __launch_bounds__(kBlock) void dual_bound_many_kernel(const BoundManyArgs b) {
+    const BoundArgs &a = b.a;
+    const int s = (int)blockIdx.y;
+    const int64_t per = 2 * ((int64_t)a.T + a.nhb);
+    const BoundView v{b.S, s, (int64_t)s * a.T, (int64_t)b.S * a.T, b.scale[s], a.scratch + s * per};
+    if ((int)blockIdx.x < a.T) bound_slot_terms(a, v, (int)blockIdx.x);
+    else bound_residence_terms<LPA, SPL, INTEGRAL>(a, v, (int)blockIdx.x - a.T);
+}
+
+__global__ __launch_bounds__(kBlock) void dual_bound_many_finalize_kernel(const double *__restrict__ scratch, int32_t T,
+                                                                           int64_t nhb, double *out) {
+    const int64_t s = blockIdx.x;
+    bound_finalize(scratch + s * 2 * ((int64_t)T + nhb), T, nhb, out + 4 * s);
 }
 
 }  // namespace revs
@@ -1934,5 +1984,49 @@ extern "C" int revs_dual_bound(int64_t n_homes, int32_t T, const float *cost, co
     REVS_CHECK_LAUNCH("revs_dual_bound");
     hipLaunchKernelGGL(dual_bound_finalize_kernel, dim3(1), dim3(kBlock), 0, s, scratch, T, nhb, out);
     REVS_CHECK_LAUNCH("revs_dual_bound (finalize)");
+    return REVS_OK;
+}
+
+extern "C" int64_t revs_dual_bound_many_scratch(int64_t n_res, int32_t S, int32_t T) {
+    if (S < 1 || T <= 0 || T > REVS_MAX_T || (int64_t)S * T > REVS_ENS_MAX_COLS) return 0;
+    return S * revs_dual_bound_scratch(n_res, T);
+}
+
+extern "C" int revs_dual_bound_many(int64_t n_res, int32_t S, int32_t T, const float *cost, const revs_home_t *homes,
+                                    const int32_t *node_of, int32_t m, const double *d, const double *y,
+                                    const double *load_node, const double *scale, double vlo, double vhi,
+                                    int32_t integral, double *scratch, double *out, void *stream) {
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "revs_dual_bound_many: T=%d outside 1..%d", (int)T, REVS_MAX_T);
+    REVS_REQUIRE(S >= 1, "revs_dual_bound_many: S=%d scenarios (S >= 1 required)", (int)S);
+    REVS_REQUIRE((int64_t)S * T <= REVS_ENS_MAX_COLS, "revs_dual_bound_many: S*T=%lld columns exceed %d",
+                 (long long)S * T, REVS_ENS_MAX_COLS);
+    REVS_REQUIRE(n_res >= 0, "revs_dual_bound_many: n_res >= 0 required");
+    REVS_REQUIRE(m > 0, "revs_dual_bound_many: m > 0 required");
+    REVS_REQUIRE(cost, "revs_dual_bound_many: null pointer argument (cost)");
+    REVS_REQUIRE(scale, "revs_dual_bound_many: null pointer argument (scale)");
+    REVS_REQUIRE(scratch, "revs_dual_bound_many: null pointer argument (scratch)");
+    REVS_REQUIRE(out, "revs_dual_bound_many: null pointer argument (out)");
+    REVS_REQUIRE(n_res == 0 || homes, "revs_dual_bound_many: null pointer argument (homes)");
+    REVS_REQUIRE(n_res == 0 || node_of, "revs_dual_bound_many: null pointer argument (node_of)");
+    REVS_REQUIRE(!d || y, "revs_dual_bound_many: d = R y given without y");
+    REVS_REQUIRE(!y || d, "revs_dual_bound_many: y given without d = R y");
+    REVS_REQUIRE(vlo <= vhi, "revs_dual_bound_many: vlo > vhi");
+    const int64_t nhb = dual_bound_blocks(n_res, T);
+    REVS_REQUIRE(nhb + T < (int64_t)1 << 31, "revs_dual_bound_many: too many residences for one launch (n_res)");
+    BoundManyArgs b{{n_res, T, m, (int32_t)nhb, cost, homes, node_of, d, y, load_node, 0.0, vlo, vhi, scratch, nullptr},
+                    S, scale};
+    const Shape sh = pick_shape(T);
+    const dim3 grid((unsigned)(T + nhb), (unsigned)S);
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(LPA, SPL)                                                                                       \
+    do {                                                                                                     \
+        if (integral) hipLaunchKernelGGL((dual_bound_many_kernel<LPA, SPL, true>), grid, dim3(kBlock), 0, s, b); \
+        else hipLaunchKernelGGL((dual_bound_many_kernel<LPA, SPL, false>), grid, dim3(kBlock), 0, s, b);     \
+    } while (0)
+    REVS_FOR_SHAPE(sh, CALL);
+#undef CALL
+    REVS_CHECK_LAUNCH("revs_dual_bound_many");
+    hipLaunchKernelGGL(dual_bound_many_finalize_kernel, dim3((unsigned)S), dim3(kBlock), 0, s, scratch, T, nhb, out);
+    REVS_CHECK_LAUNCH("revs_dual_bound_many (finalize)");
     return REVS_OK;
 }

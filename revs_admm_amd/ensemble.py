@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from ._lib import HOME_DTYPE
 from .engine import AdmmEngine, OperatorOptions, _on_current_stream
+from .ensemble_certificate import EnsembleCertificateMixin
 
 # the ADMM forms of the operator QP (operator_admm.py) multiply by the dense factors of R: the dense products' column limit
 ADMM_FORM_MAX_COLS = _lib.MAX_T
@@ -43,7 +44,7 @@ def check_shape(S: int, T: int, group=None) -> None:
                          f"{_lib.ENS_MAX_COLS} (at most {_lib.ENS_MAX_COLS // T} scenarios at T = {T})")
 
 
-class AdmmEnsemble(AdmmEngine):
+class AdmmEnsemble(EnsembleCertificateMixin, AdmmEngine):
     """S ADMM runs on one feeder, side by side on one GPU.
 
     Parameters as AdmmEngine's, except
@@ -201,7 +202,8 @@ class AdmmEnsemble(AdmmEngine):
         return out
 
     def _one_schedule_only(self, *a, **k):
-        raise NotImplementedError("AdmmEnsemble: reports and certificates take one schedule -- pass result()[0][s] to "
+        raise NotImplementedError("AdmmEnsemble: this method takes one schedule -- every scenario's bound and certificate "
+                                  "come from lower_bounds() / certificates(); for reports pass result()[0][s] to "
                                   "study.study_report / network.network_report, or solve the scenario on an AdmmEngine")
 
     network_report = lower_bound = certificate = voltage = _one_schedule_only

@@ -153,11 +153,15 @@ def split_scenarios(S: int, T: int):
 
 
 def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
-                    vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None):
+                    vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None,
+                    return_certificates=False):
     """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
     `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
     DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
-    Every dict must hold every residence of the graph (KeyError) with LOADs of len(cost) slots (ValueError)."""
+    Every dict must hold every residence of the graph (KeyError) with LOADs of len(cost) slots (ValueError).
+    return_certificates=True: -> (solutions, certificates), one engine.Certificate per scenario in `homes_list` order
+    (AdmmEnsemble.certificates of every ensemble after its run: the schedules' cost, a dual bound below the centralized
+    optimum, the worst voltage row)."""
     from .ensemble import AdmmEnsemble
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]
     T = len(cost)
@@ -173,9 +177,9 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
         recs.append(rec)
     parts = split_scenarios(len(recs), T)
     if not parts:
-        return []
+        return ([], []) if return_certificates else []
     R_res, feeder = feeder if feeder is not None else feeder_of(graph)
-    out = []
+    out, certs = [], []
     for a, b in parts:
         shared = all(np.array_equal(loads[a], l) for l in loads[a + 1:b])
         eng = AdmmEnsemble(np.asarray(cost, float), recs[a:b], loads[a] if shared else np.stack(loads[a:b]),
@@ -188,8 +192,10 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
                         {h: P_sch[s, i].tolist() for i, h in enumerate(res)},
                         {h: S[s, i].tolist() for i, h in enumerate(res)},
                         {h: C[s, i].tolist() for i, h in enumerate(res)}))
+        if return_certificates:
+            certs += eng.certificates()
         del eng
-    return out
+    return (out, certs) if return_certificates else out
 
 
 def solve_residences(tariff, homes, device="cuda:0"):

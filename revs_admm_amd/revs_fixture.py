@@ -104,7 +104,7 @@ class REVS:
         return Pres, Pev, soc
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
-              methods=("distributed", "individual"), group_by="method", ensemble=False, **opt):
+              methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -123,7 +123,9 @@ class REVS:
         either the loading records are empty).  The feeder's matrix and tree are formed once.
         ensemble=True: the distributed scenarios of the grid are solved side by side (lpsolver.solve_ADMM_many, DESIGN.md
         section 3.9) instead of one engine after the other -- the same schedules to the operator's tolerance, not bit
-        for bit."""
+        for bit.  certify=True (with ensemble=True): labels[s]["certificate"] of every distributed scenario is its
+        engine.Certificate -- the schedule's cost, a dual bound below the centralized optimum and the gap between them,
+        all scenarios of an ensemble certified together (AdmmEnsemble.certificates)."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -132,6 +134,8 @@ class REVS:
         unknown += [m for m in methods if m not in ("distributed", "individual")]
         if unknown:
             raise ValueError(f"REVS.study: unknown group key or method {unknown[0]!r}")
+        if certify and not ensemble:
+            raise ValueError("REVS.study: certify=True certifies the scenarios of an ensemble together: pass ensemble=True")
         res = [n for n in dist if dist.nodes[n]["label"] == "H"]
         nonsub = [n for n in dist if dist.nodes[n]["label"] != "S"]
         pos = {n: i for i, n in enumerate(nonsub)}
@@ -165,7 +169,12 @@ class REVS:
             sols = solve_ADMM_many([h for _, h in deferred], dist, tariff, None, kappa=opt.get("kappa", 5.0),
                                    iter_max=opt.get("max_iterations", 15), vset=opt.get("v0", 1.03),
                                    vlow=opt.get("vlow", 0.95), vhigh=opt.get("vhigh", 1.05),
-                                   mode=opt.get("mode", "binary"), device=self.device, feeder=feeder)
+                                   mode=opt.get("mode", "binary"), device=self.device, feeder=feeder,
+                                   return_certificates=certify)
+            if certify:
+                sols, certs = sols
+                for (i, _), cert in zip(deferred, certs):
+                    labels[i]["certificate"] = cert
             for (i, _), sol in zip(deferred, sols):
                 profiles[i] = np.array([sol[1][h] for h in res], np.float64)
         combos = [tuple(lab[k] for k in keys) for lab in labels]
