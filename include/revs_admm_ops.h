@@ -5,7 +5,9 @@
  * binding needs revs_admm.h only.  They are exported because revs_admm_amd's Python driver issues them one by
  * one on its general paths (operator_admm.py: the ADMM forms of the operator QP; operator_newton.py: the chain
  * issued in phases, the Python Newton loop kept for comparison) and because the kernel-level parity tests
- * (tests/test_gpu_newton.py, test_gpu_operator.py) call each of them against its numpy restatement.
+ * (tests/test_gpu_newton.py, test_gpu_operator.py) call each of them against its numpy restatement.  The reports'
+ * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled) and
+ * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input).
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -522,6 +524,19 @@ int revs_net_study(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host
                    int32_t B, double *flow_out, double *loading_out, double *volt_out,
                    revs_net_summary_t *summary_out, revs_net_pooled_t *pooled_out, int32_t *band_count_out,
                    void *scratch, void *stream);
+
+/* revs_net_node_sums_many: revs_net_node_sums for the S scenarios of an ensemble in one launch, on the ensemble's own
+ * layout and straight into revs_net_study's input.  load (may be NULL) and p are float[n][S][T] -- element (i, s, t) at
+ * (i S + s) T + t, a residence's S T floats contiguous -- node_ptr as there (shared by the scenarios), node_g
+ * double[S][m][T]: node_g[s][node][t] = sum over the residences i of the node of (double) load[i][s][t] + (double)
+ * p[i][s][t].  One thread per (node, column s T + t), one accumulator from +0.0, the residences in ascending index, the
+ * widened pair added first: scenario s's slice carries the bits revs_net_node_sums gives on contiguous copies of
+ * scenario s's rows, and the same bits from call to call; a node without residences gives 0.0.  Writes S m T doubles
+ * from node_g on and nothing else: a caller that fills one study buffer from several ensembles passes
+ * node_g + s0 m T.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S, T outside 1..REVS_MAX_T, m outside
+ * 1..65535 (the report's limit), m S T >= 2^31, a null node_ptr, p or node_g. */
+int revs_net_node_sums_many(int32_t S, int32_t m, int32_t T, const int64_t *node_ptr, const float *load, const float *p,
+                            double *node_g, void *stream);
 
 #ifdef __cplusplus
 }

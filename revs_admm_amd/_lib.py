@@ -251,6 +251,7 @@ SIGNATURES = {
     "revs_plan_stream_run": (C.c_int, [_p, _i32, C.POINTER(StreamState), _f64, _f64, _p, _p, _p]),
     "revs_plan_status_flags": (_i32, [_p, _i32]),
     "revs_net_node_sums": (C.c_int, [_i32, _i32, _p, _p, _p, _p, _p]),
+    "revs_net_node_sums_many": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "revs_net_report": (C.c_int, [_i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _p, _p, _p, _p]),
     "revs_net_study_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_study": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _i32, _p,

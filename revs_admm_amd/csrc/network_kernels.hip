@@ -4,6 +4,7 @@
 //
 //   revs_net_node_sums   node_g[m][t] = sum over the homes of m of (double) load + (double) p, one thread per
 //                        (node, slot), the homes in ascending index, one accumulator: a fixed order
+//   revs_net_node_sums_many   the same sums for the S scenarios of an ensemble, float[n][S][T] -> double[S][m][T]
 //   revs_net_report      net_report_kernel<NT, IPT>, the four shapes of tree_shape()
 //
 // The scans are tree_scan's (tree_body.h), restated here with the two intermediate values kept that tree_scan
@@ -39,6 +40,29 @@ __global__ void net_node_sums_kernel(int m, int Ts, const int64_t *node_ptr, con
         for (int64_t i = i0; i < i1; ++i) acc += (double)p[i * Ts + t];
     }
     out[idx] = acc;
+}
+
+// The same sums on an ensemble's layout: load / p float[n][S][Ts] (a residence's S Ts floats contiguous), out
+// double[S][m][Ts], the study's.  One thread per (node, column c = s Ts + t), the column fastest: the reads are those
+// of net_node_sums_kernel over the (n, S Ts) view, the transposition is in the one store.  The same accumulator,
+// order and widening as above: scenario s's slice carries the bits of that kernel on scenario s's rows alone.
+__global__ void net_node_sums_many_kernel(int m, int S, int Ts, const int64_t *node_ptr, const float *load, const float *p,
+                                          double *out) {
+    const int cols = S * Ts;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= m * cols) return;
+    const int node = idx / cols, c = idx - node * cols;
+    const int s = c / Ts, t = c - s * Ts;
+    const int64_t i0 = node_ptr[node], i1 = node_ptr[node + 1];
+    double acc = 0.0;
+    if (load) {
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) acc += (double)load[i * cols + c] + (double)p[i * cols + c];
+    } else {
+#pragma unroll 4
+        for (int64_t i = i0; i < i1; ++i) acc += (double)p[i * cols + c];
+    }
+    out[((int64_t)s * m + node) * Ts + t] = acc;
 }
 
 struct NetArgs {
@@ -768,6 +792,23 @@ extern "C" int revs_net_node_sums(int32_t m, int32_t T, const int64_t *node_ptr,
     hipLaunchKernelGGL(net_node_sums_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        m, T, node_ptr, load, p, node_g);
     REVS_CHECK_LAUNCH("revs_net_node_sums");
+    return REVS_OK;
+}
+
+extern "C" int revs_net_node_sums_many(int32_t S, int32_t m, int32_t T, const int64_t *node_ptr, const float *load,
+                                       const float *p, double *node_g, void *stream) {
+    const char *who = "revs_net_node_sums_many";
+    REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
+    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
+    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "%s: m=%d outside 1..65535", who, (int)m);
+    const int64_t total = (int64_t)m * S * T;
+    REVS_REQUIRE(total < ((int64_t)1 << 31), "%s: m*S*T=%lld outputs, 2^31 or more", who, (long long)total);
+    REVS_REQUIRE(node_ptr, "%s: null pointer argument node_ptr", who);
+    REVS_REQUIRE(p, "%s: null pointer argument p", who);
+    REVS_REQUIRE(node_g, "%s: null pointer argument node_g", who);
+    hipLaunchKernelGGL(net_node_sums_many_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       m, S, T, node_ptr, load, p, node_g);
+    REVS_CHECK_LAUNCH(who);
     return REVS_OK;
 }
 

@@ -25,6 +25,7 @@ from . import _lib
 from ._lib import HOME_DTYPE
 from .engine import AdmmEngine, OperatorOptions, _on_current_stream
 from .ensemble_certificate import EnsembleCertificateMixin
+from .ensemble_report import EnsembleReportMixin
 
 # the ADMM forms of the operator QP (operator_admm.py) multiply by the dense factors of R: the dense products' column limit
 ADMM_FORM_MAX_COLS = _lib.MAX_T
@@ -44,7 +45,7 @@ def check_shape(S: int, T: int, group=None) -> None:
                          f"{_lib.ENS_MAX_COLS} (at most {_lib.ENS_MAX_COLS // T} scenarios at T = {T})")
 
 
-class AdmmEnsemble(EnsembleCertificateMixin, AdmmEngine):
+class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, AdmmEngine):
     """S ADMM runs on one feeder, side by side on one GPU.
 
     Parameters as AdmmEngine's, except
@@ -203,7 +204,8 @@ class AdmmEnsemble(EnsembleCertificateMixin, AdmmEngine):
 
     def _one_schedule_only(self, *a, **k):
         raise NotImplementedError("AdmmEnsemble: this method takes one schedule -- every scenario's bound and certificate "
-                                  "come from lower_bounds() / certificates(); for reports pass result()[0][s] to "
-                                  "study.study_report / network.network_report, or solve the scenario on an AdmmEngine")
+                                  "come from lower_bounds() / certificates(), every scenario's report from study_report() / "
+                                  "network_reports() (node_sums() for the sums alone); for one scenario's voltages solve "
+                                  "it on an AdmmEngine")
 
     network_report = lower_bound = certificate = voltage = _one_schedule_only

@@ -1,0 +1,95 @@
+"""Reports of an ensemble: every scenario's network report from the state on the device (revs_net_node_sums_many,
+DESIGN.md sections 3.7 - 3.9).  What network.py and study.py do for schedules held on the host, for the S scenarios of
+an AdmmEnsemble on the ensemble's own layout -- float[n][S][T], a residence's S T floats contiguous -- so no schedule
+is read back, turned into dicts and uploaded again: ONE launch sums every scenario's residences per node straight into
+revs_net_study's double[S][M][T], each scenario's slice bit for bit what revs_net_node_sums gives on that scenario
+alone, and one revs_net_study reports on all of them.  Methods of AdmmEnsemble (mixed in by ensemble.py); nothing here
+touches the run's state."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import study
+from ._lib import check, ptr
+from .network import NetworkReport
+
+
+class EnsembleReportMixin:
+    def _report_profile(self, profile):
+        """The profile as a contiguous float32 tensor of n S T elements in the engine's residence order."""
+        n, S, T = self.n_res, self.S_count, self.T_slot
+        if profile is None:
+            return self.P_sch
+        if isinstance(profile, torch.Tensor):
+            # (the three views the engine itself takes of a residence-side array)
+            if (profile.dtype != torch.float32 or not profile.is_contiguous() or profile.device != self.P_sch.device
+                    or tuple(profile.shape) not in ((n, S, T), (n * S, T), (n, S * T))):
+                raise ValueError(f"node_sums: a profile on the device must be a contiguous float32 ({n}, {S}, {T}) tensor "
+                                 f"on {self.dev} in the engine's residence order, got {tuple(profile.shape)} "
+                                 f"{profile.dtype} on {profile.device}")
+            return profile
+        a = np.asarray(profile, np.float32)
+        if a.shape != (S, n, T):
+            raise ValueError(f"node_sums: a profile on the host must be (S, n, T) = {(S, n, T)} in the caller's "
+                             f"residence order, got {a.shape}")
+        return self._up(a.transpose(1, 0, 2)[self.perm])
+
+    def node_sums(self, profile=None, add_load=False, out=None) -> torch.Tensor:
+        """Every scenario's profile summed over each node's residences -> (S, M, T) float64 on the device, scenario s's
+        slice bit for bit revs_net_node_sums on that scenario alone (one launch: revs_net_node_sums_many).
+
+        profile   None: the schedules P_sch -- the residences' net load g = LOAD + p, what REVS.study reports.  Else a
+                  contiguous float32 (n, S, T) tensor on the engine's device in the engine's residence order (the
+                  layout of P_sch, S and load), or a numpy (S, n, T) array in the caller's order.
+        add_load  True: the engine's LOAD is added to the profile, residence by residence before the sum -- for an
+                  EV-only profile such as the charger powers S.
+        out       where the sums go: a contiguous (S, M, T) float64 tensor on the device, e.g. the slice [s0:s0 + S] of
+                  a larger study buffer; nothing outside it is written.  None: a new tensor."""
+        S, M, T = self.S_count, self.M, self.T_slot
+        prof = self._report_profile(profile)
+        if out is None:
+            out = torch.empty(S, M, T, dtype=torch.float64, device=self.dev)
+        elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (S, M, T)
+              or not out.is_contiguous() or out.device != self.P_sch.device):
+            raise ValueError(f"node_sums: out must be a contiguous float64 {(S, M, T)} tensor on {self.dev}")
+        if not self.n_res:
+            return out.zero_()
+        check(self.lib.revs_net_node_sums_many(S, M, T, ptr(self.node_ptr), ptr(self.load) if add_load else None,
+                                               ptr(prof), ptr(out), self.stream), "revs_net_node_sums_many")
+        return out
+
+    def _report_tree(self):
+        if self._tree is None:
+            raise ValueError("network_report needs the feeder as a tree: pass feeder=(parent, edge_r, cons_of) to "
+                             "AdmmEngine (without it the engine recovers one from Rn only for the Newton operator "
+                             "up to 4096 rows, and only when Rn is a radial feeder's matrix)")
+        return self._tree, self._tree_host, self._tree_nodes
+
+    def study_report(self, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98), arrays=False, profile=None,
+                     add_load=False, vset=None, vmin=None, vmax=None) -> study.StudyReport:
+        """study.study_report of the S scenarios from the state on the device -> StudyReport: per-scenario summaries and
+        band counts, box-plot numbers pooled over `groups`, with arrays=True flow / loading / volt of every scenario
+        (groups, rating, nodes, bands, arrays: see study.study_report; tree nodes are those of feeder=, as
+        AdmmEngine.network_report's).  profile / add_load: see node_sums -- the default reports P_sch alone.
+        vset / vmin / vmax default to the constructor's vset / vlow / vhigh, as network_report's.  One node-sum launch
+        and one revs_net_study; the records and StudyReport.node_p (S, M, T) are read back.  The run's state is read,
+        never written."""
+        bands, gid, _ = study.check_study_args(self.S_count, bands, groups)      # (before anything is launched)
+        tree, tree_host, n_nodes = self._report_tree()
+        node_g = self.node_sums(profile, add_load)
+        return study.study_report_device(node_g, tree=(tree, tree_host, n_nodes), groups=None if groups is None else gid,
+                                         rating=rating, nodes=nodes, bands=bands,
+                                         vset=self.vset if vset is None else vset,
+                                         vmin=self.vlow if vmin is None else vmin,
+                                         vmax=self.vhigh if vmax is None else vmax, arrays=arrays, lib=self.lib,
+                                         stream=self.stream)
+
+    def network_reports(self, rating=None, nodes=None, arrays=True, profile=None, add_load=False) -> list:
+        """AdmmEngine.network_report for every scenario -> S NetworkReports, from study_report's single launch without
+        pools and bands (revs_net_study gives every scenario the bits of revs_net_report on it alone)."""
+        rep = self.study_report(None, rating, nodes, (), arrays, profile, add_load)
+        pick = lambda a, s: None if a is None else a[s]
+        return [NetworkReport(pick(rep.flow, s), pick(rep.loading, s), pick(rep.volt, s), rep.summary_loading[s],
+                              rep.summary_volt[s], rep.node_p[s], rep.vset, rep.vmin, rep.vmax)
+                for s in range(self.S_count)]

@@ -154,14 +154,20 @@ def split_scenarios(S: int, T: int):
 
 def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
                     vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None,
-                    return_certificates=False):
+                    return_certificates=False, return_node_sums=False):
     """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
     `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
     DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
     Every dict must hold every residence of the graph (KeyError) with LOADs of len(cost) slots (ValueError).
     return_certificates=True: -> (solutions, certificates), one engine.Certificate per scenario in `homes_list` order
     (AdmmEnsemble.certificates of every ensemble after its run: the schedules' cost, a dual bound below the centralized
-    optimum, the worst voltage row)."""
+    optimum, the worst voltage row).
+    return_node_sums=True: -> (solutions, node_g), or (solutions, certificates, node_g) with return_certificates: ONE
+    (len(homes_list), M, T) float64 tensor on the device, scenario s's schedule P_sch summed over every row's
+    residences (M rows, one per residence here), in `homes_list` order -- study.study_report_device's input.  Every
+    ensemble fills its slice from its state (AdmmEnsemble.node_sums(out=)) before it is released; an empty list gives
+    an empty tensor."""
+    import torch
     from .ensemble import AdmmEnsemble
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]
     T = len(cost)
@@ -176,10 +182,16 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
         loads.append(load)
         recs.append(rec)
     parts = split_scenarios(len(recs), T)
+
+    def answer(out, certs, node_g):
+        extra = ((certs,) if return_certificates else ()) + ((node_g,) if return_node_sums else ())
+        return (out,) + extra if extra else out
+
     if not parts:
-        return ([], []) if return_certificates else []
+        return answer([], [], torch.empty(0, len(res), T, dtype=torch.float64, device=device)
+                      if return_node_sums else None)
     R_res, feeder = feeder if feeder is not None else feeder_of(graph)
-    out, certs = [], []
+    out, certs, node_g = [], [], None
     for a, b in parts:
         shared = all(np.array_equal(loads[a], l) for l in loads[a + 1:b])
         eng = AdmmEnsemble(np.asarray(cost, float), recs[a:b], loads[a] if shared else np.stack(loads[a:b]),
@@ -194,8 +206,12 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
                         {h: C[s, i].tolist() for i, h in enumerate(res)}))
         if return_certificates:
             certs += eng.certificates()
+        if return_node_sums:
+            if node_g is None:
+                node_g = torch.empty(len(recs), eng.M, T, dtype=torch.float64, device=eng.dev)
+            eng.node_sums(out=node_g[a:b])
         del eng
-    return (out, certs) if return_certificates else out
+    return answer(out, certs, node_g)
 
 
 def solve_residences(tariff, homes, device="cuda:0"):

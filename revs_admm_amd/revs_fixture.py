@@ -104,7 +104,8 @@ class REVS:
         return Pres, Pev, soc
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
-              methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, **opt):
+              methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
+              **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -125,7 +126,12 @@ class REVS:
         section 3.9) instead of one engine after the other -- the same schedules to the operator's tolerance, not bit
         for bit.  certify=True (with ensemble=True): labels[s]["certificate"] of every distributed scenario is its
         engine.Certificate -- the schedule's cost, a dual bound below the centralized optimum and the gap between them,
-        all scenarios of an ensemble certified together (AdmmEnsemble.certificates)."""
+        all scenarios of an ensemble certified together (AdmmEnsemble.certificates).  device_report=True (with
+        ensemble=True): the distributed scenarios' rows of the report's input never leave the device -- every ensemble
+        sums its schedules per row from its own state (solve_ADMM_many(return_node_sums=True)), the individual methods'
+        profiles are uploaded as the float64 values they are, the (S, M, T) buffer is assembled on the device in label
+        order and reported by study.study_report_device; labels, groups and every report field keep their meaning
+        (StudyReport.node_p is the buffer read back)."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -136,6 +142,8 @@ class REVS:
             raise ValueError(f"REVS.study: unknown group key or method {unknown[0]!r}")
         if certify and not ensemble:
             raise ValueError("REVS.study: certify=True certifies the scenarios of an ensemble together: pass ensemble=True")
+        if device_report and not ensemble:
+            raise ValueError("REVS.study: device_report=True reports from the state of an ensemble: pass ensemble=True")
         res = [n for n in dist if dist.nodes[n]["label"] == "H"]
         nonsub = [n for n in dist if dist.nodes[n]["label"] != "S"]
         pos = {n: i for i, n in enumerate(nonsub)}
@@ -170,15 +178,31 @@ class REVS:
                                    iter_max=opt.get("max_iterations", 15), vset=opt.get("v0", 1.03),
                                    vlow=opt.get("vlow", 0.95), vhigh=opt.get("vhigh", 1.05),
                                    mode=opt.get("mode", "binary"), device=self.device, feeder=feeder,
-                                   return_certificates=certify)
+                                   return_certificates=certify, return_node_sums=device_report)
+            node_g = None
+            if device_report:                    # (solutions[, certificates], node sums)
+                *head, node_g = sols
+                sols = tuple(head) if certify else head[0]
             if certify:
                 sols, certs = sols
                 for (i, _), cert in zip(deferred, certs):
                     labels[i]["certificate"] = cert
-            for (i, _), sol in zip(deferred, sols):
-                profiles[i] = np.array([sol[1][h] for h in res], np.float64)
+            for k, ((i, _), sol) in enumerate(zip(deferred, sols)):
+                profiles[i] = node_g[k] if device_report else np.array([sol[1][h] for h in res], np.float64)
         combos = [tuple(lab[k] for k in keys) for lab in labels]
         order = list(dict.fromkeys(combos))
+        if device_report:
+            import torch
+            # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
+            buf = torch.empty(len(profiles), len(res), len(tariff), dtype=torch.float64, device=self.device)
+            for s, prof in enumerate(profiles):
+                buf[s].copy_(prof if isinstance(prof, torch.Tensor) else torch.from_numpy(prof))
+            rep = st.study_report_device(buf, feeder=(parent, edge_r, cons_of), groups=[order.index(c) for c in combos],
+                                         rating=node_rating, nodes=[pos[h] for h in community],
+                                         bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
+                                         vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
+                                         arrays=opt.get("arrays", False))
+            return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
                               bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),

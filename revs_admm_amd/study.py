@@ -72,44 +72,70 @@ class StudyReport:
         return lo, hi
 
 
-def native_study(parent, edge_r, cons_of, node_p, groups, n_groups, bands, rating, nodes, vset, vmin, vmax, arrays,
-                 device) -> StudyReport:
-    """revs_net_study on checked arguments: node_p (S, M, T) float64, groups (S,) int32 in -1 .. n_groups - 1.  The
-    one place the library is called from (a host test puts tests/study_ref.py here)."""
-    from .engine import _dev_check
-    lib, dev = _lib.load(), _dev_check(device)
-    S, M, T = node_p.shape
-    n, B, G = len(parent), len(bands), int(n_groups)
-    with torch.cuda.device(dev):
-        th, tree, _keep = tree_on_device(dev, parent, edge_r, cons_of, M)
-        d_nop, d_rating, d_mask = side_arrays(dev, th, n, rating, nodes)
-        g = torch.from_numpy(node_p).to(dev)
-        out = [torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays else [None] * 3
-        d_sum = torch.zeros(S * 2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        d_pool = d_scratch = d_band = None
-        if G:                                   # staging only when pools are asked for
-            d_pool = torch.zeros(G * 2 * T * POOLED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            nbytes = int(lib.revs_net_study_scratch(S, T, th["n"]))
-            if nbytes <= 0:
-                raise ValueError(f"study report: no staging size for S={S}, T={T}, tree of {th['n']}")
-            d_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-        if B:
-            d_band = torch.zeros(S, T, B, dtype=torch.int32, device=dev)
-        h_group = np.ascontiguousarray(groups, np.int32)
-        h_band = np.ascontiguousarray(bands, np.float64)
-        check(lib.revs_net_study(S, M, T, C.byref(tree), ptr(g), ptr(d_rating), ptr(d_mask), ptr(d_nop), n, float(vset),
-                                 float(vmin), float(vmax), h_group.ctypes.data if G else None, G,
-                                 h_band.ctypes.data if B else None, B, ptr(out[0]), ptr(out[1]), ptr(out[2]),
-                                 ptr(d_sum), ptr(d_pool), ptr(d_band), ptr(d_scratch),
-                                 torch.cuda.current_stream(dev).cuda_stream), "revs_net_study")
-        rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, 2, T)
-        pool = (d_pool.cpu().numpy().view(POOLED_DTYPE).reshape(G, 2, T) if G
-                else np.zeros((0, 2, T), POOLED_DTYPE))
-        counts = d_band.cpu().numpy() if B else np.zeros((S, T, 0), np.int32)
-        flow, loading, volt = (None if o is None else o.cpu().numpy() for o in out)
+def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, groups, n_groups, bands, rating, nodes, vset,
+                        vmin, vmax, arrays) -> StudyReport:
+    """revs_net_study on node sums that lie on the device: node_g (S, M, T) float64 device tensor, tree: _lib.Tree (device
+    pack / w), tree_host: the dict of feeder_tree, n_nodes: its nodes before padding; groups (S,) int32 in
+    -1 .. n_groups - 1.  The one place the library is called from (a host test puts tests/study_ref.py here); the
+    records and the S M T node sums are read back."""
+    S, M, T = node_g.shape
+    n, B, G = int(n_nodes), len(bands), int(n_groups)
+    d_nop, d_rating, d_mask = side_arrays(dev, tree_host, n, rating, nodes)
+    out = [torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays else [None] * 3
+    d_sum = torch.zeros(S * 2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_pool = d_scratch = d_band = None
+    if G:                                   # staging only when pools are asked for
+        d_pool = torch.zeros(G * 2 * T * POOLED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        nbytes = int(lib.revs_net_study_scratch(S, T, tree_host["n"]))
+        if nbytes <= 0:
+            raise ValueError(f"study report: no staging size for S={S}, T={T}, tree of {tree_host['n']}")
+        d_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    if B:
+        d_band = torch.zeros(S, T, B, dtype=torch.int32, device=dev)
+    h_group = np.ascontiguousarray(groups, np.int32)
+    h_band = np.ascontiguousarray(bands, np.float64)
+    check(lib.revs_net_study(S, M, T, C.byref(tree), ptr(node_g), ptr(d_rating), ptr(d_mask), ptr(d_nop), n, float(vset),
+                             float(vmin), float(vmax), h_group.ctypes.data if G else None, G,
+                             h_band.ctypes.data if B else None, B, ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                             ptr(d_sum), ptr(d_pool), ptr(d_band), ptr(d_scratch), stream), "revs_net_study")
+    rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, 2, T)
+    pool = (d_pool.cpu().numpy().view(POOLED_DTYPE).reshape(G, 2, T) if G
+            else np.zeros((0, 2, T), POOLED_DTYPE))
+    counts = d_band.cpu().numpy() if B else np.zeros((S, T, 0), np.int32)
+    flow, loading, volt = (None if o is None else o.cpu().numpy() for o in out)
     return StudyReport(rec[:, 0].copy(), rec[:, 1].copy(), pool[:, 0].copy(), pool[:, 1].copy(), counts,
                        tuple(float(b) for b in bands), np.asarray(groups, np.int64).copy(), flow, loading, volt,
-                       node_p, float(vset), float(vmin), float(vmax))
+                       node_g.cpu().numpy(), float(vset), float(vmin), float(vmax))
+
+
+def native_study(parent, edge_r, cons_of, node_p, groups, n_groups, bands, rating, nodes, vset, vmin, vmax, arrays,
+                 device) -> StudyReport:
+    """revs_net_study on checked arguments held on the host: node_p (S, M, T) float64, groups (S,) int32 in
+    -1 .. n_groups - 1 -- the whole feeder's tree built and the profiles uploaded, then native_study_device."""
+    from .engine import _dev_check
+    lib, dev = _lib.load(), _dev_check(device)
+    with torch.cuda.device(dev):
+        th, tree, _keep = tree_on_device(dev, parent, edge_r, cons_of, node_p.shape[1])
+        g = torch.from_numpy(node_p).to(dev)
+        rep = native_study_device(lib, dev, torch.cuda.current_stream(dev).cuda_stream, tree, th, len(parent), g, groups,
+                                  n_groups, bands, rating, nodes, vset, vmin, vmax, arrays)
+    rep.node_p = node_p
+    return rep
+
+
+def check_study_args(S, bands, groups):
+    """study_report's checks of S, bands and groups -> (bands, group ids int32 (S,), G)."""
+    if not 1 <= S <= _lib.STUDY_MAX_S:
+        raise ValueError(f"study report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    bands = tuple(float(b) for b in bands)
+    if len(bands) > _lib.STUDY_MAX_BANDS or not np.isfinite(bands).all():
+        raise ValueError(f"study report: at most {_lib.STUDY_MAX_BANDS} finite bands, got {bands}")
+    if groups is None:
+        return bands, np.full(S, -1, np.int32), 0
+    gid = np.asarray(groups)
+    if gid.shape != (S,) or not np.issubdtype(gid.dtype, np.integer) or gid.min() < -1:
+        raise ValueError(f"study report: groups must be {S} integers >= -1")
+    return bands, gid.astype(np.int32), int(gid.max()) + 1
 
 
 def study_report(parent, edge_r, cons_of, node_p, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98),
@@ -127,17 +153,40 @@ def study_report(parent, edge_r, cons_of, node_p, groups=None, rating=None, node
     node_p = np.ascontiguousarray(node_p, np.float64)
     if node_p.ndim != 3:
         raise ValueError(f"study report: node_p must be (scenarios, rows, slots), got {node_p.shape}")
-    S = node_p.shape[0]
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"study report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    bands = tuple(float(b) for b in bands)
-    if len(bands) > _lib.STUDY_MAX_BANDS or not np.isfinite(bands).all():
-        raise ValueError(f"study report: at most {_lib.STUDY_MAX_BANDS} finite bands, got {bands}")
-    if groups is None:
-        gid, G = np.full(S, -1, np.int32), 0
-    else:
-        gid = np.asarray(groups)
-        if gid.shape != (S,) or not np.issubdtype(gid.dtype, np.integer) or gid.min() < -1:
-            raise ValueError(f"study report: groups must be {S} integers >= -1")
-        gid, G = gid.astype(np.int32), int(gid.max()) + 1
+    bands, gid, G = check_study_args(node_p.shape[0], bands, groups)
     return native_study(parent, edge_r, cons_of, node_p, gid, G, bands, rating, nodes, vset, vmin, vmax, arrays, device)
+
+
+def study_report_device(node_g, feeder=None, tree=None, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98),
+                        vset=1.0, vmin=0.95, vmax=1.05, arrays=False, lib=None, stream=None) -> StudyReport:
+    """study_report over node sums that lie on the device: node_g a contiguous (S, M, T) float64 tensor, row
+    cons_of[i] of scenario s injected at tree node i (what AdmmEnsemble.node_sums / revs_net_node_sums_many write).
+    The feeder comes as feeder=(parent, edge_r, cons_of), study_report's first three arguments -- its tree is built
+    and uploaded here -- or as tree=(_lib.Tree, the dict of feeder_tree, nodes before padding) where it already lies
+    on node_g's device (an engine's).  Every other argument and check as study_report's; nothing is uploaded but the
+    side arrays, and StudyReport.node_p is node_g read back.  lib / stream: the library and the HIP stream of the
+    launch (default: the loaded one, torch's current stream)."""
+    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() != 3 \
+            or not node_g.is_contiguous():
+        raise ValueError("study report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
+    if (feeder is None) == (tree is None):
+        raise ValueError("study report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
+    bands, gid, G = check_study_args(node_g.shape[0], bands, groups)
+    dev = node_g.device
+
+    def run():
+        if tree is None:
+            th, tr, _keep = tree_on_device(dev, *feeder, node_g.shape[1])
+            n_nodes = len(feeder[0])
+        else:
+            tr, th, n_nodes = tree
+        st = stream
+        if st is None and dev.type == "cuda":
+            st = torch.cuda.current_stream(dev).cuda_stream
+        return native_study_device(lib or _lib.load(), dev, st, tr, th, n_nodes, node_g, gid, G, bands, rating, nodes,
+                                   vset, vmin, vmax, arrays)
+
+    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
+        return run()
+    with torch.cuda.device(dev):
+        return run()
