@@ -6,8 +6,9 @@
  * one on its general paths (operator_admm.py: the ADMM forms of the operator QP; operator_newton.py: the chain
  * issued in phases, the Python Newton loop kept for comparison) and because the kernel-level parity tests
  * (tests/test_gpu_newton.py, test_gpu_operator.py) call each of them against its numpy restatement.  The reports'
- * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled) and
- * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input).
+ * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled),
+ * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input)
+ * and revs_net_across (per node and per line, the statistics across the scenarios of a group).
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -537,6 +538,50 @@ int revs_net_study(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host
  * 1..65535 (the report's limit), m S T >= 2^31, a null node_ptr, p or node_g. */
 int revs_net_node_sums_many(int32_t S, int32_t m, int32_t T, const int64_t *node_ptr, const float *load, const float *p,
                             double *node_g, void *stream);
+
+/* ---- study report, per node and per line: statistics of every cell ACROSS the scenarios of a group ------------------
+ * The records above summarise over the feeder; these say WHERE: for every node (line) n and slot t, the box-plot numbers
+ * of values[s][n][t] over the scenarios s of group g, how many of them violate [lo, hi] and how many reach each band.
+ * Quantiles do not compose: they are selected exactly from all members' values of the cell (csrc/across_kernels.hip).
+ *
+ * values: device double[S][n_out][T], revs_net_study's volt_out (lo = vmin, hi = vmax, sense = -1) or loading_out
+ * (lo = -inf, hi = 1, sense = +1); any double is allowed, -0.0 orders and is reported as +0.0.  group / G / band / B as
+ * revs_net_study's (HOST arrays), keep: device uint8[n_out] or NULL (every cell).  One cell's record, over the members
+ * of the group in ascending scenario index: a NaN counts in n_nan and is left out of everything else; min .. max are
+ * numpy.percentile's (linear, rank (count - 1) e / 4, the roundings of the other summaries); mean is the sum from +0.0
+ * in that order divided by count; worst_scenario has the largest max(lo - v, v - hi), the lowest scenario on ties;
+ * band_count[b] members have v <= band[b] (sense < 0) or v >= band[b] (sense > 0), entries b >= B are 0.  With
+ * count == 0 every double is a NaN, worst_scenario -1 and the other integers 0; a cell with keep[n] == 0 gets that
+ * record with n_nan 0 too.  Every byte of every output is written.  An INFINITY among a cell's values follows
+ * numpy.percentile as well: all five of min .. max are interpolated as a + (b - a) t, min and max with t = 0, so a
+ * statistic whose neighbour (or itself) is infinite is a NaN although count > 0 -- a lone +inf gives five NaNs,
+ * {1, +inf} gives min = max = NaN.  For finite values min and max are the smallest and the largest value themselves.
+ *   slot_out      revs_net_across_t[G][n_out][T]: the record of values[s][n][t]
+ *   daily_out     revs_net_across_t[G][n_out]: the record of the members' daily extremes d_s = min over t (sense < 0) /
+ *                 max over t (sense > 0) of values[s][n][t], a NaN if any slot is one (numpy.min / numpy.max) -- written
+ *                 once into `scratch` as double[S][n_out] and summarised by the same kernel as its T = 1 case
+ *   exposure_out  int32[G][n_out]: the (member, slot) pairs with v < lo or v > hi: the sum over t of slot_out's
+ *                 n_violations
+ * Any output may be NULL, not all.  Reads values and keep, writes the outputs and the scratch.  REVS_EINVAL before any
+ * launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; n_out outside 1..65535; S n_out T >= 2^31; G outside
+ * 1..S; group NULL; a group id outside -1..G-1; B outside 0..8; band NULL with B > 0; a threshold that is not finite;
+ * sense not -1 / +1; lo > hi or a NaN in either; values NULL; every output NULL; daily_out or exposure_out without a
+ * 16-byte aligned scratch of revs_net_across_scratch bytes (8 S n_out; 0 for a bad size). */
+#define REVS_ACROSS_MAX_BANDS 8
+typedef struct {
+    double min, q1, median, q3, max;  /* over the group's non-NaN values of the cell; numpy.percentile, linear
+                                         (NaN beside an infinite value, as numpy's: see above) */
+    double mean;                      /* sum in ascending scenario order from +0.0, divided by count */
+    int32_t count, n_nan;             /* group members with a value / with a NaN */
+    int32_t n_violations;             /* members with v < lo or v > hi */
+    int32_t worst_scenario;           /* largest max(lo - v, v - hi); the lowest scenario on ties; -1: count == 0 */
+    int32_t band_count[8];            /* members with v <= band[b] (sense < 0) or v >= band[b] (sense > 0); rest 0 */
+} revs_net_across_t;                  /* 96 bytes */
+int64_t revs_net_across_scratch(int32_t S, int32_t n_out);
+int revs_net_across(int32_t S, int32_t n_out, int32_t T, const double *values, const uint8_t *keep, const int32_t *group,
+                    int32_t G, double lo, double hi, int32_t sense, const double *band, int32_t B,
+                    revs_net_across_t *slot_out, revs_net_across_t *daily_out, int32_t *exposure_out, void *scratch,
+                    void *stream);
 
 #ifdef __cplusplus
 }

@@ -124,6 +124,13 @@ STREAM_BLOCK_MAX = 256   # REVS_STREAM_BLOCK_MAX
 AGENT_MAX_INNER = 32     # REVS_AGENT_MAX_INNER
 STUDY_MAX_S = 4096       # REVS_STUDY_MAX_S
 STUDY_MAX_BANDS = 8      # REVS_STUDY_MAX_BANDS
+ACROSS_MAX_BANDS = 8     # REVS_ACROSS_MAX_BANDS
+
+# numpy mirror of revs_net_across_t (include/revs_admm_ops.h)
+ACROSS_DTYPE = np.dtype([("min", "<f8"), ("q1", "<f8"), ("median", "<f8"), ("q3", "<f8"), ("max", "<f8"), ("mean", "<f8"),
+                         ("count", "<i4"), ("n_nan", "<i4"), ("n_violations", "<i4"), ("worst_scenario", "<i4"),
+                         ("band_count", "<i4", (ACROSS_MAX_BANDS,))])
+assert ACROSS_DTYPE.itemsize == 96
 
 
 class RevsError(RuntimeError):
@@ -256,6 +263,8 @@ SIGNATURES = {
     "revs_net_study_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_study": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _f64, _f64, _f64, _p, _i32, _p,
                                  _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_across_scratch": (_i64, [_i32, _i32]),
+    "revs_net_across": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _i32, _f64, _f64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -205,7 +205,7 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, AdmmEngine):
     def _one_schedule_only(self, *a, **k):
         raise NotImplementedError("AdmmEnsemble: this method takes one schedule -- every scenario's bound and certificate "
                                   "come from lower_bounds() / certificates(), every scenario's report from study_report() / "
-                                  "network_reports() (node_sums() for the sums alone); for one scenario's voltages solve "
-                                  "it on an AdmmEngine")
+                                  "network_reports() (node_sums() for the sums alone), every scenario's voltages from "
+                                  "voltages()")
 
     network_report = lower_bound = certificate = voltage = _one_schedule_only

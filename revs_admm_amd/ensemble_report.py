@@ -7,12 +7,14 @@ alone, and one revs_net_study reports on all of them.  Methods of AdmmEnsemble (
 touches the run's state."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
 from . import study
 from ._lib import check, ptr
-from .network import NetworkReport
+from .network import NetworkReport, side_arrays
 
 
 class EnsembleReportMixin:
@@ -67,14 +69,16 @@ class EnsembleReportMixin:
         return self._tree, self._tree_host, self._tree_nodes
 
     def study_report(self, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98), arrays=False, profile=None,
-                     add_load=False, vset=None, vmin=None, vmax=None) -> study.StudyReport:
+                     add_load=False, vset=None, vmin=None, vmax=None, across=False) -> study.StudyReport:
         """study.study_report of the S scenarios from the state on the device -> StudyReport: per-scenario summaries and
         band counts, box-plot numbers pooled over `groups`, with arrays=True flow / loading / volt of every scenario
         (groups, rating, nodes, bands, arrays: see study.study_report; tree nodes are those of feeder=, as
         AdmmEngine.network_report's).  profile / add_load: see node_sums -- the default reports P_sch alone.
         vset / vmin / vmax default to the constructor's vset / vlow / vhigh, as network_report's.  One node-sum launch
-        and one revs_net_study; the records and StudyReport.node_p (S, M, T) are read back.  The run's state is read,
-        never written."""
+        and one revs_net_study; the records and StudyReport.node_p (S, M, T) are read back.  across=True (with groups):
+        StudyReport.across, per node and per line the statistics across each group's scenarios, from the arrays on the
+        device (study.across_report_device).  The run's state is read, never written."""
+        study.check_across_groups(across, groups)
         bands, gid, _ = study.check_study_args(self.S_count, bands, groups)      # (before anything is launched)
         tree, tree_host, n_nodes = self._report_tree()
         node_g = self.node_sums(profile, add_load)
@@ -83,7 +87,33 @@ class EnsembleReportMixin:
                                          vset=self.vset if vset is None else vset,
                                          vmin=self.vlow if vmin is None else vmin,
                                          vmax=self.vhigh if vmax is None else vmax, arrays=arrays, lib=self.lib,
-                                         stream=self.stream)
+                                         stream=self.stream, across=across)
+
+    def voltages(self, profile=None, add_load=False, nodes=None, vset=None, out=None) -> torch.Tensor:
+        """Every scenario's node voltages -> (S, nodes, T) float64 on the device, scenario s bit for bit
+        network_reports()[s].volt: one node-sum launch and one revs_net_study with volt_out alone; nothing is read
+        back.  profile / add_load: see node_sums; vset defaults to the constructor's.  nodes: None, every tree node of
+        feeder= in its order; else the node indices wanted, gathered on the device.  out: a contiguous float64 tensor
+        of the result's shape on the device to write into (with nodes=None the launch writes it directly)."""
+        tree, tree_host, n_nodes = self._report_tree()
+        S, T = self.S_count, self.T_slot
+        idx = None if nodes is None else torch.as_tensor(np.asarray(nodes, np.int64), device=self.dev)
+        shape = (S, n_nodes if idx is None else len(idx), T)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64
+                                or tuple(out.shape) != shape or not out.is_contiguous()
+                                or out.device != self.P_sch.device):
+            raise ValueError(f"voltages: out must be a contiguous float64 {shape} tensor on {self.dev}")
+        node_g = self.node_sums(profile, add_load)
+        volt = out if out is not None and idx is None else torch.empty(S, n_nodes, T, dtype=torch.float64, device=self.dev)
+        d_nop, _, _ = side_arrays(self.dev, tree_host, n_nodes)
+        v = self.vset if vset is None else vset
+        check(self.lib.revs_net_study(S, self.M, T, C.byref(tree), ptr(node_g), None, None, ptr(d_nop), n_nodes, float(v),
+                                      float(self.vlow), float(self.vhigh), None, 0, None, 0, None, None, ptr(volt),
+                                      None, None, None, None, self.stream), "revs_net_study")
+        if idx is None:
+            return volt
+        picked = volt.index_select(1, idx)
+        return picked if out is None else out.copy_(picked)
 
     def network_reports(self, rating=None, nodes=None, arrays=True, profile=None, add_load=False) -> list:
         """AdmmEngine.network_report for every scenario -> S NetworkReports, from study_report's single launch without

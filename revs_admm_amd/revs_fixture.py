@@ -105,7 +105,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              **opt):
+              across=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -131,7 +131,10 @@ class REVS:
         sums its schedules per row from its own state (solve_ADMM_many(return_node_sums=True)), the individual methods'
         profiles are uploaded as the float64 values they are, the (S, M, T) buffer is assembled on the device in label
         order and reported by study.study_report_device; labels, groups and every report field keep their meaning
-        (StudyReport.node_p is the buffer read back)."""
+        (StudyReport.node_p is the buffer read back).  across=True: StudyReport.across, per community node and per rated
+        line the statistics across each group's scenarios (study.AcrossReport: in how many seeds a node goes below a
+        band at some hour, its median daily minimum, the slots in violation) -- on either path from the arrays on the
+        device."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -201,13 +204,13 @@ class REVS:
                                          rating=node_rating, nodes=[pos[h] for h in community],
                                          bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
                                          vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
-                                         arrays=opt.get("arrays", False))
+                                         arrays=opt.get("arrays", False), across=across)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
                               bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
                               vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
-                              arrays=opt.get("arrays", False), device=self.device)
+                              arrays=opt.get("arrays", False), device=self.device, across=across)
         return labels, rep
 
     def result_frames(self, demand, dist, community=None, start=11, end=23, shift=6, rating=None):

@@ -3,7 +3,9 @@ published figures are made of (test-dist-ind-opt.py:219-342 compare_method / com
 plots per hour pooled over all seeds of a group; test-dist-ind-adopt.py:73-117 compare_node_counts: per seed and hour
 the number of residences at or below 0.92 / 0.95 / 0.98 p.u.).  revs_net_study (include/revs_admm_ops.h, DESIGN.md
 section 3.8): per-schedule summaries and band counts from revs_net_report's kernel on a slots x schedules grid, and the
-pooled box-plot numbers by an exact selection over the group's staged keys.  Drawing stays outside the project."""
+pooled box-plot numbers by an exact selection over the group's staged keys; revs_net_across: per node and per line the
+statistics ACROSS the scenarios of a group (AcrossReport: which nodes fail, in how many seeds).  Drawing stays outside
+the project."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,7 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check, ptr
+from ._lib import ACROSS_DTYPE, check, ptr
 from .network import SUMMARY_DTYPE, side_arrays, tree_on_device
 
 # revs_net_pooled_t (include/revs_admm_ops.h): revs_net_summary_t with worst_scenario in the first reserved word
@@ -25,12 +27,56 @@ assert POOLED_DTYPE.itemsize == 96
 
 
 @dataclass
+class AcrossReport:
+    """Statistics per node and per line across the scenarios of each group (revs_net_across):
+    where the feeder fails and in how many scenarios.  ACROSS_DTYPE records -- min / q1 / median / q3 / max / mean over
+    the group's scenarios, count, n_nan, n_violations, worst_scenario, band_count[b] -- of
+    slot_volt / slot_loading     (G, nodes, T): the cell's values (None with slots=False)
+    daily_volt / daily_loading   (G, nodes): every scenario's daily extreme, the lowest voltage / the highest loading of
+                                 the day: band_count[b] is the number of scenarios in which the node goes at or below
+                                 bands_volt[b] (the line reaches bands_loading[b]) at some hour
+    exposure_volt / exposure_loading   (G, nodes) int32: the (scenario, slot) pairs in violation.
+    The *_loading fields are None without line ratings.  Nodes outside `nodes` and unrated lines hold empty records
+    (count 0).  group_sizes: (G,) scenarios per group."""
+    slot_volt: np.ndarray | None
+    slot_loading: np.ndarray | None
+    daily_volt: np.ndarray
+    daily_loading: np.ndarray | None
+    exposure_volt: np.ndarray
+    exposure_loading: np.ndarray | None
+    group_sizes: np.ndarray
+    bands_volt: tuple
+    bands_loading: tuple
+
+    def _kind(self, kind):
+        if kind not in ("volt", "loading"):
+            raise ValueError(f"across report: kind must be 'volt' or 'loading', got {kind!r}")
+        daily, exposure = getattr(self, "daily_" + kind), getattr(self, "exposure_" + kind)
+        if daily is None:
+            raise ValueError("across report: no loading records (the report had no line ratings)")
+        return daily, exposure
+
+    def probability(self, kind, b):
+        """(G, nodes): the share of the group's scenarios in which the node's daily extreme reaches band b --
+        daily band_count[..., b] / count; NaN where count == 0."""
+        daily, _ = self._kind(kind)
+        cnt = daily["count"].astype(np.float64)
+        return np.where(cnt > 0, daily["band_count"][..., b] / np.where(cnt > 0, cnt, 1.0), np.nan)
+
+    def expected_slots(self, kind):
+        """(G, nodes): the slots in violation per scenario -- exposure / count; NaN where count == 0."""
+        daily, exposure = self._kind(kind)
+        cnt = daily["count"].astype(np.float64)
+        return np.where(cnt > 0, exposure / np.where(cnt > 0, cnt, 1.0), np.nan)
+
+
+@dataclass
 class StudyReport:
     """summary_loading / summary_volt: (S, T) SUMMARY_DTYPE records, scenario s's as report_for_tree gives them.
     pooled_loading / pooled_volt: (G, T) POOLED_DTYPE records over all values of a group's scenarios ((0, T) without
     groups).  band_counts: (S, T, B) int32, the nodes of `nodes` with volt <= bands[b] (cumulative; NaNs never
     counted).  flow, loading, volt: (S, nodes, T) float64 or None (arrays=False).  groups: (S,) int, -1: in no pool.
-    node_p: (S, M, T) float64, the profiles reported."""
+    node_p: (S, M, T) float64, the profiles reported.  across: the AcrossReport of across=True, else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -45,6 +91,7 @@ class StudyReport:
     vset: float
     vmin: float
     vmax: float
+    across: AcrossReport | None = None
 
     @property
     def n_groups(self):
@@ -72,16 +119,107 @@ class StudyReport:
         return lo, hi
 
 
+def native_across(lib, stream, values, keep, groups, n_groups, lo, hi, sense, bands, slots):
+    """revs_net_across on values that lie on the device: values (S, n, T) float64 device tensor, keep (n,) bool or None,
+    groups (S,) int32 in -1 .. n_groups - 1 -> (slot records (G, n, T) or None, daily records (G, n), exposure (G, n)
+    int32), read back.  The one place this entry is called from (a host test puts tests/across_ref.py here)."""
+    S, n, T = values.shape
+    dev, G, B = values.device, int(n_groups), len(bands)
+    rec = ACROSS_DTYPE.itemsize
+    d_keep = None if keep is None else torch.from_numpy(np.ascontiguousarray(keep, np.uint8)).to(dev)
+    d_slot = torch.empty(G * n * T * rec, dtype=torch.uint8, device=dev) if slots else None
+    d_daily = torch.empty(G * n * rec, dtype=torch.uint8, device=dev)
+    d_exp = torch.empty(G, n, dtype=torch.int32, device=dev)
+    nbytes = int(lib.revs_net_across_scratch(S, n))
+    if nbytes <= 0:
+        raise ValueError(f"across report: no scratch size for S={S}, {n} nodes")
+    d_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    h_group = np.ascontiguousarray(groups, np.int32)
+    h_band = np.ascontiguousarray(bands, np.float64)
+    check(lib.revs_net_across(S, n, T, ptr(values), ptr(d_keep), h_group.ctypes.data, G, float(lo), float(hi), int(sense),
+                              h_band.ctypes.data if B else None, B, ptr(d_slot), ptr(d_daily), ptr(d_exp),
+                              ptr(d_scratch), stream), "revs_net_across")
+    slot = d_slot.cpu().numpy().view(ACROSS_DTYPE).reshape(G, n, T) if slots else None
+    return slot, d_daily.cpu().numpy().view(ACROSS_DTYPE).reshape(G, n), d_exp.cpu().numpy()
+
+
+def check_across_args(bands, loading_bands):
+    out = []
+    for b in (bands, loading_bands):
+        b = tuple(float(x) for x in b)
+        if len(b) > _lib.ACROSS_MAX_BANDS or not np.isfinite(b).all():
+            raise ValueError(f"across report: at most {_lib.ACROSS_MAX_BANDS} finite bands, got {b}")
+        out.append(b)
+    return out
+
+
+def across_report_device(volt, loading, groups, nodes=None, rated=None, bands=(0.92, 0.95, 0.98),
+                         loading_bands=(0.8, 1.0), vmin=0.95, vmax=1.05, slots=True, lib=None, stream=None) -> AcrossReport:
+    """Per node and per line, the statistics across each group's scenarios of voltages and loadings that lie on the
+    device: volt, loading contiguous (S, n, T) float64 tensors (study_report's arrays; loading may be None), groups one
+    integer per scenario as study_report's (not None).  Nothing but the records is read back.
+
+    nodes           the nodes the voltage records cover (None: all); the others hold empty records
+    rated           (n,) ratings or booleans: the loading records cover the lines with rated > 0 (None: all)
+    bands           up to 8 voltage thresholds: band_count[b] scenarios at or below bands[b]
+    loading_bands   up to 8 loading thresholds: band_count[b] scenarios at or above loading_bands[b]
+    vmin / vmax     a voltage outside them is a violation; a loading above 1 is one
+    slots           False: no (G, n, T) records, the daily ones and the exposure alone."""
+    for name, a in (("volt", volt), ("loading", loading)):
+        if a is None and name == "loading":
+            continue
+        if not isinstance(a, torch.Tensor) or a.dtype != torch.float64 or a.dim() != 3 or not a.is_contiguous():
+            raise ValueError(f"across report: {name} must be a contiguous (scenarios, nodes, slots) float64 tensor")
+    if loading is not None and (loading.shape != volt.shape or loading.device != volt.device):
+        raise ValueError("across report: volt and loading differ in shape or device")
+    S, n, T = volt.shape
+    if groups is None:
+        raise ValueError("across report: statistics across scenarios need groups (one integer per scenario)")
+    _, gid, G = check_study_args(S, (), groups)
+    if G < 1:
+        raise ValueError("across report: no scenario is in a group")
+    bands, loading_bands = check_across_args(bands, loading_bands)
+    keep_v = keep_l = None
+    if nodes is not None:
+        keep_v = np.zeros(n, bool)
+        keep_v[np.asarray(nodes)] = True
+    if rated is not None:
+        keep_l = np.nan_to_num(np.asarray(rated, np.float64), nan=0.0) > 0
+        if keep_l.shape != (n,):
+            raise ValueError(f"across report: rated must have one entry per node ({n}), got {keep_l.shape}")
+    dev = volt.device
+
+    def run():
+        st = stream
+        if st is None and dev.type == "cuda":
+            st = torch.cuda.current_stream(dev).cuda_stream
+        lb = lib or (_lib.load() if dev.type == "cuda" else None)
+        sv, dv, ev = native_across(lb, st, volt, keep_v, gid, G, vmin, vmax, -1, bands, slots)
+        sl = dl = el = None
+        if loading is not None:
+            sl, dl, el = native_across(lb, st, loading, keep_l, gid, G, -np.inf, 1.0, 1, loading_bands, slots)
+        return AcrossReport(sv, sl, dv, dl, ev, el, np.bincount(gid[gid >= 0], minlength=G).astype(np.int64), bands,
+                            loading_bands)
+
+    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
+        return run()
+    with torch.cuda.device(dev):
+        return run()
+
+
 def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, groups, n_groups, bands, rating, nodes, vset,
-                        vmin, vmax, arrays) -> StudyReport:
+                        vmin, vmax, arrays, across=False) -> StudyReport:
     """revs_net_study on node sums that lie on the device: node_g (S, M, T) float64 device tensor, tree: _lib.Tree (device
     pack / w), tree_host: the dict of feeder_tree, n_nodes: its nodes before padding; groups (S,) int32 in
     -1 .. n_groups - 1.  The one place the library is called from (a host test puts tests/study_ref.py here); the
-    records and the S M T node sums are read back."""
+    records and the S M T node sums are read back.  across=True (with groups): the arrays are written on the device
+    whatever `arrays` says, handed to across_report_device before anything is read back -> StudyReport.across, and read
+    back themselves only with arrays=True."""
     S, M, T = node_g.shape
     n, B, G = int(n_nodes), len(bands), int(n_groups)
     d_nop, d_rating, d_mask = side_arrays(dev, tree_host, n, rating, nodes)
-    out = [torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays else [None] * 3
+    out = ([torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays or across
+           else [None] * 3)
     d_sum = torch.zeros(S * 2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
     d_pool = d_scratch = d_band = None
     if G:                                   # staging only when pools are asked for
@@ -98,6 +236,12 @@ def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, grou
                              float(vmin), float(vmax), h_group.ctypes.data if G else None, G,
                              h_band.ctypes.data if B else None, B, ptr(out[0]), ptr(out[1]), ptr(out[2]),
                              ptr(d_sum), ptr(d_pool), ptr(d_band), ptr(d_scratch), stream), "revs_net_study")
+    acr = None
+    if across:
+        acr = across_report_device(out[2], out[1] if rating is not None else None, groups, nodes=nodes, rated=rating,
+                                   bands=bands, vmin=vmin, vmax=vmax, lib=lib, stream=stream)
+    if not arrays:
+        out = [None] * 3
     rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, 2, T)
     pool = (d_pool.cpu().numpy().view(POOLED_DTYPE).reshape(G, 2, T) if G
             else np.zeros((0, 2, T), POOLED_DTYPE))
@@ -105,11 +249,11 @@ def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, grou
     flow, loading, volt = (None if o is None else o.cpu().numpy() for o in out)
     return StudyReport(rec[:, 0].copy(), rec[:, 1].copy(), pool[:, 0].copy(), pool[:, 1].copy(), counts,
                        tuple(float(b) for b in bands), np.asarray(groups, np.int64).copy(), flow, loading, volt,
-                       node_g.cpu().numpy(), float(vset), float(vmin), float(vmax))
+                       node_g.cpu().numpy(), float(vset), float(vmin), float(vmax), acr)
 
 
 def native_study(parent, edge_r, cons_of, node_p, groups, n_groups, bands, rating, nodes, vset, vmin, vmax, arrays,
-                 device) -> StudyReport:
+                 device, across=False) -> StudyReport:
     """revs_net_study on checked arguments held on the host: node_p (S, M, T) float64, groups (S,) int32 in
     -1 .. n_groups - 1 -- the whole feeder's tree built and the profiles uploaded, then native_study_device."""
     from .engine import _dev_check
@@ -118,9 +262,26 @@ def native_study(parent, edge_r, cons_of, node_p, groups, n_groups, bands, ratin
         th, tree, _keep = tree_on_device(dev, parent, edge_r, cons_of, node_p.shape[1])
         g = torch.from_numpy(node_p).to(dev)
         rep = native_study_device(lib, dev, torch.cuda.current_stream(dev).cuda_stream, tree, th, len(parent), g, groups,
-                                  n_groups, bands, rating, nodes, vset, vmin, vmax, arrays)
+                                  n_groups, bands, rating, nodes, vset, vmin, vmax, arrays, **_across_kw(across))
     rep.node_p = node_p
     return rep
+
+
+def check_across_groups(across, groups):
+    """across=True needs groups with at least one scenario in one: refused before anything is launched."""
+    if not across:
+        return
+    if groups is None:
+        raise ValueError("study report: across=True reports across the scenarios of each group: pass groups")
+    gid = np.asarray(groups)
+    if gid.size and np.issubdtype(gid.dtype, np.integer) and gid.max() < 0:
+        raise ValueError("study report: across=True, but no scenario is in a group")
+
+
+def _across_kw(across):
+    """The trailing across=True of native_study / native_study_device, passed only when asked for: a stand-in with
+    the signature before it keeps working for every other call."""
+    return {"across": True} if across else {}
 
 
 def check_study_args(S, bands, groups):
@@ -139,7 +300,7 @@ def check_study_args(S, bands, groups):
 
 
 def study_report(parent, edge_r, cons_of, node_p, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98),
-                 vset=1.0, vmin=0.95, vmax=1.05, arrays=False, device="cuda:0") -> StudyReport:
+                 vset=1.0, vmin=0.95, vmax=1.05, arrays=False, device="cuda:0", across=False) -> StudyReport:
     """The report of S schedules on one feeder (network.report_for_tree's arguments; node_p is (S, M, T): row
     cons_of[i] of scenario s injected at tree node i).
 
@@ -149,16 +310,21 @@ def study_report(parent, edge_r, cons_of, node_p, groups=None, rating=None, node
               quantiles do not compose.
     bands     up to 8 voltage thresholds, any order: band_counts[s, t, b] nodes of `nodes` at or below bands[b].
     nodes     the nodes the voltage summaries, pools and band counts cover (the reference: the community); None: all.
-    arrays    True: also flow / loading / volt of every scenario, (S, nodes, T)."""
+    arrays    True: also flow / loading / volt of every scenario, (S, nodes, T).
+    across    True (needs groups): StudyReport.across, the AcrossReport of the voltages and -- with ratings -- the
+              loadings: per node and per line the statistics across each group's scenarios, from the arrays on the
+              device (across_report_device; `bands` are its voltage bands too)."""
     node_p = np.ascontiguousarray(node_p, np.float64)
     if node_p.ndim != 3:
         raise ValueError(f"study report: node_p must be (scenarios, rows, slots), got {node_p.shape}")
+    check_across_groups(across, groups)
     bands, gid, G = check_study_args(node_p.shape[0], bands, groups)
-    return native_study(parent, edge_r, cons_of, node_p, gid, G, bands, rating, nodes, vset, vmin, vmax, arrays, device)
+    return native_study(parent, edge_r, cons_of, node_p, gid, G, bands, rating, nodes, vset, vmin, vmax, arrays, device,
+                        **_across_kw(across))
 
 
 def study_report_device(node_g, feeder=None, tree=None, groups=None, rating=None, nodes=None, bands=(0.92, 0.95, 0.98),
-                        vset=1.0, vmin=0.95, vmax=1.05, arrays=False, lib=None, stream=None) -> StudyReport:
+                        vset=1.0, vmin=0.95, vmax=1.05, arrays=False, lib=None, stream=None, across=False) -> StudyReport:
     """study_report over node sums that lie on the device: node_g a contiguous (S, M, T) float64 tensor, row
     cons_of[i] of scenario s injected at tree node i (what AdmmEnsemble.node_sums / revs_net_node_sums_many write).
     The feeder comes as feeder=(parent, edge_r, cons_of), study_report's first three arguments -- its tree is built
@@ -171,6 +337,7 @@ def study_report_device(node_g, feeder=None, tree=None, groups=None, rating=None
         raise ValueError("study report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
     if (feeder is None) == (tree is None):
         raise ValueError("study report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
+    check_across_groups(across, groups)
     bands, gid, G = check_study_args(node_g.shape[0], bands, groups)
     dev = node_g.device
 
@@ -184,7 +351,7 @@ def study_report_device(node_g, feeder=None, tree=None, groups=None, rating=None
         if st is None and dev.type == "cuda":
             st = torch.cuda.current_stream(dev).cuda_stream
         return native_study_device(lib or _lib.load(), dev, st, tr, th, n_nodes, node_g, gid, G, bands, rating, nodes,
-                                   vset, vmin, vmax, arrays)
+                                   vset, vmin, vmax, arrays, **_across_kw(across))
 
     if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
         return run()
