@@ -583,6 +583,57 @@ int revs_net_across(int32_t S, int32_t n_out, int32_t T, const double *values, c
                     revs_net_across_t *slot_out, revs_net_across_t *daily_out, int32_t *exposure_out, void *scratch,
                     void *stream);
 
+/* ---- bill report: what a schedule costs each residence, and its deviation from a baseline schedule ------------------
+ * The reference's last result figure: per residence C = sum over t of P_res[t] COST[t] for two schedules and
+ * dev = 100 (C2 - C1) / C1.  Here for S schedules at once, from the state on the device (csrc/bill_kernels.hip).
+ *
+ * revs_bill_rows: bill[s][i] = sum over t of tariff[t] * (double) g[s stride_s + i stride_i + t], ONE double accumulator
+ * from +0.0, the slots ascending, product and sum rounded separately (no fused multiply-add): the bits of the numpy loop
+ * acc = acc + c[t] * g[:, t], whatever S, the layout and the thread that holds the row.  g: device float (g_f64 = 0: an
+ * ensemble's P_sch, float[n][S][T], stride_s = T, stride_i = S T) or double (g_f64 = 1: a study buffer double[S][n][T],
+ * stride_s = n T, stride_i = T); strides in elements.  tariff: device double[T].  bill: device double[S][n], S n
+ * doubles written from the pointer on and nothing else: a caller fills one buffer from several ensembles through
+ * bill + s0 n.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; n < 1 or
+ * S n >= 2^31; a null g, tariff or bill; g_f64 not 0 / 1; strides under which rows overlap -- accepted are exactly
+ * stride_i >= T && stride_s >= n stride_i, or stride_s >= T && stride_i >= S stride_s. */
+int revs_bill_rows(int32_t S, int64_t n, int32_t T, const void *g, int32_t g_f64, int64_t stride_s, int64_t stride_i,
+                   const double *tariff, double *bill, void *stream);
+
+/* revs_bill_study: deviations from a baseline row and box-plot records per scenario and pooled over groups.
+ *   dev[s][i] = (100 (bill[s][i] - bill[b][i])) / bill[b][i], b = base[s] (HOST int32[S]; -1: a row of NaN), every
+ *   operation rounded on its own in that order: numpy's 100*(C2-C1)/C1; a zero baseline bill gives what IEEE gives.
+ *   dev_out: device double[S][n], or NULL (the deviations then live in `scratch` only).
+ *   summary_out[s][q] (revs_bill_summary_t[S][2]; q = 0: bill, 1: dev): the record of scenario s's rows with
+ *   keep[s][i] != 0 (device uint8[S][n]; NULL keeps every row); worst_scenario is s.
+ *   pooled_out[g][q] ([G][2]): the same rule over the multiset of all kept values of the scenarios with group[s] == g
+ *   (HOST int32[S] in -1..G-1, as revs_net_study's).  A pool of one scenario equals that scenario's record in every field.
+ * A record: a kept value that is not finite counts in n_nan and is left out of everything else.  Quartiles are selected
+ * exactly (digit-wise radix select over the values' ordered bit patterns, no sort) and interpolated as
+ * numpy.percentile's, with the roundings of the other summaries; min and max are the smallest and the largest value;
+ * whiskers and fliers as revs_net_summary_t's; -0.0 orders and is reported as +0.0.  worst_*: the largest value, ties to
+ * the lowest scenario, then the lowest caller-side index index_of_row[i] (device int32[n]; NULL: i).  total: a sum in a
+ * fixed tree order, the same bits from call to call.  With count == 0 every statistic is a NaN, both indices -1 and the
+ * counts 0.  reserved0 is 0.
+ * A fixed sequence of launches on one stream (deviations, then one selection workgroup per (member set, quantity)); no
+ * grid-wide barrier.  Any output may be NULL, not all.  Reads bill, keep and index_of_row; writes the outputs and the
+ * scratch.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; n < 1 or S n >= 2^31; bill NULL; base NULL
+ * or an entry outside -1..S-1; G outside 0..S; group NULL with G > 0; a group id outside -1..G-1; pooled_out with
+ * G == 0; summary_out or pooled_out without a 16-byte aligned scratch of revs_bill_study_scratch bytes (8 S n; 0 for a
+ * bad size); every output NULL. */
+typedef struct {
+    double min, q1, median, q3, max;   /* numpy.percentile, linear, over the values summarised */
+    double whisker_lo, whisker_hi;     /* farthest values within 1.5 (q3 - q1) of the box */
+    double total;                      /* sum of the values summarised */
+    double reserved0;
+    int32_t count, n_nan;              /* kept values that are finite / that are not */
+    int32_t n_fliers, n_above;         /* beyond the whiskers / > 0.0 */
+    int32_t worst_index, worst_scenario; /* caller's index and scenario of the largest value; -1: count == 0 */
+} revs_bill_summary_t;                 /* 96 bytes */
+int64_t revs_bill_study_scratch(int32_t S, int64_t n);
+int revs_bill_study(int32_t S, int64_t n, const double *bill, const int32_t *base, const uint8_t *keep,
+                    const int32_t *index_of_row, const int32_t *group, int32_t G, double *dev_out,
+                    revs_bill_summary_t *summary_out, revs_bill_summary_t *pooled_out, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,13 @@ ACROSS_DTYPE = np.dtype([("min", "<f8"), ("q1", "<f8"), ("median", "<f8"), ("q3"
                          ("band_count", "<i4", (ACROSS_MAX_BANDS,))])
 assert ACROSS_DTYPE.itemsize == 96
 
+# numpy mirror of revs_bill_summary_t (include/revs_admm_ops.h)
+BILL_DTYPE = np.dtype([("min", "<f8"), ("q1", "<f8"), ("median", "<f8"), ("q3", "<f8"), ("max", "<f8"),
+                       ("whisker_lo", "<f8"), ("whisker_hi", "<f8"), ("total", "<f8"), ("reserved0", "<f8"),
+                       ("count", "<i4"), ("n_nan", "<i4"), ("n_fliers", "<i4"), ("n_above", "<i4"),
+                       ("worst_index", "<i4"), ("worst_scenario", "<i4")])
+assert BILL_DTYPE.itemsize == 96
+
 
 class RevsError(RuntimeError):
     pass
@@ -265,6 +272,9 @@ SIGNATURES = {
                                  _i32, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_net_across_scratch": (_i64, [_i32, _i32]),
     "revs_net_across": (C.c_int, [_i32, _i32, _i32, _p, _p, _p, _i32, _f64, _f64, _i32, _p, _i32, _p, _p, _p, _p, _p]),
+    "revs_bill_rows": (C.c_int, [_i32, _i64, _i32, _p, _i32, _i64, _i64, _p, _p, _p]),
+    "revs_bill_study_scratch": (_i64, [_i32, _i64]),
+    "revs_bill_study": (C.c_int, [_i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -24,6 +24,7 @@ import torch
 from . import _lib
 from ._lib import HOME_DTYPE
 from .engine import AdmmEngine, OperatorOptions, _on_current_stream
+from .ensemble_bills import EnsembleBillsMixin
 from .ensemble_certificate import EnsembleCertificateMixin
 from .ensemble_report import EnsembleReportMixin
 
@@ -45,7 +46,7 @@ def check_shape(S: int, T: int, group=None) -> None:
                          f"{_lib.ENS_MAX_COLS} (at most {_lib.ENS_MAX_COLS // T} scenarios at T = {T})")
 
 
-class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, AdmmEngine):
+class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsMixin, AdmmEngine):
     """S ADMM runs on one feeder, side by side on one GPU.
 
     Parameters as AdmmEngine's, except

@@ -105,7 +105,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, **opt):
+              across=False, bills=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -134,10 +134,14 @@ class REVS:
         (StudyReport.node_p is the buffer read back).  across=True: StudyReport.across, per community node and per rated
         line the statistics across each group's scenarios (study.AcrossReport: in how many seeds a node goes below a
         band at some hour, its median daily minimum, the slots in violation) -- on either path from the arrays on the
-        device."""
+        device.  bills=True: StudyReport.bills, the bills.BillReport of the study's rows (the residences) under
+        `tariff`: every scenario's bills, their deviation from the individual schedule of the same (adoption, rating,
+        seed) -- base[s] is that row, -1 without one -- and the records over each scenario's EV homes, pooled by the
+        report's groups; on the device_report path from the buffer on the device."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
+        from .bills import bill_report, bill_report_device
         keys = (group_by,) if isinstance(group_by, str) else tuple(group_by)
         unknown = [k for k in keys if k not in ("method", "adoption", "rating", "seed")]
         unknown += [m for m in methods if m not in ("distributed", "individual")]
@@ -156,7 +160,8 @@ class REVS:
         edges = list(dist.edges)
         if opt.get("line_rating") is not None or (edges and all("rating" in dist.edges[e] for e in edges)):
             node_rating = line_nodes(dist, opt.get("line_rating"), parent, nonsub)[0]
-        labels, profiles, deferred = [], [], []      # deferred: (position in profiles, homes) of the ensemble's scenarios
+        # deferred: (position in profiles, homes) of the ensemble's scenarios; owners: every scenario's EV homes
+        labels, profiles, deferred, owners = [], [], [], []
         for adoption in adoptions:
             for rating in ratings:
                 for seed in seeds:
@@ -167,6 +172,7 @@ class REVS:
                                                opt.get("end_time", 23))
                     for method in methods:
                         labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
+                        owners.append(ev_homes)
                         if method == "distributed" and ensemble:
                             deferred.append((len(profiles), homes))
                             profiles.append(None)
@@ -194,6 +200,12 @@ class REVS:
                 profiles[i] = node_g[k] if device_report else np.array([sol[1][h] for h in res], np.float64)
         combos = [tuple(lab[k] for k in keys) for lab in labels]
         order = list(dict.fromkeys(combos))
+        bill_kw = None
+        if bills:
+            case = lambda lab: (lab["adoption"], lab["rating"], lab["seed"])
+            ind = {case(lab): s for s, lab in enumerate(labels) if lab["method"] == "individual"}
+            bill_kw = dict(base=[ind.get(case(lab), -1) for lab in labels], groups=[order.index(c) for c in combos],
+                           keep=np.array([np.isin(res, ev) for ev in owners]), arrays=opt.get("arrays", False))
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -205,12 +217,16 @@ class REVS:
                                          bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
                                          vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
                                          arrays=opt.get("arrays", False), across=across)
+            if bills:
+                rep.bills = bill_report_device(buf, tariff, **bill_kw)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
                               bands=opt.get("bands", (0.92, 0.95, 0.98)), vset=opt.get("report_vset", 1.0),
                               vmin=opt.get("vmin", 0.95), vmax=opt.get("vmax", 1.05),
                               arrays=opt.get("arrays", False), device=self.device, across=across)
+        if bills:
+            rep.bills = bill_report(np.stack(profiles), tariff, device=self.device, **bill_kw)
         return labels, rep
 
     def result_frames(self, demand, dist, community=None, start=11, end=23, shift=6, rating=None):

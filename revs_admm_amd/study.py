@@ -76,7 +76,8 @@ class StudyReport:
     pooled_loading / pooled_volt: (G, T) POOLED_DTYPE records over all values of a group's scenarios ((0, T) without
     groups).  band_counts: (S, T, B) int32, the nodes of `nodes` with volt <= bands[b] (cumulative; NaNs never
     counted).  flow, loading, volt: (S, nodes, T) float64 or None (arrays=False).  groups: (S,) int, -1: in no pool.
-    node_p: (S, M, T) float64, the profiles reported.  across: the AcrossReport of across=True, else None."""
+    node_p: (S, M, T) float64, the profiles reported.  across: the AcrossReport of across=True, else None.  bills: the
+    bills.BillReport of REVS.study(bills=True), else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -92,6 +93,7 @@ class StudyReport:
     vmin: float
     vmax: float
     across: AcrossReport | None = None
+    bills: object | None = None
 
     @property
     def n_groups(self):
