@@ -188,14 +188,19 @@ int revs_op_node_update(int32_t m, int32_t T, int32_t nslab, const double *va,
  *                           Q (l ph0)) against the bounds; cx = v0; stats (double[2], ZERO on
  *                           entry): [0] = largest row violation (0 <=> g0 already respects
  *                           every voltage row), [1] = max(0, -min gmin) (> 0 <=> some
- *                           residence has g0 < 0).  Both 0 <=> the answer is g0 itself
+ *                           residence has g0 < 0).  Both 0 <=> the answer is g0 itself.
+ *                           stats is MERGED, not overwritten: each entry becomes the maximum of
+ *                           what it held (>= 0) and of the call's value, like res
  *   revs_op_nodefast_scale  xh = (kappa ph0 + l wh)/(kappa + rho_v l^2), sx = l xh
  *                           (wh = Q^T w as nslab slabs, ph0 = Q^T p0)
  *   revs_op_nodefast_update z_v, y_v, w from zt = Q sx (nslab slabs); res rows 0,3,4
  *   revs_op_nodefast_dualres res rows 2,5,6,7 from yh = Q^T y_v (nslab slabs), in the
- *                           eigenbasis: |kappa (xh - ph0) + l yh|, kappa|xh| ...
+ *                           eigenbasis: max |kappa (xh - ph0) + l yh|, |xh|, |l yh|, kappa|ph0|
+ *                           (row 5 without kappa, as in revs_op_home_pass: the driver scales
+ *                           it); res is required and merged by maximum
  *   revs_op_nodefast_finish d = Q xh - p0 (x as nslab slabs), slack = gmin + isn d;
- *                           stats (double[2], ZERO on entry) = {max(0, -min slack), max|p0|}
+ *                           stats (double[2], ZERO on entry) = {max(0, -min slack), max|p0|},
+ *                           merged by maximum like that of revs_op_nodefast_feas
  *   revs_op_node_apply      P_est_i = max(g0_i + isn[m] d[m], 0) as float (g0 as in prep)   */
 int revs_op_node_prep(int32_t m, int32_t T, const int64_t *node_ptr, const double *inv_sqrt_n,
                       const float *p_est, const float *p_sch, const float *gamma, double kappa,

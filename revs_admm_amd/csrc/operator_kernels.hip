@@ -122,7 +122,8 @@ __global__ __launch_bounds__(256) void op_home_pass_kernel(
             double vav = nu.va[idx], zt = nu.usa[idx];
             for (int q = 1; q < nu.nslab; ++q) { vav += nu.va[idx + q * total]; zt += nu.usa[idx + q * total]; }
             const double rv = nu.rho_v[t];
-            const double xcv = vav - rhat[idx] * inv_c;
+            // a division, as in op_node_update_kernel: the fused form owes that kernel's bits
+            const double xcv = vav - rhat[idx] / (kappa + rb);
             const double h = alpha * zt + (1.0 - alpha) * nu.zv[idx];
             double y = nu.yv[idx];
             const double bs = nu.bscale ? nu.bscale[node] : 1.0;
@@ -393,8 +394,9 @@ __global__ void op_nodefast_update_kernel(int total, int T, int nslab, const dou
     }
 }
 
-// dual residual in the eigenbasis: rows 2,5,6,7 = max |kappa (xh - ph0) + l yh|, kappa|xh|,
-// |l yh|, kappa|ph0|   (yh = Q^T y as nslab slabs).  Row 1 (bound rows) stays 0.
+// dual residual in the eigenbasis: rows 2,5,6,7 = max |kappa (xh - ph0) + l yh|, |xh|,
+// |l yh|, kappa|ph0|   (yh = Q^T y as nslab slabs; row 5 without kappa, the driver scales it).
+// Row 1 (bound rows) is left alone.
 __global__ void op_nodefast_dualres_kernel(int total, int T, int nslab, const double *xh,
                                            const double *ph0, const double *lam,
                                            const double *yh_s, double kappa, double *res) {

@@ -254,3 +254,59 @@ def test_operator_edge_topologies(gpu_lib):
                                w.kappa, vlo, vhi)
         assert np.abs(ref - np.maximum(g0, 0)).max() > 1e-3
         assert np.abs(got - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
+
+
+GEMM_F32_SHAPES = [(37, 5, 19), (16, 16, 4), (1, 1, 1), (130, 192, 257), (70, 40, 33), (70, 100, 33),
+                   (70, 128, 33),
+                   # the column-tile counts (2, 4, 6 of 16) the shapes above leave out
+                   (70, 24, 33), (70, 64, 33), (70, 96, 33)]
+
+
+def test_gemm_f32_shapes_take_every_tile_variant():
+    """launch_gemm (csrc/gemm_kernels.hip) picks its kernel by nt = ceil(n / 16): <= 1, 2, 3, 4, 6, 8, else 12."""
+    variant = lambda n: next(v for v in (1, 2, 3, 4, 6, 8, 12) if (n + 15) // 16 <= v)
+    assert {variant(n) for _, n, _ in GEMM_F32_SHAPES} == {1, 2, 3, 4, 6, 8, 12}
+
+
+@pytest.mark.parametrize("m,n,k", GEMM_F32_SHAPES)
+def test_gemm_tn_f32(gpu_lib, m, n, k):
+    """C = At^T B on v_mfma_f32_16x16x4_f32, called directly: integer data (exact in float at these
+    sizes: |c| <= 16 k), overwrite and accumulate."""
+    import torch
+    from revs_admm_amd._lib import check, ptr
+    rng = np.random.default_rng(m + n + k)
+    At = rng.integers(-4, 5, (k, m)).astype(np.float32)
+    B = rng.integers(-4, 5, (k, n)).astype(np.float32)
+    C0 = rng.integers(-9, 10, (m, n)).astype(np.float32)
+    ref = At.astype(np.float64).T @ B.astype(np.float64)
+    dA, dB = _up(At, np.float32), _up(B, np.float32)
+    st = torch.cuda.current_stream().cuda_stream
+    for acc in (0, 1):
+        dC = _up(C0, np.float32)
+        check(gpu_lib.revs_gemm_tn_f32(m, n, k, ptr(dA), m, ptr(dB), n, ptr(dC), n, acc, st))
+        assert (dC.cpu().numpy().astype(np.float64) == ref + acc * C0).all(), acc
+
+
+@pytest.mark.parametrize("dt", [np.float64, np.float32])
+@pytest.mark.parametrize("m,n,k", [(37, 5, 19), (130, 47, 65)])
+def test_gemm_padded_leading_dimensions(gpu_lib, dt, m, n, k):
+    """lda = m + 3, ldb = n + 5, ldc = n + 2, as the header offers: integer data, exact; the pad
+    columns of A and B hold values that must not enter, those of C a sentinel that must survive."""
+    import torch
+    from revs_admm_amd._lib import check, ptr
+    rng = np.random.default_rng(m + n + k)
+    lda, ldb, ldc = m + 3, n + 5, n + 2
+    At = rng.integers(-4, 5, (k, lda)).astype(dt)
+    B = rng.integers(-4, 5, (k, ldb)).astype(dt)
+    C0 = rng.integers(-9, 10, (m, ldc)).astype(dt)
+    C0[:, n:] = 12345.0
+    ref = At[:, :m].astype(np.float64).T @ B[:, :n].astype(np.float64)
+    dA, dB = _up(At, dt), _up(B, dt)
+    fn = gpu_lib.revs_gemm_tn_f64 if dt is np.float64 else gpu_lib.revs_gemm_tn_f32
+    st = torch.cuda.current_stream().cuda_stream
+    for acc in (0, 1):
+        dC = _up(C0, dt)
+        check(fn(m, n, k, ptr(dA), lda, ptr(dB), ldb, ptr(dC), ldc, acc, st))
+        got = dC.cpu().numpy()
+        assert (got[:, :n].astype(np.float64) == ref + acc * C0[:, :n]).all(), acc
+        assert (got[:, n:] == 12345.0).all()
