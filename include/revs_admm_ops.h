@@ -639,6 +639,59 @@ int revs_bill_study(int32_t S, int64_t n, const double *bill, const int32_t *bas
                     const int32_t *index_of_row, const int32_t *group, int32_t G, double *dev_out,
                     revs_bill_summary_t *summary_out, revs_bill_summary_t *pooled_out, void *scratch, void *stream);
 
+/* ---- convergence report: per-iteration and per-residence statistics of the residual history -------------------------
+ * The reference's solve_ADMM returns diff[h][k], every residence's residual at every iteration, and plot_convergence
+ * draws it.  Here from the history where the streaming launches leave it (csrc/convergence_kernels.hip), for one run or
+ * the S scenarios of an ensemble.
+ *
+ * hist: device float, K rows with a row stride of ld elements; element (k, i, s) -- row k, residence i, scenario s -- at
+ * k ld + i S + s: the ensemble's [n][S] sweep layout, with S = 1 the single engine's float[K][n].  keep: device
+ * uint8[S][n], the residences of scenario s the records cover (NULL: all).  index: device int32[n], the caller-side
+ * index reported for row i (NULL: i).  groups: HOST int32[S] in -1..G-1, as revs_bill_study's.
+ *   iter_rec[s][k] (revs_bill_summary_t[S][K]): the record of the kept hist[k][i][s], widened to double (exact), under
+ *   revs_bill_study's rules -- a kept value that is not finite counts in n_nan and is left out; quartiles selected
+ *   exactly (digit-wise radix select over the floats' ordered bit patterns, four 8-bit digits, no sort) and interpolated
+ *   as numpy.percentile's, no fused multiply-add; whiskers and fliers as revs_net_summary_t's; -0.0 orders and is
+ *   reported as +0.0; with count == 0 every statistic a NaN, both indices -1, the counts 0 -- except that n_above counts
+ *   the values > eps.  worst_index: the largest value, ties to the lowest caller-side index; worst_scenario = s.
+ *   total: a sum in a fixed tree order, the same bits from call to call.
+ *   pool_rec[g][k] ([G][K]): the same record over all kept values of the scenarios with groups[s] == g; the worst entry
+ *   is the largest value, then the lowest scenario, then the lowest index; total is the members' totals added in scenario
+ *   order.  A pool of one scenario repeats that scenario's record byte for byte.
+ *   res_rec[s][i] (revs_conv_res_t[S][n], every residence, kept or not): a row is ABOVE when !(x <= eps), so a NaN is
+ *   above.  n_above: the rows above; settle: 1 + the last row above (0: never above; K: the last row is above, not
+ *   settled within the history); max: the largest value that is no NaN, -0.0 as +0.0 (NaN: none); worst_iteration: its
+ *   first row (-1: none); last: hist[K-1]; reserved: 0.
+ *   run_rec[s] (revs_conv_run_t[S]): with m[k] = iter_rec[s][k].max, converged_at is the first row k0 with m[k] <= eps
+ *   for all of k0 .. k0 + patience - 1, all below K, else -1 (AdmmEngine.run's stopping rule; a row with an empty
+ *   sample is not within eps); last_above the last row with !(m[k] <= eps), or -1; n_unsettled / n_never the kept
+ *   residences with settle == K / settle == 0 -- both -1 when res_rec is NULL.
+ *   settle_rec[s] (revs_bill_summary_t[S]): the record over (double) settle of the kept residences, n_above those with
+ *   settle > 0, worst_index the caller-side index of the largest settle (ties: the lowest); exact in every field.
+ * res_rec, run_rec and settle_rec may be NULL: that output is skipped, the others are the same bytes.  A fixed sequence
+ * of launches on one stream (a selection workgroup per (row, block of 8 scenarios), one per (row, block of 4 groups), a
+ * thread per column over the rows, a workgroup per scenario); no grid-wide barrier, no floating-point atomics.  Reads
+ * hist, keep, index; writes the outputs and the scratch (revs_conv_report_scratch bytes, 16-byte aligned: integer
+ * histograms of settle, 4 S (K + 1) + 8 S bytes rounded up; <= 0 for sizes the report refuses).
+ * REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; n < 1; K < 1; S n >= 2^31; ld < n S; patience < 1; eps
+ * negative or a NaN; a null hist, iter_rec or scratch; G outside 0..REVS_STUDY_MAX_S (a pool without members has
+ * empty records); G > 0 without groups or without pool_rec; a group
+ * id outside -1..G-1. */
+typedef struct {
+    float max, last;                   /* the largest residual that is no NaN; the last row's */
+    int32_t settle, n_above;           /* 1 + the last row above eps; the rows above eps */
+    int32_t worst_iteration, reserved; /* the first row that holds max, -1: none; 0 */
+} revs_conv_res_t;                     /* 24 bytes */
+typedef struct {
+    int32_t converged_at, last_above;  /* first row of `patience` rows within eps, -1: none; last row above, -1: none */
+    int32_t n_unsettled, n_never;      /* kept residences with settle == K / settle == 0; -1 without res_rec */
+} revs_conv_run_t;                     /* 16 bytes */
+int64_t revs_conv_report_scratch(int32_t S, int64_t n, int32_t K, int32_t G);
+int revs_conv_report(int32_t S, int64_t n, int32_t K, const float *hist, int64_t ld, const uint8_t *keep,
+                     const int32_t *index, const int32_t *groups, int32_t G, double eps, int32_t patience,
+                     revs_bill_summary_t *iter_rec, revs_bill_summary_t *pool_rec, revs_conv_res_t *res_rec,
+                     revs_conv_run_t *run_rec, revs_bill_summary_t *settle_rec, void *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,13 @@ BILL_DTYPE = np.dtype([("min", "<f8"), ("q1", "<f8"), ("median", "<f8"), ("q3", 
                        ("worst_index", "<i4"), ("worst_scenario", "<i4")])
 assert BILL_DTYPE.itemsize == 96
 
+# numpy mirrors of revs_conv_res_t and revs_conv_run_t (include/revs_admm_ops.h)
+CONV_RES_DTYPE = np.dtype([("max", "<f4"), ("last", "<f4"), ("settle", "<i4"), ("n_above", "<i4"),
+                           ("worst_iteration", "<i4"), ("reserved", "<i4")])
+assert CONV_RES_DTYPE.itemsize == 24
+CONV_RUN_DTYPE = np.dtype([("converged_at", "<i4"), ("last_above", "<i4"), ("n_unsettled", "<i4"), ("n_never", "<i4")])
+assert CONV_RUN_DTYPE.itemsize == 16
+
 
 class RevsError(RuntimeError):
     pass
@@ -275,6 +282,8 @@ SIGNATURES = {
     "revs_bill_rows": (C.c_int, [_i32, _i64, _i32, _p, _i32, _i64, _i64, _p, _p, _p]),
     "revs_bill_study_scratch": (_i64, [_i32, _i64]),
     "revs_bill_study": (C.c_int, [_i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
+    "revs_conv_report_scratch": (_i64, [_i32, _i64, _i32, _i32]),
+    "revs_conv_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _f64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -1027,11 +1027,23 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         `history=False`: the per-residence diff of every iteration is neither kept nor fetched (at
         100 000 residences x 500 iterations it is 200 MB to carry to the host, more time than the
         iterations themselves take); returns the number of iterations run, `max_diff` holds max_h diff[h]
-        of the streamed ones."""
-        rows = max(1, min(iter_max, int(2e9) // (4 * max(self.n, 1)))) if history else iter_max
+        of the streamed ones.
+        `history="device"`: the history is kept and not fetched -- one piece on the device, `self.diff_history`
+        (iterations run, n) float32 in the engine's sweep order (row r: the caller's residence perm[r]), for
+        convergence_report(); returns the number of iterations run.  ValueError before anything runs when
+        iter_max n 4 bytes exceed the 2 GB of a piece."""
+        on_device = isinstance(history, str)      # (a string is truthy: every `if history` below means "rows are kept")
+        if on_device and history != "device":
+            raise ValueError(f'run: history must be True, False or "device", got {history!r}')
+        if on_device and iter_max * max(self.n, 1) * 4 > int(2e9):
+            raise ValueError(f'run: history="device" keeps the history in one piece of at most 2 GB; {iter_max} iterations '
+                             f"x {self.n} residences x 4 bytes are more")
+        self.diff_history = None
+        rows = max(1, min(iter_max, int(2e9) // (4 * max(self.n, 1)))) if history and not on_device else iter_max
         if history:
-            diffs = torch.empty((iter_max, self.n), dtype=torch.float32)
             hist = torch.empty((rows, self.n), dtype=torch.float32, device=self.dev)
+        if history and not on_device:
+            diffs = torch.empty((iter_max, self.n), dtype=torch.float32)
             inv = torch.from_numpy(np.ascontiguousarray(self.inv_perm, dtype=np.int64)).to(self.dev)
         self.converged_at = None
         k, it0, good, seen, stop = 0, self.iteration, 0, self.iteration, False
@@ -1087,14 +1099,34 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
                             self.converged_at = seen - patience + 1
                             stop = True
             # (back to the caller's home order on the device: one gather, one copy)
-            if history:
+            if history and not on_device:
                 diffs[base:k].copy_(hist[:r].index_select(1, inv))
             if stop and last:
                 break
         if status_pending:
             self.check_status(deferred=True)
         self.check_status()
+        if on_device:
+            self.diff_history = hist[:k]
+            return k
         return diffs[:k].numpy() if history else k
+
+    def convergence_report(self, eps, patience=8, keep=None, arrays=True):
+        """convergence.ConvergenceReport of the last run(history="device"), from self.diff_history where it lies: only the
+        records are read back.  Row k of the report is iteration (self.iteration - rows + k + 1).  keep: None, or n
+        booleans in the caller's home order -- the residences the records cover; `residences`, `keep` and worst_index
+        are in the caller's home order."""
+        from . import convergence
+        hist = getattr(self, "diff_history", None)
+        if hist is None:
+            raise ValueError('convergence report: no history on the device -- run(history="device") first')
+        if keep is not None:
+            keep = np.asarray(keep)
+            if keep.shape != (self.n,):
+                raise ValueError(f"convergence report: keep must be one boolean per residence ({self.n}), got {keep.shape}")
+            keep = keep[self.perm][None]
+        rep = convergence.convergence_report_device(hist, eps, 1, keep, np.asarray(self.perm), None, patience, arrays)
+        return convergence.report_in_caller_order(rep, self.inv_perm)
 
     # ------------------------------------------------------- state in / out
     def set_state(self, P_est, P_sch, G, iteration=None):

@@ -26,6 +26,7 @@ from ._lib import HOME_DTYPE
 from .engine import AdmmEngine, OperatorOptions, _on_current_stream
 from .ensemble_bills import EnsembleBillsMixin
 from .ensemble_certificate import EnsembleCertificateMixin
+from .ensemble_convergence import EnsembleConvergenceMixin
 from .ensemble_report import EnsembleReportMixin
 
 # the ADMM forms of the operator QP (operator_admm.py) multiply by the dense factors of R: the dense products' column limit
@@ -46,7 +47,8 @@ def check_shape(S: int, T: int, group=None) -> None:
                          f"{_lib.ENS_MAX_COLS} (at most {_lib.ENS_MAX_COLS // T} scenarios at T = {T})")
 
 
-class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsMixin, AdmmEngine):
+class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsMixin, EnsembleConvergenceMixin,
+                   AdmmEngine):
     """S ADMM runs on one feeder, side by side on one GPU.
 
     Parameters as AdmmEngine's, except
@@ -153,11 +155,14 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsM
             self.step(write_sc=False)
 
     @_on_current_stream
-    def run(self, iter_max=15, eps=None):
+    def run(self, iter_max=15, eps=None, history=True):
         """solve_ADMM's loop for every scenario -> diff (S, iterations, n) in the caller's residence order.  With `eps`
         the run stops after the first iteration in which every scenario's max_h diff[h] is within it (schedules are
-        then written by every iteration)."""
+        then written by every iteration).  history="device": the history is not fetched -- it stays on the device as
+        `self.diff_history`, (iterations, n S) float32 in the sweep's layout, for convergence_report(); returns the
+        number of iterations run."""
         n, S = self.n_res, self.S_count
+        on_device = self._history_on_device(history, iter_max)
         hist = torch.empty((iter_max, n * S), dtype=torch.float32, device=self.dev)
         k = 0
         while k < iter_max:
@@ -169,6 +174,9 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsM
             if eps is not None and (self.scenario_max_diff() <= eps).all():
                 break
         self.check_status()
+        if on_device:
+            self.diff_history = hist[:k]
+            return k
         d = hist[:k].view(k, n, S).permute(2, 0, 1).cpu().numpy()
         return np.ascontiguousarray(d[:, :, self.inv_perm])
 

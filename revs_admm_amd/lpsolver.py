@@ -154,7 +154,8 @@ def split_scenarios(S: int, T: int):
 
 def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
                     vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None,
-                    return_certificates=False, return_node_sums=False):
+                    return_certificates=False, return_node_sums=False, return_convergence=None,
+                    convergence_groups=None, convergence_patience=8):
     """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
     `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
     DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
@@ -166,7 +167,15 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
     (len(homes_list), M, T) float64 tensor on the device, scenario s's schedule P_sch summed over every row's
     residences (M rows, one per residence here), in `homes_list` order -- study.study_report_device's input.  Every
     ensemble fills its slice from its state (AdmmEnsemble.node_sums(out=)) before it is released; an empty list gives
-    an empty tensor."""
+    an empty tensor.
+    return_convergence=eps (a number, not None): the convergence.ConvergenceReport of all scenarios at that eps is
+    appended to the tuple -- (solutions[, certificates][, node_g], report), in that order -- with `convergence_groups`
+    (None, or one pool id per scenario, -1: none) and `convergence_patience`.  Every ensemble then runs with
+    history="device": its residuals stay on the device, are put into the caller's residence order there and gathered in
+    ONE (iterations, n, len(homes_list)) float32 buffer which convergence.convergence_report_device reads; the report's
+    records are read back and nothing else of it.  What IS still fetched is every solution's `diff` entry, from that
+    buffer, because each returned tuple keeps solve_ADMM's form; the schedules are fetched as without the report.  An
+    empty list gives None for the report."""
     import torch
     from .ensemble import AdmmEnsemble
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]
@@ -183,21 +192,39 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
         recs.append(rec)
     parts = split_scenarios(len(recs), T)
 
-    def answer(out, certs, node_g):
+    want_conv = return_convergence is not None
+    if want_conv:
+        from . import convergence
+        # (every check of the report's arguments before anything is solved)
+        convergence.check_conv_args(max(len(recs), 1), max(len(res), 1), iter_max, return_convergence,
+                                    convergence_patience, convergence_groups if recs else None, None)
+
+    def answer(out, certs, node_g, conv=None):
         extra = ((certs,) if return_certificates else ()) + ((node_g,) if return_node_sums else ())
+        extra += (conv,) if want_conv else ()
         return (out,) + extra if extra else out
 
     if not parts:
         return answer([], [], torch.empty(0, len(res), T, dtype=torch.float64, device=device)
                       if return_node_sums else None)
     R_res, feeder = feeder if feeder is not None else feeder_of(graph)
-    out, certs, node_g = [], [], None
+    out, certs, node_g, conv_hist = [], [], None, None
     for a, b in parts:
         shared = all(np.array_equal(loads[a], l) for l in loads[a + 1:b])
         eng = AdmmEnsemble(np.asarray(cost, float), recs[a:b], loads[a] if shared else np.stack(loads[a:b]),
                            np.arange(len(res)), R_res, kappa=kappa, vset=vset, vlow=vlow, vhigh=vhigh, mode=mode,
                            device=device, op=operator, feeder=feeder)
-        d = eng.run(iter_max)
+        if want_conv:
+            # the history in the caller's residence order, into the scenarios' columns of the one buffer
+            eng.run(iter_max, history="device")
+            if conv_hist is None:
+                conv_hist = torch.empty(iter_max, len(res), len(recs), dtype=torch.float32, device=eng.dev)
+            inv = torch.from_numpy(np.ascontiguousarray(eng.inv_perm, dtype=np.int64)).to(eng.dev)
+            conv_hist[:, :, a:b] = eng.diff_history.view(iter_max, len(res), b - a).index_select(1, inv)
+            eng.diff_history = None
+            d = conv_hist[:, :, a:b].permute(2, 0, 1).cpu().numpy()
+        else:
+            d = eng.run(iter_max)
         P_sch, S, C = eng.result()
         for s in range(b - a):
             out.append(({k + 1: {h: float(d[s, k, i]) for i, h in enumerate(res)} for k in range(iter_max)},
@@ -211,7 +238,11 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
                 node_g = torch.empty(len(recs), eng.M, T, dtype=torch.float64, device=eng.dev)
             eng.node_sums(out=node_g[a:b])
         del eng
-    return answer(out, certs, node_g)
+    conv = None
+    if want_conv:
+        conv = convergence.convergence_report_device(conv_hist.view(iter_max, -1), return_convergence, len(recs), None,
+                                                     None, convergence_groups, convergence_patience)
+    return answer(out, certs, node_g, conv)
 
 
 def solve_residences(tariff, homes, device="cuda:0"):

@@ -105,7 +105,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, bills=False, **opt):
+              across=False, bills=False, convergence=None, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -137,7 +137,11 @@ class REVS:
         device.  bills=True: StudyReport.bills, the bills.BillReport of the study's rows (the residences) under
         `tariff`: every scenario's bills, their deviation from the individual schedule of the same (adoption, rating,
         seed) -- base[s] is that row, -1 without one -- and the records over each scenario's EV homes, pooled by the
-        report's groups; on the device_report path from the buffer on the device."""
+        report's groups; on the device_report path from the buffer on the device.  convergence=eps (with ensemble=True):
+        StudyReport.convergence, the convergence.ConvergenceReport of the distributed scenarios' residual histories at
+        that eps, from the ensembles' histories on the device (solve_ADMM_many(return_convergence=eps)): its scenarios
+        are the distributed ones in label order, `groups` their ids among the report's groups, pooled (G, iterations)
+        by them -- a group without a distributed scenario has empty records."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -149,6 +153,8 @@ class REVS:
             raise ValueError(f"REVS.study: unknown group key or method {unknown[0]!r}")
         if certify and not ensemble:
             raise ValueError("REVS.study: certify=True certifies the scenarios of an ensemble together: pass ensemble=True")
+        if convergence is not None and not ensemble:
+            raise ValueError("REVS.study: convergence=eps reports from the histories of an ensemble: pass ensemble=True")
         if device_report and not ensemble:
             raise ValueError("REVS.study: device_report=True reports from the state of an ensemble: pass ensemble=True")
         res = [n for n in dist if dist.nodes[n]["label"] == "H"]
@@ -182,12 +188,19 @@ class REVS:
                         else:
                             P_res = self.get_individual_optimal(tariff, homes)[0]
                         profiles.append(np.array([P_res[h] for h in res], np.float64))
+        conv_rep = None
         if deferred:
             sols = solve_ADMM_many([h for _, h in deferred], dist, tariff, None, kappa=opt.get("kappa", 5.0),
                                    iter_max=opt.get("max_iterations", 15), vset=opt.get("v0", 1.03),
                                    vlow=opt.get("vlow", 0.95), vhigh=opt.get("vhigh", 1.05),
                                    mode=opt.get("mode", "binary"), device=self.device, feeder=feeder,
-                                   return_certificates=certify, return_node_sums=device_report)
+                                   return_certificates=certify, return_node_sums=device_report,
+                                   return_convergence=convergence,
+                                   convergence_groups=self._deferred_groups(labels, keys, [i for i, _ in deferred]),
+                                   convergence_patience=opt.get("patience", 8))
+            if convergence is not None:
+                *head, conv_rep = sols
+                sols = tuple(head) if len(head) > 1 else head[0]
             node_g = None
             if device_report:                    # (solutions[, certificates], node sums)
                 *head, node_g = sols
@@ -219,6 +232,7 @@ class REVS:
                                          arrays=opt.get("arrays", False), across=across)
             if bills:
                 rep.bills = bill_report_device(buf, tariff, **bill_kw)
+            rep.convergence = conv_rep
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -227,7 +241,16 @@ class REVS:
                               arrays=opt.get("arrays", False), device=self.device, across=across)
         if bills:
             rep.bills = bill_report(np.stack(profiles), tariff, device=self.device, **bill_kw)
+        rep.convergence = conv_rep
         return labels, rep
+
+    @staticmethod
+    def _deferred_groups(labels, keys, which):
+        """The study's group ids (distinct combinations of the label keys, in order of first appearance over ALL
+        scenarios) of the scenarios `which`."""
+        combos = [tuple(lab[k] for k in keys) for lab in labels]
+        order = list(dict.fromkeys(combos))
+        return [order.index(combos[i]) for i in which]
 
     def result_frames(self, demand, dist, community=None, start=11, end=23, shift=6, rating=None):
         """The two long tables the reference's box plots are drawn from (drawing.py:125-176, boxplot_flow /

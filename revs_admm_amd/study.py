@@ -77,7 +77,8 @@ class StudyReport:
     groups).  band_counts: (S, T, B) int32, the nodes of `nodes` with volt <= bands[b] (cumulative; NaNs never
     counted).  flow, loading, volt: (S, nodes, T) float64 or None (arrays=False).  groups: (S,) int, -1: in no pool.
     node_p: (S, M, T) float64, the profiles reported.  across: the AcrossReport of across=True, else None.  bills: the
-    bills.BillReport of REVS.study(bills=True), else None."""
+    bills.BillReport of REVS.study(bills=True), else None.  convergence: the convergence.ConvergenceReport of
+    REVS.study(convergence=eps) over the ensemble's scenarios, else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -94,6 +95,7 @@ class StudyReport:
     vmax: float
     across: AcrossReport | None = None
     bills: object | None = None
+    convergence: object | None = None
 
     @property
     def n_groups(self):
