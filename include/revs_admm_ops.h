@@ -8,7 +8,8 @@
  * (tests/test_gpu_newton.py, test_gpu_operator.py) call each of them against its numpy restatement.  The reports'
  * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled),
  * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input)
- * and revs_net_across (per node and per line, the statistics across the scenarios of a group).
+ * and revs_net_across (per node and per line, the statistics across the scenarios of a group), then the bill and the
+ * convergence report, and last revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -691,6 +692,41 @@ int revs_conv_report(int32_t S, int64_t n, int32_t K, const float *hist, int64_t
                      const int32_t *index, const int32_t *groups, int32_t G, double eps, int32_t patience,
                      revs_bill_summary_t *iter_rec, revs_bill_summary_t *pool_rec, revs_conv_res_t *res_rec,
                      revs_conv_run_t *run_rec, revs_bill_summary_t *settle_rec, void *scratch, void *stream);
+
+/* ---- rule schedules: what a charger does when nobody schedules it ----------------------------------------------------
+ * The "before" of the reference's study (test-altered-profile.py:35-46: constant charger power from the arrival slot on,
+ * laid over the base load), in closed form from the residence records (csrc/rule_kernels.hip).
+ *
+ * homes revs_home_t[rows]; load, p_out, g_out float[rows][T]; soc_out float[rows][T + 1]; status_out int32[rows]; all
+ * contiguous.  A row is one (residence, scenario) record: an ensemble's float[n][S][T] is rows = n S as it stands.  Any
+ * output may be NULL (not wanted: it then costs nothing), not all four; load may be NULL only if g_out is.
+ *
+ * Per row, the record's fields widened to double, every double operation rounded on its own:
+ *   ws = clamp(start, 0, T), we = clamp(end, 0, T), W = max(we - ws, 0); window position j = t - ws.
+ *   ev == 0: p = 0, soc = 0 (all T + 1 entries), g = load, status 0.
+ *   Own rows empty (nmax < 0, or integral and nmin > nmax): p = 0, soc[t] = initial, status 1.
+ *   integral != 0 (on/off charger): k = nmin (REVS_FILL_TARGET) or nmax (REVS_FILL_FULL) as the record holds them,
+ *     on = min(k, W); ASAP: positions j < on at `rating`; ALAP: positions j >= W - on; status 1 iff on < nmin.
+ *   integral == 0 (continuous charger): E_lo = (max(0.9, initial) - initial) capacity, E_hi = (1.0 - initial) capacity,
+ *     E = E_lo / E_hi by the fill, D = min(E, rating W), status 1 iff D < E_lo.
+ *     ASAP / ALAP: kf = min(floor(D / rating), W) (0 where rating <= 0), rem = D - kf rating (0 where kf == W, and
+ *       where the rounded quotient reached an integer from below: never a negative power);
+ *       ASAP: j < kf at `rating`, j == kf at (float) rem; ALAP: j >= W - kf at `rating`, j == W - kf - 1 at (float) rem.
+ *     EVEN: (float)(D / W) at every window position (W > 0).
+ *   soc[0] = initial, soc[t] = (float)(initial + E_before(t) / capacity), E_before(t) the energy of the slots before t
+ *     in closed form -- (full slots before t) rating, plus rem once the partial slot lies before t; EVEN: (window slots
+ *     before t) (D / W) -- no scan.  g[t] = load[t] + p[t], one float addition.
+ * Status bit 1 carries the sweep's "no solution" meaning: the EV leaves below the state of charge the model demands.
+ * Enqueues only (capturable); the same bits from call to call.  REVS_EINVAL before any launch: rows < 1 (or rows T
+ * beyond one launch's grid), T outside 1..REVS_MAX_T, null homes, an unknown policy or fill, REVS_RULE_EVEN with
+ * integral != 0, every output NULL, g_out without load. */
+#define REVS_RULE_ASAP  0   /* charge from the first window slot on: uncontrolled */
+#define REVS_RULE_ALAP  1   /* finish in the last window slot: last-minute         */
+#define REVS_RULE_EVEN  2   /* the same power in every window slot: trickle (continuous chargers only) */
+#define REVS_FILL_TARGET 0  /* deliver what the model demands: s_T >= 0.9 (nmin slots / E_lo) */
+#define REVS_FILL_FULL   1  /* charge to 100 %                         (nmax slots / E_hi) */
+int revs_rule_schedule(int64_t rows, int32_t T, const revs_home_t *homes, const float *load, int32_t policy, int32_t fill,
+                       int32_t integral, float *p_out, float *soc_out, float *g_out, int32_t *status_out, void *stream);
 
 #ifdef __cplusplus
 }

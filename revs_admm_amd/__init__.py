@@ -4,6 +4,7 @@
     revs_fixture   REVS class (read_inputs / get_*_optimal) over the engine
     engine         array-level AdmmEngine: device buffers + kernel driver
     network        AdmmEngine.network_report: line flows / loading, node voltages and their box-plot numbers
+    baselines      rule schedules: uncontrolled / last-minute / trickle charging from the residence records
     drawing        the reference's compute_flows / compute_voltage over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

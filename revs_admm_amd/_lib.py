@@ -284,6 +284,7 @@ SIGNATURES = {
     "revs_bill_study": (C.c_int, [_i32, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _p, _p]),
     "revs_conv_report_scratch": (_i64, [_i32, _i64, _i32, _i32]),
     "revs_conv_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _f64, _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_rule_schedule": (C.c_int, [_i64, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
@@ -291,6 +292,8 @@ DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 
 DUAL_AMAX_BIG = 512      # REVS_DUAL_AMAX_BIG
 ENS_MAX_COLS = 1024      # REVS_ENS_MAX_COLS: columns (scenarios x slots) of one dual Newton launch
 MAX_T = 192              # REVS_MAX_T: slots of a residence sweep, columns of a dense product
+RULE_ASAP, RULE_ALAP, RULE_EVEN = 0, 1, 2    # REVS_RULE_*: revs_rule_schedule's policies
+FILL_TARGET, FILL_FULL = 0, 1                # REVS_FILL_*
 
 _lib = None
 

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from ._lib import HOME_DTYPE, MODES, PDHG, check, ptr
+from .baselines import RuleScheduleMixin
 from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (re-exported)
 from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
 from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
@@ -199,7 +200,7 @@ def _on_current_stream(fn):
     return wrapped
 
 
-class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin):
+class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

@@ -180,6 +180,10 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsM
         d = hist[:k].view(k, n, S).permute(2, 0, 1).cpu().numpy()
         return np.ascontiguousarray(d[:, :, self.inv_perm])
 
+    def _rule_shape(self):
+        """rule_schedule()'s net load as the reports' profile= takes it: (n, S, T)."""
+        return (self.n_res, self.S_count, self.T_slot)
+
     # ---------------------------------------------------------------- state in / out
     def set_state(self, s, P_est, P_sch, G, iteration=None):
         """Load (P_est[k], P_sch[k], G[k]) of scenario s in the caller's residence order; the operator's multipliers stay

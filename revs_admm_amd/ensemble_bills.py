@@ -8,12 +8,13 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from . import bills
+from . import baselines, bills
 from ._lib import check, ptr
 
 
 class EnsembleBillsMixin:
-    def bill_report(self, baseline="individual", groups=None, ev_only=True, arrays=True) -> bills.BillReport:
+    def bill_report(self, baseline="individual", groups=None, ev_only=True, arrays=True,
+                    baseline_fill="target") -> bills.BillReport:
         """bills.BillReport of the S scenarios' schedules P_sch under the engine's tariff (the float32 prices the sweep
         runs on, widened).
 
@@ -21,6 +22,9 @@ class EnsembleBillsMixin:
                   (lpsolver.solve_residences on the device: one revs_residence_solve over all n S records).  The report
                   then has 2 S rows: the first S are the ensemble's scenarios, with base[s] = S + s, the last S the
                   baselines' bills, in no group and without a baseline themselves.
+                  "uncontrolled" / "last_minute" / "trickle" (baselines.POLICIES): the rule schedule of that name on the
+                  same records and loads, filled to `baseline_fill` ("target" / "full"), for the charger of the engine's
+                  mode -- ONE revs_rule_schedule over the n S records, its net load only; rows as for "individual".
                   None: bills only, S rows.  An (S, n, T) array in the caller's residence order: uploaded as float64,
                   rows S .. 2S - 1 as above.
         groups    None, or one integer per scenario (S of them): bills.bill_report_device's.
@@ -30,10 +34,14 @@ class EnsembleBillsMixin:
         bill / dev / keep and worst_index are in the caller's residence order, and every record is bit for bit what
         bills.bill_report gives on result()'s schedules.  The run's state is read, never written."""
         S, n, T = self.S_count, self.n_res, self.T_slot
-        individual = isinstance(baseline, str)
-        if individual and baseline != "individual":
-            raise ValueError(f'bill report: baseline must be "individual", None or an (S, n, T) array, got {baseline!r}')
-        if baseline is not None and not individual:
+        named = isinstance(baseline, str)
+        individual = named and baseline == "individual"
+        if named and not individual and baseline not in baselines.POLICIES:
+            raise ValueError(f'bill report: baseline must be "individual", one of {sorted(baselines.POLICIES)}, None or an '
+                             f'(S, n, T) array, got {baseline!r}')
+        if named and not individual:
+            baselines.rule_args(baseline, baseline_fill, self.mode)                      # (before anything is launched)
+        if baseline is not None and not named:
             baseline = np.asarray(baseline, np.float64)
             if baseline.shape != (S, n, T):
                 raise ValueError(f"bill report: a baseline must be (S, n, T) = {(S, n, T)} in the caller's residence "
@@ -55,6 +63,10 @@ class EnsembleBillsMixin:
             p, g, soc = torch.empty(n * S, T, **f32), torch.empty(n * S, T, **f32), torch.empty(n * S, T + 1, **f32)
             check(lib.revs_residence_solve(n * S, T, ptr(self.cost), ptr(self.homes), ptr(self.load), ptr(p), ptr(soc),
                                            ptr(g), st), "revs_residence_solve")
+            check(lib.revs_bill_rows(S, n, T, ptr(g), 0, T, S * T, ptr(d_tariff), ptr(d_bill[S:]), st), "revs_bill_rows")
+        elif named:
+            g = baselines.rule_schedule_device(self.homes, self.load, baseline, baseline_fill, self.mode, want="g",
+                                               stream=st)[2]
             check(lib.revs_bill_rows(S, n, T, ptr(g), 0, T, S * T, ptr(d_tariff), ptr(d_bill[S:]), st), "revs_bill_rows")
         elif baseline is not None:
             d_base = self._up(baseline[:, self.perm, :])

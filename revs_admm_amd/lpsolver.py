@@ -21,7 +21,7 @@ from . import _lib
 from .engine import AdmmEngine, OperatorOptions, pack_homes, residence_solve
 
 __all__ = ["compute_Rmat", "solve_ADMM", "solve_ADMM_many", "split_scenarios", "solve_residence", "solve_residences",
-           "solve_central", "homes_to_arrays", "feeder_arrays", "feeder_of"]
+           "solve_uncontrolled", "solve_central", "homes_to_arrays", "feeder_arrays", "feeder_of"]
 
 
 def compute_Rmat(graph) -> np.ndarray:
@@ -251,6 +251,23 @@ def solve_residences(tariff, homes, device="cuda:0"):
     load, rec = homes_to_arrays(homes, keys)
     p, s, g = residence_solve(np.asarray(tariff, float), rec, load, device)
     return {h: (p[i], s[i], g[i]) for i, h in enumerate(keys)}
+
+
+def solve_uncontrolled(homes, T=None, policy="uncontrolled", fill="target", charger="binary", device="cuda:0",
+                       return_status=False):
+    """The rule schedule of every residence of a `homes` dict (baselines.rule_schedule: "uncontrolled" -- the charger runs
+    from the first slot of its window on, test-altered-profile.py:35-46 --, "last_minute" or "trickle"; fill "target" /
+    "full"; charger "binary" / "continuous") -> {h: (p, s, g)}, as solve_residences.  T: the number of slots, checked
+    against the LOADs when given.  return_status=True: -> (that dict, {h: status}), status 1 where the EV leaves below
+    the state of charge the model demands."""
+    from .baselines import rule_schedule
+    keys = list(homes)
+    load, rec = homes_to_arrays(homes, keys)
+    if T is not None and load.shape[1] != int(T):
+        raise ValueError(f"solve_uncontrolled: LOAD has {load.shape[1]} slots, T = {T}")
+    p, s, g, status = rule_schedule(rec, load, policy, fill, charger, device)
+    sol = {h: (p[i], s[i], g[i]) for i, h in enumerate(keys)}
+    return (sol, {h: int(status[i]) for i, h in enumerate(keys)}) if return_status else sol
 
 
 def solve_residence(tariff, data, path=None):

@@ -14,7 +14,9 @@ import numpy as np
 
 from .extract import (GetCommunity, GetDistNet, GetHomeLoad, GetTariff, combine_result,
                       get_homes_ev_param)
-from .lpsolver import solve_ADMM, solve_ADMM_many, solve_central, solve_residences
+from .lpsolver import solve_ADMM, solve_ADMM_many, solve_central, solve_residences, solve_uncontrolled
+
+RULE_METHODS = ("uncontrolled", "last_minute", "trickle")       # baselines.POLICIES: REVS.study's rule methods
 
 
 class REVS:
@@ -80,6 +82,22 @@ class REVS:
                        kwargs.get("adoption", 90), kwargs.get("rating", 4800), kwargs.get("seed"))
         return Pres, Pev, soc
 
+    def get_uncontrolled(self, tariff, homes, save=False, **kwargs):
+        """The schedule nobody optimised (test-altered-profile.py:35-46: the charger runs from the arrival slot on)
+        -> (Pres, Pev, soc) like get_individual_optimal.  **kwargs: policy ("uncontrolled" / "last_minute" / "trickle"),
+        fill ("target" / "full"), charger ("binary" / "continuous") of lpsolver.solve_uncontrolled, and the labels
+        `save` files the result under.  The tariff plays no part in a rule schedule; its length is the number of slots."""
+        sol = solve_uncontrolled(homes, len(tariff), policy=kwargs.get("policy", "uncontrolled"),
+                                 fill=kwargs.get("fill", "target"), charger=kwargs.get("charger", "binary"),
+                                 device=self.device)
+        Pev = {h: sol[h][0] for h in homes}
+        soc = {h: sol[h][1] for h in homes}
+        Pres = {h: sol[h][2] for h in homes}
+        if save:
+            self._save(combine_result(Pres, Pev, soc, kwargs.get("ev_homes")),
+                       kwargs.get("adoption", 90), kwargs.get("rating", 4800), kwargs.get("seed"))
+        return Pres, Pev, soc
+
     def get_centralized_optimal(self, tariff, homes, dist, save=False, **kwargs):
         """revs_fixture.py:225-249."""
         Pev, soc, Pres = solve_central(tariff, homes, dist, None, kwargs.get("v0", 1.03),
@@ -112,7 +130,11 @@ class REVS:
 
         For every adoption (%), rating (W) and seed -- in that nesting -- the EV homes are drawn from `community`
         exactly as read_inputs draws them, then every method of `methods` is solved; labels[s] = dict(method,
-        adoption, rating, seed) of scenario s.  ONE study_report over all schedules' P_res follows, with
+        adoption, rating, seed) of scenario s.  Methods: "distributed", "individual" and the rule schedules
+        "uncontrolled", "last_minute", "trickle" (baselines.py; filled to opt rule_fill, "target" by default, for the
+        charger of opt mode; labels[s]["unserved"] is then the number of residences whose EV leaves below the state of
+        charge the model demands), labelled, grouped and pooled like any method.
+        ONE study_report over all schedules' P_res follows, with
         nodes=community, the graph's line ratings, and pools by `group_by`: one label key or a tuple of them, a group
         being one distinct combination in order of first appearance ("method" at one adoption and rating:
         compare_method; "adoption" at one method: compare_adoption; "rating": compare_rating; ("method", "adoption"):
@@ -135,8 +157,9 @@ class REVS:
         line the statistics across each group's scenarios (study.AcrossReport: in how many seeds a node goes below a
         band at some hour, its median daily minimum, the slots in violation) -- on either path from the arrays on the
         device.  bills=True: StudyReport.bills, the bills.BillReport of the study's rows (the residences) under
-        `tariff`: every scenario's bills, their deviation from the individual schedule of the same (adoption, rating,
-        seed) -- base[s] is that row, -1 without one -- and the records over each scenario's EV homes, pooled by the
+        `tariff`: every scenario's bills, their deviation from the schedule of method opt bill_base (default
+        "individual") of the same (adoption, rating, seed) -- base[s] is that row, -1 without one -- and the records
+        over each scenario's EV homes, pooled by the
         report's groups; on the device_report path from the buffer on the device.  convergence=eps (with ensemble=True):
         StudyReport.convergence, the convergence.ConvergenceReport of the distributed scenarios' residual histories at
         that eps, from the ensembles' histories on the device (solve_ADMM_many(return_convergence=eps)): its scenarios
@@ -148,7 +171,10 @@ class REVS:
         from .bills import bill_report, bill_report_device
         keys = (group_by,) if isinstance(group_by, str) else tuple(group_by)
         unknown = [k for k in keys if k not in ("method", "adoption", "rating", "seed")]
-        unknown += [m for m in methods if m not in ("distributed", "individual")]
+        unknown += [m for m in methods if m not in ("distributed", "individual") + RULE_METHODS]
+        bill_base = opt.get("bill_base", "individual")
+        if bill_base not in ("distributed", "individual") + RULE_METHODS:
+            unknown.append(bill_base)
         if unknown:
             raise ValueError(f"REVS.study: unknown group key or method {unknown[0]!r}")
         if certify and not ensemble:
@@ -185,6 +211,13 @@ class REVS:
                             continue
                         if method == "distributed":
                             P_res = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[0]
+                        elif method in RULE_METHODS:
+                            sol, status = solve_uncontrolled(homes, len(tariff), policy=method,
+                                                             fill=opt.get("rule_fill", "target"),
+                                                             charger=opt.get("mode", "binary"), device=self.device,
+                                                             return_status=True)
+                            P_res = {h: sol[h][2] for h in homes}
+                            labels[-1]["unserved"] = sum(1 for h in res if status[h] & 1)
                         else:
                             P_res = self.get_individual_optimal(tariff, homes)[0]
                         profiles.append(np.array([P_res[h] for h in res], np.float64))
@@ -216,7 +249,7 @@ class REVS:
         bill_kw = None
         if bills:
             case = lambda lab: (lab["adoption"], lab["rating"], lab["seed"])
-            ind = {case(lab): s for s, lab in enumerate(labels) if lab["method"] == "individual"}
+            ind = {case(lab): s for s, lab in enumerate(labels) if lab["method"] == bill_base}
             bill_kw = dict(base=[ind.get(case(lab), -1) for lab in labels], groups=[order.index(c) for c in combos],
                            keep=np.array([np.isin(res, ev) for ev in owners]), arrays=opt.get("arrays", False))
         if device_report:
