@@ -9,7 +9,8 @@
  * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled),
  * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input)
  * and revs_net_across (per node and per line, the statistics across the scenarios of a group), then the bill and the
- * convergence report, and last revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at.
+ * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at, and last
+ * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -727,6 +728,58 @@ int revs_conv_report(int32_t S, int64_t n, int32_t K, const float *hist, int64_t
 #define REVS_FILL_FULL   1  /* charge to 100 %                         (nmax slots / E_hi) */
 int revs_rule_schedule(int64_t rows, int32_t T, const revs_home_t *homes, const float *load, int32_t policy, int32_t fill,
                        int32_t integral, float *p_out, float *soc_out, float *g_out, int32_t *status_out, void *stream);
+
+/* ---- load-profile report: demand per slot, peaks and diversity of a schedule, by class of residence ----------------
+ * The reference's demand curve (test-altered-profile.py:25-57: the residences' load per slot, with and without EVs),
+ * from a schedule where it lies on the device (csrc/load_profile_kernels.hip).
+ *
+ * g: device float; element (residence i, scenario s, slot t) at i stride_i + s stride_s + t, strides in elements,
+ * accepted under exactly revs_bill_rows' rule (an ensemble's float[n][S][T]: stride_s = T, stride_i = S T; one engine:
+ * S = 1).  cls: device uint8[S][n]; cls[s][i] < C is the class of residence i in scenario s, any other value leaves it
+ * out of every set.  Q = C + 1 sets: set q < C is class q, set C every residence with a class.  cls = NULL needs C = 0:
+ * every residence is in the one set.  index_of_row: device int32[n] in 0..2^31 - 2, the caller-side index of row i
+ * (NULL: i).  groups: HOST int32[S] in -1..G-1, as revs_bill_study's.
+ *   slot_rec[s][q][t] (revs_bill_summary_t[S][Q][T]): the record over the set's values at slot t, widened to double, by
+ *   revs_conv_report's iter_rec rules -- a value that is not finite counts in n_nan and is left out; quartiles selected
+ *   exactly (radix select over the floats' ordered keys) and interpolated as numpy.percentile's, no fused multiply-add;
+ *   whiskers and fliers as revs_net_summary_t's; -0.0 orders and is reported as +0.0; n_above counts the values > above
+ *   (any double but a NaN); worst_index: the largest value, ties to the lowest caller-side index; worst_scenario = s;
+ *   total: a sum in a fixed order, the same bits from call to call; an empty set: NaN statistics, indices -1, counts 0;
+ *   reserved0 is 0.
+ *   peak_rec[s][q] ([S][Q]): the same record over x_i = max over t of g[i][s][t], each residence's own daily peak; a
+ *   row that holds a value that is not finite gives a NaN and counts in n_nan.
+ *   day_rec[s][q] (revs_profile_day_t[S][Q]): from A[t] = slot_rec[s][q][t].total over the slots with count > 0, by the
+ *   formulas beside the fields; a function of the records the same call computes, whether they are asked for or not.
+ *   Where no slot holds a value the doubles are NaN, the slot indices -1 and slots 0.
+ *   pool_slot_rec[gid][q][t] / pool_peak_rec[gid][q] ([G][Q][T] / [G][Q]): the same rules over the multiset of all member
+ *   scenarios' values; total: the members' totals added in scenario order; the worst entry: the largest value, then the
+ *   lowest scenario, then the lowest index.  A pool of one scenario repeats that scenario's record byte for byte.
+ * Any output may be NULL, not all; the others are the same bytes.  Reads g, cls, index_of_row; writes the outputs and the
+ * scratch.  A fixed sequence of launches on one stream, the residences split over workgroups (integer histograms merged
+ * through integer atomics, partial sums folded in a fixed order); no grid-wide barrier, no floating-point atomics; the
+ * call only enqueues.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; n < 1 or
+ * S n >= 2^31; C outside 0..REVS_PROFILE_MAX_CLASSES; cls and C disagreeing about NULL / 0; strides revs_bill_rows would
+ * refuse; above a NaN; a null g; G outside 0..S; groups NULL with G > 0; a group id outside -1..G-1; a pool output with
+ * G == 0; a null or misaligned (16 bytes) scratch; every output NULL.  scratch: revs_load_profile_scratch bytes (<= 0
+ * for sizes the report refuses).  revs_load_profile_chunk: the residences one workgroup of a walk owns. */
+#define REVS_PROFILE_MAX_CLASSES 4
+typedef struct {
+    double peak, valley;              /* largest / smallest slot total of the set's aggregate profile */
+    double energy;                    /* sum over t of those totals, t ascending from +0.0 (kW x slots) */
+    double load_factor;               /* (energy / slots) / peak, each operation rounded on its own */
+    double sum_peaks;                 /* peak_rec's total: the residences' own daily peaks added up */
+    double diversity;                 /* sum_peaks / peak */
+    int32_t peak_slot, valley_slot;   /* earliest slot on ties; -1: no slot holds a value */
+    int32_t slots, reserved;          /* slots with count > 0; 0 */
+} revs_profile_day_t;                 /* 64 bytes */
+int32_t revs_load_profile_chunk(void);
+int64_t revs_load_profile_scratch(int32_t S, int64_t n, int32_t T, int32_t C, int32_t G);
+int revs_load_profile(int32_t S, int64_t n, int32_t T, const float *g, int64_t stride_s, int64_t stride_i,
+                      const uint8_t *cls, int32_t C, const int32_t *index_of_row,
+                      const int32_t *groups, int32_t G, double above,
+                      revs_bill_summary_t *slot_rec, revs_bill_summary_t *peak_rec, revs_profile_day_t *day_rec,
+                      revs_bill_summary_t *pool_slot_rec, revs_bill_summary_t *pool_peak_rec,
+                      void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

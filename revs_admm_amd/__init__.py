@@ -5,6 +5,7 @@
     engine         array-level AdmmEngine: device buffers + kernel driver
     network        AdmmEngine.network_report: line flows / loading, node voltages and their box-plot numbers
     baselines      rule schedules: uncontrolled / last-minute / trickle charging from the residence records
+    load_profile   the demand curve of a schedule: load per slot by class of residence, peaks, load factor, diversity
     drawing        the reference's compute_flows / compute_voltage over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

@@ -146,6 +146,13 @@ assert CONV_RES_DTYPE.itemsize == 24
 CONV_RUN_DTYPE = np.dtype([("converged_at", "<i4"), ("last_above", "<i4"), ("n_unsettled", "<i4"), ("n_never", "<i4")])
 assert CONV_RUN_DTYPE.itemsize == 16
 
+# numpy mirror of revs_profile_day_t (include/revs_admm_ops.h)
+PROFILE_DAY_DTYPE = np.dtype([("peak", "<f8"), ("valley", "<f8"), ("energy", "<f8"), ("load_factor", "<f8"),
+                              ("sum_peaks", "<f8"), ("diversity", "<f8"), ("peak_slot", "<i4"), ("valley_slot", "<i4"),
+                              ("slots", "<i4"), ("reserved", "<i4")])
+assert PROFILE_DAY_DTYPE.itemsize == 64
+PROFILE_MAX_CLASSES = 4  # REVS_PROFILE_MAX_CLASSES
+
 
 class RevsError(RuntimeError):
     pass
@@ -285,6 +292,10 @@ SIGNATURES = {
     "revs_conv_report_scratch": (_i64, [_i32, _i64, _i32, _i32]),
     "revs_conv_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _p, _p, _p, _i32, _f64, _i32, _p, _p, _p, _p, _p, _p, _p]),
     "revs_rule_schedule": (C.c_int, [_i64, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p, _p]),
+    "revs_load_profile_chunk": (_i32, []),
+    "revs_load_profile_scratch": (_i64, [_i32, _i64, _i32, _i32, _i32]),
+    "revs_load_profile": (C.c_int, [_i32, _i64, _i32, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _f64, _p, _p, _p, _p, _p, _p,
+                                    _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -27,6 +27,7 @@ from ._lib import HOME_DTYPE, MODES, PDHG, check, ptr
 from .baselines import RuleScheduleMixin
 from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (re-exported)
 from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
+from .load_profile import LoadProfileMixin
 from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
@@ -200,7 +201,8 @@ def _on_current_stream(fn):
     return wrapped
 
 
-class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin):
+class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
+                 LoadProfileMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

@@ -123,7 +123,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, bills=False, convergence=None, **opt):
+              across=False, bills=False, convergence=None, load_profile=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -164,7 +164,13 @@ class REVS:
         StudyReport.convergence, the convergence.ConvergenceReport of the distributed scenarios' residual histories at
         that eps, from the ensembles' histories on the device (solve_ADMM_many(return_convergence=eps)): its scenarios
         are the distributed ones in label order, `groups` their ids among the report's groups, pooled (G, iterations)
-        by them -- a group without a distributed scenario has empty records."""
+        by them -- a group without a distributed scenario has empty records.  load_profile=True:
+        StudyReport.load_profile, the load_profile.LoadProfileReport of every method's schedules (the residences' rows),
+        classes "without EV" / "with EV" by each scenario's own EV homes, pooled by the report's groups, followed by one
+        row per (adoption, rating, seed) case with the base load "load" under that case's EV homes, in no pool
+        (StudyReport.load_profile_rows names every row; opt profile_above: n_above's threshold, 0.0 by default).  The
+        report works on float32, the precision of the engines' state; on the device_report path it reads the buffer on
+        the device, otherwise the profiles are uploaded once."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -252,6 +258,17 @@ class REVS:
             ind = {case(lab): s for s, lab in enumerate(labels) if lab["method"] == bill_base}
             bill_kw = dict(base=[ind.get(case(lab), -1) for lab in labels], groups=[order.index(c) for c in combos],
                            keep=np.array([np.isin(res, ev) for ev in owners]), arrays=opt.get("arrays", False))
+        prof_kw = None
+        if load_profile:
+            case = lambda lab: (lab["adoption"], lab["rating"], lab["seed"])
+            cases = list(dict.fromkeys(case(lab) for lab in labels))
+            first = [next(s for s, lab in enumerate(labels) if case(lab) == c) for c in cases]
+            base_load = np.array([all_homes[h] for h in res], np.float32)
+            prof_kw = dict(classes=np.array([np.isin(res, owners[s]) for s in list(range(len(labels))) + first], np.int64),
+                           n_classes=2, names=("without EV", "with EV"), above=opt.get("profile_above", 0.0),
+                           groups=[order.index(c) for c in combos] + [-1] * len(cases))
+            prof_rows = [dict(lab) for lab in labels] + [dict(method="load", adoption=c[0], rating=c[1], seed=c[2])
+                                                         for c in cases]
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -266,6 +283,12 @@ class REVS:
             if bills:
                 rep.bills = bill_report_device(buf, tariff, **bill_kw)
             rep.convergence = conv_rep
+            if load_profile:
+                from .load_profile import load_profile_report_device
+                d_load = torch.from_numpy(base_load).to(buf.device)
+                g = torch.cat([buf.float(), d_load[None].expand(len(cases), -1, -1)]).permute(1, 0, 2).contiguous()
+                rep.load_profile = load_profile_report_device(g, **prof_kw)
+                rep.load_profile_rows = prof_rows
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -275,6 +298,11 @@ class REVS:
         if bills:
             rep.bills = bill_report(np.stack(profiles), tariff, device=self.device, **bill_kw)
         rep.convergence = conv_rep
+        if load_profile:
+            from .load_profile import load_profile_report
+            g = np.concatenate([np.stack(profiles).astype(np.float32), np.broadcast_to(base_load, (len(cases),) + base_load.shape)])
+            rep.load_profile = load_profile_report(g, device=self.device, **prof_kw)
+            rep.load_profile_rows = prof_rows
         return labels, rep
 
     @staticmethod

@@ -78,7 +78,10 @@ class StudyReport:
     counted).  flow, loading, volt: (S, nodes, T) float64 or None (arrays=False).  groups: (S,) int, -1: in no pool.
     node_p: (S, M, T) float64, the profiles reported.  across: the AcrossReport of across=True, else None.  bills: the
     bills.BillReport of REVS.study(bills=True), else None.  convergence: the convergence.ConvergenceReport of
-    REVS.study(convergence=eps) over the ensemble's scenarios, else None."""
+    REVS.study(convergence=eps) over the ensemble's scenarios, else None.  load_profile: the
+    load_profile.LoadProfileReport of REVS.study(load_profile=True), else None; its rows are load_profile_rows: the
+    study's labels, then one row dict(method="load", adoption, rating, seed) per case -- the base load under that case's
+    EV homes."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -96,6 +99,8 @@ class StudyReport:
     across: AcrossReport | None = None
     bills: object | None = None
     convergence: object | None = None
+    load_profile: object | None = None
+    load_profile_rows: list | None = None
 
     @property
     def n_groups(self):
