@@ -9,8 +9,9 @@
  * launches close the file: revs_net_node_sums / revs_net_report (one schedule), revs_net_study (S schedules, pooled),
  * revs_net_node_sums_many (the node sums of an ensemble's S scenarios from its own layout into revs_net_study's input)
  * and revs_net_across (per node and per line, the statistics across the scenarios of a group), then the bill and the
- * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at, and last
- * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence.
+ * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at,
+ * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence -- and
+ * last revs_charge_report: what the chargers do, per EV and per slot.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -780,6 +781,68 @@ int revs_load_profile(int32_t S, int64_t n, int32_t T, const float *g, int64_t s
                       revs_bill_summary_t *slot_rec, revs_bill_summary_t *peak_rec, revs_profile_day_t *day_rec,
                       revs_bill_summary_t *pool_slot_rec, revs_bill_summary_t *pool_peak_rec,
                       void *scratch, void *stream);
+
+/* ---- charging report: what the chargers do, per EV and per slot ---------------------------------------------------
+ * The second of the three arrays every solver entry of the reference returns (ev_schedule; AdmmEngine.S, an ensemble's
+ * float[n][S][T], the p of revs_rule_schedule), read where it lies (csrc/charge_kernels.hip).
+ *
+ * p: device float; element (residence i, scenario s, slot t) at i stride_i + s stride_s + t, strides in elements,
+ * accepted under exactly revs_bill_rows' rule.  homes: device revs_home_t[n][S], the record of (i, s) at i S + s.
+ * tariff: device double[T], or NULL: every cost is then a NaN.
+ *
+ * Per row, the record's fields widened to double, every operation rounded on its own, no fused multiply-add:
+ *   ws = clamp(start, 0, T), we = clamp(end, 0, T) (revs_rule_schedule's window).
+ *   slot t is ON iff (double) p[t] > on_frac * (double) rating (a NaN is off); FULL iff on and p[t] >= rating.
+ *   energy = sum over all T slots of (double) p[t], one accumulator from +0.0, t ascending; cost = sum of
+ *   tariff[t] * (double) p[t] in the same way (revs_bill_rows' rule); soc_end = (float)(initial + energy / capacity).
+ *   n_on, n_full: the counts; first_on, last_on: slot indices, -1 when never on; sessions: the on slots whose
+ *   predecessor is off (or t == 0); wait = first_on - ws (it may be negative), -1 when never on; n_outside: the on slots
+ *   with t < ws or t >= we.  flags: bit 0 ev != 0; bit 1 under target, max(0.9, initial) - (initial + energy / capacity)
+ *   > short_tol; bit 2 some p[t] is not finite (the doubles are then what IEEE gives).
+ *   row_rec is [S][n].  A row with ev == 0 gets zeros, -1 in first_on, last_on and wait, flags 0, whatever p holds (its
+ *   p is not read).
+ * slot_rec[s][t] ([S][T]) counts over the rows with ev != 0: n_ev (the same in every slot), n_plugged (ws <= t < we),
+ *   n_on, n_full, n_starts (sessions that begin at t); power: the sum of (double) p[t] in a fixed order, the same bits
+ *   from call to call.
+ * day_rec[s] ([S]), a function of the records above whether or not they are asked for: peak_power / peak_power_slot
+ *   and peak_on / peak_on_slot by a scan from slot 0 that moves on `>` only (the earliest slot wins ties; a NaN power
+ *   never wins, one at slot 0 stays); both slots -1 without an EV; energy: the slots' power added, t ascending from
+ *   +0.0; coincidence = peak_on / n_ev (NaN without an EV); cost: the EV rows' costs added in a fixed order; n_under /
+ *   n_never / n_interrupted / n_outside: the EV rows with flags bit 1 / n_on == 0 / sessions > 1 / n_outside > 0.
+ * hist: int32[S][3][T + 1] over the EV rows: [0] of n_on, [1] of wait (rows never on or with a negative wait are not
+ *   counted), [2] of sessions.
+ * val_out: double[4][S][n]: energy, cost, (double) soc_end, (double) wait; a NaN where the row is no EV, where flags
+ *   bit 2 is set, and for wait where the charger is never on.  keep_out: uint8[S][n], 1 for EV rows without bit 2.  The
+ *   two are what revs_bill_study (base = -1) takes: the box-plot records come from that selection.
+ * Any output may be NULL, not all; the others are the same bytes.  Reads p, homes, tariff; writes the outputs and the
+ * scratch.  A thread owns a row and walks its slots in chunks of revs_charge_report_chunk() staged through LDS; the
+ * scenario is grid.y.  Slot counts: wavefront ballots, LDS counters, one global integer atomic per (workgroup, slot,
+ * counter); power and cost: per-workgroup partials in the scratch, folded in a fixed order by a second kernel (32 runs
+ * of consecutive workgroups, then the runs in order); a third derives the day records.  No floating-point atomics, no grid-wide barrier, a fixed sequence of launches on one
+ * stream; the call only enqueues.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; T outside
+ * 1..REVS_MAX_T; n < 1 or S n >= 2^31; strides revs_bill_rows would refuse; a null p or homes; on_frac or short_tol
+ * negative or a NaN; a null or misaligned (16 bytes) scratch; every output NULL.  scratch: revs_charge_report_scratch
+ * bytes (<= 0 for sizes the report refuses). */
+typedef struct {
+    double energy, cost;
+    float soc_end, reserved0;
+    int32_t n_on, n_full, first_on, last_on, sessions, wait, n_outside, flags;
+    int32_t reserved[2];
+} revs_charge_row_t;                  /* 64 bytes */
+typedef struct {
+    int32_t n_ev, n_plugged, n_on, n_full, n_starts, reserved;
+    double power;
+} revs_charge_slot_t;                 /* 32 bytes */
+typedef struct {
+    double peak_power, energy, coincidence, cost;
+    int32_t peak_on, peak_on_slot, peak_power_slot, n_ev, n_under, n_never, n_interrupted, n_outside;
+} revs_charge_day_t;                  /* 64 bytes */
+int32_t revs_charge_report_chunk(void);
+int64_t revs_charge_report_scratch(int32_t S, int64_t n, int32_t T);
+int revs_charge_report(int32_t S, int64_t n, int32_t T, const float *p, int64_t stride_s, int64_t stride_i,
+                       const revs_home_t *homes, const double *tariff, double on_frac, double short_tol,
+                       revs_charge_row_t *row_rec, revs_charge_slot_t *slot_rec, revs_charge_day_t *day_rec,
+                       int32_t *hist, double *val_out, uint8_t *keep_out, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

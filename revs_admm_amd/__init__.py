@@ -6,6 +6,8 @@
     network        AdmmEngine.network_report: line flows / loading, node voltages and their box-plot numbers
     baselines      rule schedules: uncontrolled / last-minute / trickle charging from the residence records
     load_profile   the demand curve of a schedule: load per slot by class of residence, peaks, load factor, diversity
+    charging       what the chargers do: ChargingReport, charging_report / charging_report_device -- sessions, waits,
+                   chargers on per slot, state of charge at departure and cost per EV
     drawing        the reference's compute_flows / compute_voltage over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

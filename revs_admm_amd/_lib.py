@@ -153,6 +153,21 @@ PROFILE_DAY_DTYPE = np.dtype([("peak", "<f8"), ("valley", "<f8"), ("energy", "<f
 assert PROFILE_DAY_DTYPE.itemsize == 64
 PROFILE_MAX_CLASSES = 4  # REVS_PROFILE_MAX_CLASSES
 
+# numpy mirrors of revs_charge_row_t, revs_charge_slot_t and revs_charge_day_t (include/revs_admm_ops.h)
+CHARGE_ROW_DTYPE = np.dtype([("energy", "<f8"), ("cost", "<f8"), ("soc_end", "<f4"), ("reserved0", "<f4"),
+                             ("n_on", "<i4"), ("n_full", "<i4"), ("first_on", "<i4"), ("last_on", "<i4"),
+                             ("sessions", "<i4"), ("wait", "<i4"), ("n_outside", "<i4"), ("flags", "<i4"),
+                             ("reserved", "<i4", (2,))])
+assert CHARGE_ROW_DTYPE.itemsize == 64
+CHARGE_SLOT_DTYPE = np.dtype([("n_ev", "<i4"), ("n_plugged", "<i4"), ("n_on", "<i4"), ("n_full", "<i4"),
+                              ("n_starts", "<i4"), ("reserved", "<i4"), ("power", "<f8")])
+assert CHARGE_SLOT_DTYPE.itemsize == 32
+CHARGE_DAY_DTYPE = np.dtype([("peak_power", "<f8"), ("energy", "<f8"), ("coincidence", "<f8"), ("cost", "<f8"),
+                             ("peak_on", "<i4"), ("peak_on_slot", "<i4"), ("peak_power_slot", "<i4"), ("n_ev", "<i4"),
+                             ("n_under", "<i4"), ("n_never", "<i4"), ("n_interrupted", "<i4"), ("n_outside", "<i4")])
+assert CHARGE_DAY_DTYPE.itemsize == 64
+CHARGE_EV, CHARGE_UNDER, CHARGE_NONFINITE = 1, 2, 4      # bits of revs_charge_row_t.flags
+
 
 class RevsError(RuntimeError):
     pass
@@ -296,6 +311,9 @@ SIGNATURES = {
     "revs_load_profile_scratch": (_i64, [_i32, _i64, _i32, _i32, _i32]),
     "revs_load_profile": (C.c_int, [_i32, _i64, _i32, _p, _i64, _i64, _p, _i32, _p, _p, _i32, _f64, _p, _p, _p, _p, _p, _p,
                                     _p]),
+    "revs_charge_report_chunk": (_i32, []),
+    "revs_charge_report_scratch": (_i64, [_i32, _i64, _i32]),
+    "revs_charge_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _i64, _p, _p, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX

@@ -28,6 +28,7 @@ from .baselines import RuleScheduleMixin
 from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (re-exported)
 from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
 from .load_profile import LoadProfileMixin
+from .charging import ChargingMixin
 from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
@@ -202,7 +203,7 @@ def _on_current_stream(fn):
 
 
 class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
-                 LoadProfileMixin):
+                 LoadProfileMixin, ChargingMixin):
     """State of one ADMM run on one GPU.
 
     Parameters
@@ -887,6 +888,8 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         elif o.solver == "newton" and o.chain and self._chain_ok:
             if self._fold_ok():
                 self._chain_run(1, write_sc)         # (books the iteration itself)
+                if write_sc:
+                    self._sc_iteration = self.iteration
                 return
             self._chain_step(write_sc)       # binding steady state: one Newton iteration enqueued unread
         else:
@@ -896,6 +899,8 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         if self._fused_ready:             # the next P_est_new is already in the spare buffer
             self.P_est_new, self.P_est_alt = self.P_est_alt, self.P_est_new
         self.iteration += 1
+        if write_sc:                      # (S and Csoc are this iteration's: charging_report() may read them)
+            self._sc_iteration = self.iteration
 
     @_on_current_stream
     def run_steps(self, count):
@@ -1147,6 +1152,7 @@ class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateM
         self._p_clear = None
         self._chain_ok = False
         self._fold_resume = False
+        self._sc_iteration = -1
         if iteration is not None:
             self.iteration = int(iteration)
 

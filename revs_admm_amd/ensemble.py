@@ -192,6 +192,7 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsM
             a = np.ascontiguousarray(np.asarray(a, np.float32)[self.perm])
             assert a.shape == (self.n_res, self.T_slot)
             self._by_scenario(t, self.T_slot)[:, s, :].copy_(torch.from_numpy(a))
+        self._sc_iteration = -1
         if iteration is not None:
             self.iteration = int(iteration)
 
@@ -206,6 +207,7 @@ class AdmmEnsemble(EnsembleCertificateMixin, EnsembleReportMixin, EnsembleBillsM
         for t in (self.P_est, self.P_sch, self.G):
             t.zero_()
         self.iteration = 0
+        self._sc_iteration = -1
 
     def result(self):
         """(P_sch, S, C) of the last iteration, each with a leading scenario axis, in the caller's residence order."""

@@ -155,7 +155,7 @@ def split_scenarios(S: int, T: int):
 def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
                     vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None,
                     return_certificates=False, return_node_sums=False, return_convergence=None,
-                    convergence_groups=None, convergence_patience=8):
+                    convergence_groups=None, convergence_patience=8, return_charging=False):
     """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
     `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
     DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
@@ -175,7 +175,10 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
     ONE (iterations, n, len(homes_list)) float32 buffer which convergence.convergence_report_device reads; the report's
     records are read back and nothing else of it.  What IS still fetched is every solution's `diff` entry, from that
     buffer, because each returned tuple keeps solve_ADMM's form; the schedules are fetched as without the report.  An
-    empty list gives None for the report."""
+    empty list gives None for the report.
+    return_charging=True: the charger power of every scenario is appended last to the tuple as ONE (n, len(homes_list),
+    T) float32 tensor on the device, residences in `res` order -- charging.charging_report_device's layout.  Every
+    ensemble's slice is copied from its own S on the device before it is released; an empty list gives None."""
     import torch
     from .ensemble import AdmmEnsemble
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]
@@ -202,8 +205,10 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
     def answer(out, certs, node_g, conv=None):
         extra = ((certs,) if return_certificates else ()) + ((node_g,) if return_node_sums else ())
         extra += (conv,) if want_conv else ()
+        extra += (charge_p,) if return_charging else ()
         return (out,) + extra if extra else out
 
+    charge_p = None
     if not parts:
         return answer([], [], torch.empty(0, len(res), T, dtype=torch.float64, device=device)
                       if return_node_sums else None)
@@ -233,6 +238,11 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
                         {h: C[s, i].tolist() for i, h in enumerate(res)}))
         if return_certificates:
             certs += eng.certificates()
+        if return_charging:
+            if charge_p is None:
+                charge_p = torch.empty(len(res), len(recs), T, dtype=torch.float32, device=eng.dev)
+            inv = torch.from_numpy(np.ascontiguousarray(eng.inv_perm, dtype=np.int64)).to(eng.dev)
+            charge_p[:, a:b] = eng.S.view(len(res), b - a, T).index_select(0, inv)
         if return_node_sums:
             if node_g is None:
                 node_g = torch.empty(len(recs), eng.M, T, dtype=torch.float64, device=eng.dev)

@@ -14,7 +14,8 @@ import numpy as np
 
 from .extract import (GetCommunity, GetDistNet, GetHomeLoad, GetTariff, combine_result,
                       get_homes_ev_param)
-from .lpsolver import solve_ADMM, solve_ADMM_many, solve_central, solve_residences, solve_uncontrolled
+from .lpsolver import (homes_to_arrays, solve_ADMM, solve_ADMM_many, solve_central, solve_residences,
+                       solve_uncontrolled)
 
 RULE_METHODS = ("uncontrolled", "last_minute", "trickle")       # baselines.POLICIES: REVS.study's rule methods
 
@@ -123,7 +124,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, bills=False, convergence=None, load_profile=False, **opt):
+              across=False, bills=False, convergence=None, load_profile=False, charging=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -170,7 +171,12 @@ class REVS:
         row per (adoption, rating, seed) case with the base load "load" under that case's EV homes, in no pool
         (StudyReport.load_profile_rows names every row; opt profile_above: n_above's threshold, 0.0 by default).  The
         report works on float32, the precision of the engines' state; on the device_report path it reads the buffer on
-        the device, otherwise the profiles are uploaded once."""
+        the device, otherwise the profiles are uploaded once.  charging=True: StudyReport.charging, the
+        charging.ChargingReport of every method's charger power (the residences' rows, each scenario under its own
+        records), pooled by the report's groups, costs under `tariff`; an ensemble's scenarios are read from the
+        ensembles' own S on the device, the other methods' power is uploaded once as float32 (opt charging_on_frac,
+        charging_short_tol: the report's thresholds, 0.0 and 1e-6 by default; the row records are read back with opt
+        arrays)."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -200,6 +206,7 @@ class REVS:
             node_rating = line_nodes(dist, opt.get("line_rating"), parent, nonsub)[0]
         # deferred: (position in profiles, homes) of the ensemble's scenarios; owners: every scenario's EV homes
         labels, profiles, deferred, owners = [], [], [], []
+        charge_p, charge_rec = [], []              # charging=True: every scenario's charger power (None: deferred), records
         for adoption in adoptions:
             for rating in ratings:
                 for seed in seeds:
@@ -211,23 +218,28 @@ class REVS:
                     for method in methods:
                         labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
                         owners.append(ev_homes)
+                        if charging:
+                            charge_rec.append(homes_to_arrays(homes, res)[1])
+                            charge_p.append(None)
                         if method == "distributed" and ensemble:
                             deferred.append((len(profiles), homes))
                             profiles.append(None)
                             continue
                         if method == "distributed":
-                            P_res = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[0]
+                            P_res, P_ev = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[:2]
                         elif method in RULE_METHODS:
                             sol, status = solve_uncontrolled(homes, len(tariff), policy=method,
                                                              fill=opt.get("rule_fill", "target"),
                                                              charger=opt.get("mode", "binary"), device=self.device,
                                                              return_status=True)
-                            P_res = {h: sol[h][2] for h in homes}
+                            P_res, P_ev = {h: sol[h][2] for h in homes}, {h: sol[h][0] for h in homes}
                             labels[-1]["unserved"] = sum(1 for h in res if status[h] & 1)
                         else:
-                            P_res = self.get_individual_optimal(tariff, homes)[0]
+                            P_res, P_ev = self.get_individual_optimal(tariff, homes)[:2]
                         profiles.append(np.array([P_res[h] for h in res], np.float64))
-        conv_rep = None
+                        if charging:
+                            charge_p[-1] = np.array([P_ev[h] for h in res], np.float32)
+        conv_rep, charge_dev = None, None
         if deferred:
             sols = solve_ADMM_many([h for _, h in deferred], dist, tariff, None, kappa=opt.get("kappa", 5.0),
                                    iter_max=opt.get("max_iterations", 15), vset=opt.get("v0", 1.03),
@@ -236,7 +248,10 @@ class REVS:
                                    return_certificates=certify, return_node_sums=device_report,
                                    return_convergence=convergence,
                                    convergence_groups=self._deferred_groups(labels, keys, [i for i, _ in deferred]),
-                                   convergence_patience=opt.get("patience", 8))
+                                   convergence_patience=opt.get("patience", 8), return_charging=charging)
+            if charging:
+                *head, charge_dev = sols
+                sols = tuple(head) if len(head) > 1 else head[0]
             if convergence is not None:
                 *head, conv_rep = sols
                 sols = tuple(head) if len(head) > 1 else head[0]
@@ -269,6 +284,20 @@ class REVS:
                            groups=[order.index(c) for c in combos] + [-1] * len(cases))
             prof_rows = [dict(lab) for lab in labels] + [dict(method="load", adoption=c[0], rating=c[1], seed=c[2])
                                                          for c in cases]
+
+        def charging_report():
+            import torch
+            from .charging import charging_report_device
+            dev = torch.device(self.device)
+            buf = torch.empty(len(res), len(labels), len(tariff), dtype=torch.float32, device=dev)
+            where = {i: k for k, (i, _) in enumerate(deferred)}
+            for s, p in enumerate(charge_p):
+                buf[:, s].copy_(charge_dev[:, where[s]] if p is None else torch.from_numpy(p))
+            rec = np.ascontiguousarray(np.stack(charge_rec, axis=1)).view(np.uint8).reshape(-1)
+            return charging_report_device(buf, torch.from_numpy(rec).to(dev), tariff,
+                                          groups=[order.index(c) for c in combos],
+                                          on_frac=opt.get("charging_on_frac", 0.0),
+                                          short_tol=opt.get("charging_short_tol", 1e-6), rows=bool(opt.get("arrays", False)))
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -289,6 +318,8 @@ class REVS:
                 g = torch.cat([buf.float(), d_load[None].expand(len(cases), -1, -1)]).permute(1, 0, 2).contiguous()
                 rep.load_profile = load_profile_report_device(g, **prof_kw)
                 rep.load_profile_rows = prof_rows
+            if charging:
+                rep.charging = charging_report()
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -303,6 +334,8 @@ class REVS:
             g = np.concatenate([np.stack(profiles).astype(np.float32), np.broadcast_to(base_load, (len(cases),) + base_load.shape)])
             rep.load_profile = load_profile_report(g, device=self.device, **prof_kw)
             rep.load_profile_rows = prof_rows
+        if charging:
+            rep.charging = charging_report()
         return labels, rep
 
     @staticmethod

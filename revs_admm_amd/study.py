@@ -81,7 +81,8 @@ class StudyReport:
     REVS.study(convergence=eps) over the ensemble's scenarios, else None.  load_profile: the
     load_profile.LoadProfileReport of REVS.study(load_profile=True), else None; its rows are load_profile_rows: the
     study's labels, then one row dict(method="load", adoption, rating, seed) per case -- the base load under that case's
-    EV homes."""
+    EV homes.  charging: the charging.ChargingReport of REVS.study(charging=True) over the study's scenarios, else
+    None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -101,6 +102,7 @@ class StudyReport:
     convergence: object | None = None
     load_profile: object | None = None
     load_profile_rows: list | None = None
+    charging: object | None = None
 
     @property
     def n_groups(self):
