@@ -10,22 +10,22 @@
 //                            then runs on it as its T = 1 case
 //   net_across_exposure_kernel   the (member, slot) pairs in violation per node
 //
-// Members travel as bit masks in the kernel arguments, as net_pool_kernel's (network_kernels.hip), as many groups per
+// Members travel as bit masks in the kernel arguments (pack_group_masks, common.h), as many groups per
 // launch as fit; a workgroup expands its group's mask once into a list of scenario indices in LDS (8 KB), so that the
 // member loops are counted loops the compiler unrolls with their loads in flight together.
 //
-// The order statistics are exact and need no sort: a double's bits under a monotone map order like the value (any
+// The order statistics are exact and need no sort: a double's ordered key (boxplot.h) orders like the value (any
 // double: negatives, infinities; -0.0 as +0.0), and the k-th smallest key is built bit by bit from the top for the
 // three quartile ranks at once, one pass over the members per bit -- starting below the bits the cell's smallest and
 // largest key share, which no pass needs to find.  The passes re-read the members' values: a study's arrays stay in L2.
 #include "common.h"
+#include "boxplot.h"
 
 #include <math.h>
 
 namespace revs {
 
 constexpr int kAcrossNT = 256;
-constexpr int kAcrossMaskWords = 448;             // member bit masks of the groups of one launch (3.5 KB of arguments)
 struct AcrossArgs {
     const double *values;                         // [S][cells]
     const uint8_t *keep;                          // [n_out], or NULL
@@ -33,24 +33,8 @@ struct AcrossArgs {
     int32_t cells, T, g0, words, le;              // cells = n_out T; le: bands count v <= band (else v >= band)
     double lo, hi;
     double band[REVS_ACROSS_MAX_BANDS];           // (a NaN: unused, never counted)
-    unsigned long long member[kAcrossMaskWords];  // [groups of this launch][words]: bit s of a group's mask: scenario s
+    unsigned long long member[kGroupMaskWords];  // [groups of this launch][words]: bit s of a group's mask: scenario s
 };
-
-// a < b  <=>  across_key(a) < across_key(b) for any two doubles that are no NaNs; -0.0 has +0.0's key
-__device__ __forceinline__ unsigned long long across_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v + 0.0);
-    return (u >> 63) ? ~u : u | (1ull << 63);
-}
-__device__ __forceinline__ double across_val(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? k ^ (1ull << 63) : ~k));
-}
-
-// numpy.percentile's linear interpolation between the order statistics a <= b at fraction t (_lerp), without
-// contraction to fused multiply-adds: network_kernels.hip's np_lerp, the same roundings
-__device__ __forceinline__ double across_lerp(double a, double b, double t) {
-    const double d = __dsub_rn(b, a);
-    return t >= 0.5 ? __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, t))) : __dadd_rn(a, __dmul_rn(d, t));
-}
 
 __global__ __launch_bounds__(kAcrossNT) void net_across_kernel(AcrossArgs A) {
     __shared__ unsigned short mem[REVS_STUDY_MAX_S];
@@ -107,15 +91,15 @@ __global__ __launch_bounds__(kAcrossNT) void net_across_kernel(AcrossArgs A) {
 
     // ---- pass 2: the quartiles' lower order statistics, rank (cnt - 1) e / 4, e = 1, 2, 3, bit by bit below the
     // prefix the smallest and the largest key share
-    int rank[3];
+    unsigned rank[3];
     unsigned long long ans[3];
-    const unsigned long long kmin = across_key(mn), kmax = across_key(mx);
+    const unsigned long long kmin = box_key(mn), kmax = box_key(mx);
     const int top = kmin == kmax ? -1 : 63 - (int)__builtin_clzll(kmin ^ kmax);
     const unsigned long long prefix = top < 0 ? kmin : kmin & ~((2ull << top) - 1ull);     // (top == 63: no shared bit)
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
-        const int rr = (cnt - 1) * (e + 1);
-        rank[e] = rr >> 2;
+        unsigned rem4;
+        box_rank((unsigned)cnt, e + 1, rank[e], rem4);
         ans[e] = prefix;
     }
 #pragma unroll 1
@@ -127,14 +111,14 @@ __global__ __launch_bounds__(kAcrossNT) void net_across_kernel(AcrossArgs A) {
 #pragma unroll 4
         for (int k = 0; k < nm; ++k) {
             const double v = col[mem[k] * stride];
-            const unsigned long long key = across_key(v);
+            const unsigned long long key = box_key(v);
             const bool ok = v == v;
 #pragma unroll
             for (int e = 0; e < 3; ++e) below[e] += (ok && key < trial[e]) ? 1 : 0;
         }
 #pragma unroll
         for (int e = 0; e < 3; ++e)
-            if (below[e] <= rank[e]) ans[e] = trial[e];
+            if ((unsigned)below[e] <= rank[e]) ans[e] = trial[e];
     }
     // ---- the upper neighbours of the five order statistics (min, the quartiles, max): the same value when it repeats
     // past the rank, else the smallest value above it
@@ -144,7 +128,7 @@ __global__ __launch_bounds__(kAcrossNT) void net_across_kernel(AcrossArgs A) {
 #pragma unroll 4
     for (int k = 0; k < nm; ++k) {
         const double v = col[mem[k] * stride];
-        const unsigned long long key = across_key(v);
+        const unsigned long long key = box_key(v);
         if (v != v) continue;
 #pragma unroll
         for (int e = 0; e < 5; ++e) {
@@ -156,11 +140,10 @@ __global__ __launch_bounds__(kAcrossNT) void net_across_kernel(AcrossArgs A) {
     double qv[5];
 #pragma unroll
     for (int e = 0; e < 5; ++e) {
-        const int rr = (cnt - 1) * e, rk = rr >> 2;
-        const double a = across_val(stat[e]);
-        const bool last = rk + 1 >= cnt;                            // (numpy clips the upper index to cnt - 1)
-        const double b = (last || cle[e] > rk + 1) ? a : across_val(nxt[e]);
-        qv[e] = across_lerp(a, b, 0.25 * (double)(rr & 3));
+        unsigned rk, rem4;
+        box_rank((unsigned)cnt, e, rk, rem4);
+        const double a = box_val(stat[e]);
+        qv[e] = box_quartile(a, box_next_differs(rk, (unsigned)cnt, (unsigned)cle[e]) ? box_val(nxt[e]) : a, rem4);
     }
     r.min = qv[0]; r.q1 = qv[1]; r.median = qv[2]; r.q3 = qv[3]; r.max = qv[4];
     r.mean = sum / (double)cnt;
@@ -188,7 +171,7 @@ struct ExposureArgs {
     int32_t *out;                                 // [G][n_out]
     int32_t n_out, T, g0, words;
     double lo, hi;
-    unsigned long long member[kAcrossMaskWords];
+    unsigned long long member[kGroupMaskWords];
 };
 
 __global__ __launch_bounds__(kAcrossNT) void net_across_exposure_kernel(ExposureArgs A) {
@@ -262,14 +245,8 @@ extern "C" int revs_net_across(int32_t S, int32_t n_out, int32_t T, const double
     for (int b = 0; b < REVS_ACROSS_MAX_BANDS; ++b) A.band[b] = b < B ? band[b] : NAN;
     ExposureArgs E;
     E.values = values; E.keep = keep; E.out = exposure_out; E.n_out = n_out; E.T = T; E.words = A.words; E.lo = lo; E.hi = hi;
-    // the groups' member masks travel as kernel arguments: as many groups per launch as kAcrossMaskWords holds
-    const int per = kAcrossMaskWords / A.words;
-    for (int g0 = 0; g0 < G; g0 += per) {
-        const int ng = G - g0 < per ? G - g0 : per;
-        for (int i = 0; i < kAcrossMaskWords; ++i) A.member[i] = 0ull;
-        for (int s = 0; s < S; ++s)
-            if (group[s] >= g0 && group[s] < g0 + ng)
-                A.member[(size_t)(group[s] - g0) * A.words + s / 64] |= 1ull << (s % 64);
+    for (int g0 = 0, ng; g0 < G; g0 += ng) {
+        ng = pack_group_masks(group, S, G, g0, A.member);
         A.g0 = g0;
         if (slot_out) {
             A.values = values; A.out = slot_out; A.cells = n_out * T; A.T = T;
@@ -284,7 +261,7 @@ extern "C" int revs_net_across(int32_t S, int32_t n_out, int32_t T, const double
             REVS_CHECK_LAUNCH(who);
         }
         if (exposure_out) {
-            for (int i = 0; i < kAcrossMaskWords; ++i) E.member[i] = A.member[i];
+            for (int i = 0; i < kGroupMaskWords; ++i) E.member[i] = A.member[i];
             E.g0 = g0;
             hipLaunchKernelGGL(net_across_exposure_kernel, dim3((unsigned)((n_out + kAcrossNT - 1) / kAcrossNT), ng),
                                dim3(kAcrossNT), 0, st, E);

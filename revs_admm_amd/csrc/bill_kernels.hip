@@ -11,13 +11,14 @@
 //                          arithmetic: the bits are those of the sequential loop.
 //   bill_dev_kernel        dev[s][i] = (100 (bill[s][i] - bill[b][i])) / bill[b][i]; the scenarios' baselines travel
 //                          in the kernel arguments, kBillBaseMax scenarios per launch
-//   bill_select_kernel     one workgroup per (member set, quantity): net_pool_kernel's digit-wise radix select
-//                          (network_kernels.hip) over signed doubles under across_kernels.hip's ordered keys, reading
+//   bill_select_kernel     one workgroup per (member set, quantity): pass 0, then the radix selection of boxplot.h
+//                          (box_select64) over signed doubles under their ordered keys, reading
 //                          the values themselves (bill / dev, double[S][n]) under the keep mask.  A member set is one
 //                          scenario (the summaries) or a group's bit mask from the kernel arguments (the pools); both
 //                          walk a scenario's row with the same thread for the same element, so a pool of one scenario
 //                          repeats that scenario's record bit for bit, `total` included.
 #include "common.h"
+#include "boxplot.h"
 
 #include <math.h>
 
@@ -121,8 +122,6 @@ __global__ __launch_bounds__(256) void bill_dev_kernel(BillDevArgs A) {
 
 // ---- the selection ---------------------------------------------------------------------------------------------------
 constexpr int kBillSelNT = 1024;
-constexpr int kBillMaskWords = 448;               // member bit masks of the groups of one launch (3.5 KB of arguments)
-constexpr int kBillRed = 8;                       // values one block reduction carries
 struct BillSelArgs {
     const double *val[2];                         // bill, dev: [S][n]
     const uint8_t *keep;                          // [S][n], or NULL
@@ -130,71 +129,12 @@ struct BillSelArgs {
     revs_bill_summary_t *out;                     // [sets][2]
     int64_t n;
     int32_t words, g0, single;                    // single: the set of workgroup y is scenario y alone (no masks)
-    unsigned long long member[kBillMaskWords];    // [groups of this launch][words]: bit s of a group's mask: scenario s
+    unsigned long long member[kGroupMaskWords];   // [groups of this launch][words]: bit s of a group's mask: scenario s
 };
 
-// a < b  <=>  bill_key(a) < bill_key(b) for two doubles that are no NaNs (across_kernels.hip's across_key)
-__device__ __forceinline__ unsigned long long bill_key(double v) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-    return (u >> 63) ? ~u : u | (1ull << 63);
-}
-__device__ __forceinline__ double bill_val(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? k ^ (1ull << 63) : ~k));
-}
-// numpy.percentile's _lerp without contraction: across_lerp's roundings
-__device__ __forceinline__ double bill_lerp(double a, double b, double t) {
-    const double d = bill_sub(b, a);
-    return t >= 0.5 ? bill_sub(b, bill_mul(d, bill_sub(1.0, t))) : bill_add(a, bill_mul(d, t));
-}
-__device__ __forceinline__ unsigned long long bill_uniform_u64(unsigned long long v) {
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (unsigned long long)hi << 32 | lo;
-}
-__device__ __forceinline__ double bill_uniform_d(double v) {
-    return __longlong_as_double((long long)bill_uniform_u64((unsigned long long)__double_as_longlong(v)));
-}
-
-// max / sum of N values over the workgroup in a fixed tree (lanes, then the 16 wavefronts across one row of lanes):
-// every thread gets them, the same bits from call to call.  `red`: 16 * kBillRed doubles.
-template <int N, bool SUM>
-__device__ __forceinline__ void bill_block_reduce(double (&v)[N], double *red) {
-    static_assert(N <= kBillRed && kBillSelNT == 1024, "");
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = SUM ? wave_sum_d(v[e]) : wave_max_d(v[e]);
-    if (lane == 0) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) red[wave * kBillRed + e] = v[e];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        double r = red[(lane & 15) * kBillRed + e];
-        r = SUM ? r + dpp_rot_d<0x128>(r) : fmax(r, dpp_rot_d<0x128>(r));
-        r = SUM ? r + dpp_rot_d<0x124>(r) : fmax(r, dpp_rot_d<0x124>(r));
-        r = SUM ? r + dpp_rot_d<0x122>(r) : fmax(r, dpp_rot_d<0x122>(r));
-        r = SUM ? r + dpp_rot_d<0x121>(r) : fmax(r, dpp_rot_d<0x121>(r));
-        v[e] = bill_uniform_d(r);
-    }
-    __syncthreads();
-}
-
-// one count into h[d] per matching lane: by the first matching lane alone when the wavefront's digits agree
-__device__ __forceinline__ void bill_hist_add(unsigned *h, bool match, unsigned d) {
-    const unsigned long long m = __ballot(match);
-    if (m == 0ull) return;
-    const int first = (int)__builtin_ctzll(m);
-    const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, first);
-    if (__ballot(match && d == d0) == m) {
-        if ((int)(threadIdx.x & 63) == first) atomicAdd(h + d0, (unsigned)__popcll(m));
-    } else if (match) {
-        atomicAdd(h + d, 1u);
-    }
-}
-
-// f(v, ok, kept, scenario, row) over every row of the set's scenarios, ascending, every thread the same number of
+// f(key, ok, v, scenario, row, kept) over every row of the set's scenarios, ascending, every thread the same number of
 // times (threads past a row's end see a value that is not kept): lane masks and reductions stay whole.  v is the
-// value with -0.0 as +0.0; ok: kept and finite.
+// value with -0.0 as +0.0, key its ordered key; ok: kept and finite.
 template <class F>
 __device__ __forceinline__ void bill_for_each(const BillSelArgs &A, const double *val, int set, F f) {
     const int tid = threadIdx.x;
@@ -207,34 +147,33 @@ __device__ __forceinline__ void bill_for_each(const BillSelArgs &A, const double
             const uint8_t *kp = A.keep ? A.keep + (int64_t)s * A.n : nullptr;
             for (int64_t jb = 0; jb < A.n; jb += kBillSelNT) {
                 const int64_t j = jb + tid;
-                double v = __builtin_nan("");
+                double raw = __builtin_nan("");
                 bool kept = false;
                 if (j < A.n) {
                     kept = !kp || kp[j] != 0;
-                    v = row[j] + 0.0;
+                    raw = row[j];
                 }
-                f(v, kept && (v - v == 0.0), kept, s, (int)j);
+                const double v = raw + 0.0;
+                f(box_key(raw), kept && (v - v == 0.0), v, s, (int)j, kept);
             }
         }
     }
 }
 
 __global__ __launch_bounds__(kBillSelNT) void bill_select_kernel(BillSelArgs A) {
-    __shared__ alignas(16) unsigned hist[3 * 256];
-    __shared__ double red[16 * kBillRed];
-    __shared__ unsigned found[3][4];              // per rank: digit, rank left inside the bin, the bin's count
+    __shared__ BoxSelect<kBillSelNT> sh;
     constexpr int NT = kBillSelNT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int q = (int)blockIdx.x, set = (int)blockIdx.y;
     const double *val = A.val[q];
     const double ninf = -__builtin_inf(), nan = __builtin_nan("");
 
-    for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
+    for (int i = tid; i < 3 * 256; i += NT) sh.hist[i] = 0u;
     __syncthreads();
     // ---- pass 0: counts, extremes, the total, and the top digit's histogram
     double c[4] = {0.0, 0.0, 0.0, 0.0};           // finite, kept and not finite, above zero; the values' sum
     double x[2] = {ninf, ninf};                   // -min, max
-    bill_for_each(A, val, set, [&](double v, bool ok, bool kept, int, int) {
+    bill_for_each(A, val, set, [&](unsigned long long k, bool ok, double v, int, int, bool kept) {
         c[0] += ok ? 1.0 : 0.0;
         c[1] += (kept && !ok) ? 1.0 : 0.0;
         if (ok) {
@@ -242,10 +181,10 @@ __global__ __launch_bounds__(kBillSelNT) void bill_select_kernel(BillSelArgs A) 
             c[3] += v;
             x[0] = fmax(x[0], -v); x[1] = fmax(x[1], v);
         }
-        bill_hist_add(hist, ok, (unsigned)(bill_key(v) >> 56));
+        hist_add(sh.hist, ok, (unsigned)(k >> 56));
     });
-    bill_block_reduce<4, true>(c, red);
-    bill_block_reduce<2, false>(x, red);
+    block_reduce_multi<NT, 4, true>(c, sh.red);
+    block_reduce_multi<NT, 2, false>(x, sh.red);
     const int kcnt = (int)c[0];
     revs_bill_summary_t r;
     r.min = r.q1 = r.median = r.q3 = r.max = r.whisker_lo = r.whisker_hi = r.total = nan;
@@ -257,111 +196,26 @@ __global__ __launch_bounds__(kBillSelNT) void bill_select_kernel(BillSelArgs A) 
         if (tid == 0) *out = r;
         return;
     }
-    // ---- the quartiles' lower order statistics: rank (k - 1) e / 4, e = 1, 2, 3
-    int rank[3], rem4[3];
-    unsigned left[3], eq[3] = {0u, 0u, 0u};       // rank left among the keys that share the prefix; keys equal to ans
-    unsigned long long ans[3] = {0ull, 0ull, 0ull};
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const long long rr = (long long)(kcnt - 1) * (e + 1);
-        rank[e] = (int)(rr >> 2); rem4[e] = (int)(rr & 3);
-        left[e] = (unsigned)rank[e];
-    }
-#pragma unroll 1
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 56 - 8 * pass;
-        // ranks whose prefixes agree share a histogram (the prefixes ascend with the ranks: equal ones are adjacent)
-        int slot[3] = {0, 0, 0};
-        if (pass > 0) {
-            slot[1] = ans[1] == ans[0] ? 0 : 1;
-            slot[2] = ans[2] == ans[1] ? slot[1] : 2;
-            const bool own1 = slot[1] == 1, own2 = slot[2] == 2;
-            const unsigned long long p0 = ans[0] >> (shift + 8), p1 = ans[1] >> (shift + 8), p2 = ans[2] >> (shift + 8);
-            bill_for_each(A, val, set, [&](double v, bool ok, bool, int, int) {
-                const unsigned long long k = bill_key(v), pk = k >> (shift + 8);
-                const unsigned d = (unsigned)(k >> shift) & 0xFFu;
-                bill_hist_add(hist, ok && pk == p0, d);
-                if (own1) bill_hist_add(hist + 256, ok && pk == p1, d);
-                if (own2) bill_hist_add(hist + 512, ok && pk == p2, d);
-            });
-        }
-        __syncthreads();
-        // the bin that holds each rank: wavefront e for rank e, four bins per lane, a prefix sum across the lanes
-        if (wave < 3) {
-            const unsigned *h = hist + 256 * slot[wave];
-            const uint4 cc = *reinterpret_cast<const uint4 *>(h + 4 * lane);
-            const unsigned own = cc.x + cc.y + cc.z + cc.w;
-            unsigned incl = own;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned up = (unsigned)__shfl_up((int)incl, o);
-                if (lane >= o) incl += up;
+    // ---- the selection; in its neighbour walk the worst entry: the largest value, lowest scenario, then lowest
+    // caller-side index.  scenario 2^31 + index < 2^43 is exact in a double.
+    double wc[1] = {ninf};                        // -(code of the worst entry)
+    const BoxFigures b = box_select64(sh, kcnt,
+        [&](auto f) {
+            bill_for_each(A, val, set, [&](unsigned long long k, bool ok, double v, int s, int j, bool) { f(k, ok, v, s, j); });
+        },
+        [&](unsigned long long, bool ok, double v, int sidx, int j) {
+            if (ok && v == x[1]) {
+                const int idx = A.ior ? A.ior[j] : j;
+                wc[0] = fmax(wc[0], -((double)sidx * 2147483648.0 + (double)idx));
             }
-            const unsigned want = left[wave], excl = incl - own;
-            if (want >= excl && want < incl) {    // (one lane: the bins' counts sum to more than the rank left)
-                unsigned b = 0, below = excl, cnt = cc.x;
-                if (want >= below + cnt) { below += cnt; b = 1; cnt = cc.y; }
-                if (b == 1 && want >= below + cnt) { below += cnt; b = 2; cnt = cc.z; }
-                if (b == 2 && want >= below + cnt) { below += cnt; b = 3; cnt = cc.w; }
-                found[wave][0] = 4u * lane + b; found[wave][1] = want - below; found[wave][2] = cnt;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            ans[e] = bill_uniform_u64(ans[e] | (unsigned long long)found[e][0] << shift);      // (every lane holds the same)
-            left[e] = __builtin_amdgcn_readfirstlane(found[e][1]); eq[e] = __builtin_amdgcn_readfirstlane(found[e][2]);
-        }
-        __syncthreads();                          // (every read of hist and found is done)
-        for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
-        __syncthreads();
-    }
-    // ---- the upper neighbours (the smallest value above each), and the worst entry: the largest value, lowest scenario,
-    // then lowest caller-side index.  scenario 2^31 + index < 2^43 is exact in a double.
-    double nw[4] = {ninf, ninf, ninf, ninf};      // -next above rank e; -(code of the worst entry)
-    bill_for_each(A, val, set, [&](double v, bool ok, bool, int sidx, int j) {
-        if (!ok) return;
-        const unsigned long long k = bill_key(v);
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-            if (k > ans[e]) nw[e] = fmax(nw[e], -v);
-        if (v == x[1]) {
-            const int idx = A.ior ? A.ior[j] : j;
-            nw[3] = fmax(nw[3], -((double)sidx * 2147483648.0 + (double)idx));
-        }
-    });
-    bill_block_reduce<4, false>(nw, red);
-    double qv[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const double lo = bill_val(ans[e]);
-        const int cle = rank[e] - (int)left[e] + (int)eq[e];        // values <= the order statistic
-        const bool last = rank[e] + 1 >= kcnt;
-        const double hi = (last || cle > rank[e] + 1) ? lo : -nw[e];
-        qv[e] = bill_lerp(lo, hi, 0.25 * (double)rem4[e]);
-    }
-    // ---- whiskers and fliers, as net_report_kernel's
-    const double iqr = bill_sub(qv[2], qv[0]);
-    const double lim0 = bill_sub(qv[0], bill_mul(1.5, iqr)), lim1 = bill_add(qv[2], bill_mul(1.5, iqr));
-    double wk[2] = {ninf, ninf};
-    bill_for_each(A, val, set, [&](double v, bool ok, bool, int, int) {
-        if (ok && v >= lim0) wk[0] = fmax(wk[0], -v);
-        if (ok && v <= lim1) wk[1] = fmax(wk[1], v);
-    });
-    bill_block_reduce<2, false>(wk, red);
-    const double wlo = (wk[0] == ninf || -wk[0] > qv[0]) ? qv[0] : -wk[0];
-    const double whi = (wk[1] == ninf || wk[1] < qv[2]) ? qv[2] : wk[1];
-    double fl[1] = {0.0};
-    bill_for_each(A, val, set, [&](double v, bool ok, bool, int, int) {
-        fl[0] += (ok && (v < wlo || v > whi)) ? 1.0 : 0.0;
-    });
-    bill_block_reduce<1, true>(fl, red);
+        });
+    block_reduce_multi<NT, 1, false>(wc, sh.red);
     if (tid == 0) {
-        const long long code = (long long)-nw[3];
-        r.min = -x[0] + 0.0; r.q1 = qv[0]; r.median = qv[1]; r.q3 = qv[2]; r.max = x[1];
-        r.whisker_lo = wlo + 0.0; r.whisker_hi = whi;
+        const long long code = (long long)-wc[0];
+        r.min = -x[0] + 0.0; r.q1 = b.q[0]; r.median = b.q[1]; r.q3 = b.q[2]; r.max = x[1];
+        r.whisker_lo = b.wlo + 0.0; r.whisker_hi = b.whi;
         r.total = c[3];
-        r.n_fliers = (int)fl[0];
+        r.n_fliers = b.n_fliers;
         r.worst_scenario = (int)(code >> 31); r.worst_index = (int)(code & 0x7FFFFFFFll);
         *out = r;
     }
@@ -371,29 +225,23 @@ __global__ __launch_bounds__(kBillSelNT) void bill_select_kernel(BillSelArgs A) 
 
 using namespace revs;
 
-static bool bill_sizes_ok(int32_t S, int64_t n) {
-    return S >= 1 && S <= REVS_STUDY_MAX_S && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)S * n < ((int64_t)1 << 31);
-}
-
 extern "C" int revs_bill_rows(int32_t S, int64_t n, int32_t T, const void *g, int32_t g_f64, int64_t stride_s,
                               int64_t stride_i, const double *tariff, double *bill, void *stream) {
     const char *who = "revs_bill_rows";
     REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
     REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
     REVS_REQUIRE(n >= 1, "%s: n=%lld < 1", who, (long long)n);
-    REVS_REQUIRE(bill_sizes_ok(S, n), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
+    REVS_REQUIRE(study_sizes_ok(S, n), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
     REVS_REQUIRE(g, "%s: null pointer argument g", who);
     REVS_REQUIRE(tariff, "%s: null pointer argument tariff", who);
     REVS_REQUIRE(bill, "%s: null pointer argument bill", who);
     REVS_REQUIRE(g_f64 == 0 || g_f64 == 1, "%s: g_f64=%d is neither 0 nor 1", who, (int)g_f64);
-    // a >= k b for positive integers is a / b >= k: no product that could overflow
-    const bool inner_i = stride_i >= T && stride_s / stride_i >= n;
-    const bool inner_s = stride_s >= T && stride_i / stride_s >= S;
-    REVS_REQUIRE(inner_i || inner_s, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
+    const int inner_i = rows_inner_i(S, n, T, stride_s, stride_i);
+    REVS_REQUIRE(inner_i >= 0, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
                  (long long)stride_s, (long long)stride_i, (int)S, (long long)n, (int)T);
     BillRowsArgs A;
     A.g = g; A.tariff = tariff; A.bill = bill; A.stride_s = stride_s; A.stride_i = stride_i;
-    A.n = (uint32_t)n; A.S = (uint32_t)S; A.rows = (uint32_t)((int64_t)S * n); A.T = T; A.inner_i = inner_i ? 1 : 0;
+    A.n = (uint32_t)n; A.S = (uint32_t)S; A.rows = (uint32_t)((int64_t)S * n); A.T = T; A.inner_i = inner_i;
     const dim3 grid((A.rows + kBillNT - 1) / kBillNT);
     if (g_f64) hipLaunchKernelGGL(bill_rows_kernel<double>, grid, dim3(kBillNT), 0, (hipStream_t)stream, A);
     else hipLaunchKernelGGL(bill_rows_kernel<float>, grid, dim3(kBillNT), 0, (hipStream_t)stream, A);
@@ -402,7 +250,7 @@ extern "C" int revs_bill_rows(int32_t S, int64_t n, int32_t T, const void *g, in
 }
 
 extern "C" int64_t revs_bill_study_scratch(int32_t S, int64_t n) {
-    if (!bill_sizes_ok(S, n)) return 0;
+    if (!study_sizes_ok(S, n)) return 0;
     return (int64_t)S * n * (int64_t)sizeof(double);
 }
 
@@ -415,7 +263,7 @@ extern "C" int revs_bill_study(int32_t S, int64_t n, const double *bill, const i
     const char *who = "revs_bill_study";
     REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
     REVS_REQUIRE(n >= 1, "%s: n=%lld < 1", who, (long long)n);
-    REVS_REQUIRE(bill_sizes_ok(S, n), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
+    REVS_REQUIRE(study_sizes_ok(S, n), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
     REVS_REQUIRE(bill, "%s: null pointer argument bill", who);
     REVS_REQUIRE(base, "%s: base is NULL", who);
     for (int s = 0; s < S; ++s)
@@ -442,24 +290,17 @@ extern "C" int revs_bill_study(int32_t S, int64_t n, const double *bill, const i
         REVS_CHECK_LAUNCH(who);
     }
     if (!select) return REVS_OK;
-    BillSelArgs A;
+    BillSelArgs A = {};
     A.val[0] = bill; A.val[1] = dev; A.keep = keep; A.ior = index_of_row; A.n = n; A.words = (S + 63) / 64;
-    for (int i = 0; i < kBillMaskWords; ++i) A.member[i] = 0ull;
     if (summary_out) {
         A.out = summary_out; A.g0 = 0; A.single = 1;
         hipLaunchKernelGGL(bill_select_kernel, dim3(2, S), dim3(kBillSelNT), 0, st, A);
         REVS_CHECK_LAUNCH(who);
     }
     if (pooled_out) {
-        // the groups' member masks travel as kernel arguments: as many groups per launch as kBillMaskWords holds
         A.out = pooled_out; A.single = 0;
-        const int per = kBillMaskWords / A.words;
-        for (int g0 = 0; g0 < G; g0 += per) {
-            const int ng = G - g0 < per ? G - g0 : per;
-            for (int i = 0; i < kBillMaskWords; ++i) A.member[i] = 0ull;
-            for (int s = 0; s < S; ++s)
-                if (group[s] >= g0 && group[s] < g0 + ng)
-                    A.member[(size_t)(group[s] - g0) * A.words + s / 64] |= 1ull << (s % 64);
+        for (int g0 = 0, ng; g0 < G; g0 += ng) {
+            ng = pack_group_masks(group, S, G, g0, A.member);
             A.g0 = g0;
             hipLaunchKernelGGL(bill_select_kernel, dim3(2, ng), dim3(kBillSelNT), 0, st, A);
             REVS_CHECK_LAUNCH(who);

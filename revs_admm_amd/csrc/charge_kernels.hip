@@ -297,8 +297,7 @@ __global__ __launch_bounds__(256) void charge_day_kernel(ChargeFoldArgs A) {
 using namespace revs;
 
 static bool charge_sizes_ok(int32_t S, int64_t n, int32_t T) {
-    return S >= 1 && S <= REVS_STUDY_MAX_S && T >= 1 && T <= REVS_MAX_T && n >= 1 && n < ((int64_t)1 << 31)
-           && (int64_t)S * n < ((int64_t)1 << 31);
+    return study_sizes_ok(S, n) && T >= 1 && T <= REVS_MAX_T;
 }
 static int64_t charge_int_bytes(int32_t S, int32_t T) {         // the counters in front of the scratch, a multiple of 16
     return ((int64_t)S * T * kChgSlotC + (int64_t)S * kChgDayC) * (int64_t)sizeof(int32_t);
@@ -326,10 +325,7 @@ extern "C" int revs_charge_report(int32_t S, int64_t n, int32_t T, const float *
     REVS_REQUIRE(charge_sizes_ok(S, n, T), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
     REVS_REQUIRE(p, "%s: null pointer argument p", who);
     REVS_REQUIRE(homes, "%s: null pointer argument homes", who);
-    // a >= k b for positive integers is a / b >= k: no product that could overflow
-    const bool inner_i = stride_i >= T && stride_s / stride_i >= n;
-    const bool inner_s = stride_s >= T && stride_i / stride_s >= S;
-    REVS_REQUIRE(inner_i || inner_s, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
+    REVS_REQUIRE(rows_inner_i(S, n, T, stride_s, stride_i) >= 0, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
                  (long long)stride_s, (long long)stride_i, (int)S, (long long)n, (int)T);
     REVS_REQUIRE(on_frac >= 0.0, "%s: on_frac=%g is negative or a NaN", who, on_frac);
     REVS_REQUIRE(short_tol >= 0.0, "%s: short_tol=%g is negative or a NaN", who, short_tol);

@@ -26,6 +26,29 @@ void set_error(const char *fmt, ...);
         }                                                                        \
     } while (0)
 
+// ---- what the reports' entry points check and pack alike ----------------
+// a study's sizes: S scenarios of n rows each, S n < 2^31
+inline bool study_sizes_ok(int32_t S, int64_t n) {
+    return S >= 1 && S <= REVS_STUDY_MAX_S && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)S * n < ((int64_t)1 << 31);
+}
+// The rows of T elements at s stride_s + i stride_i (s < S, i < n) do not overlap: 1 when i is the inner index, 0 when
+// s is, -1 when they overlap.  (a >= k b for positive integers is a / b >= k: no product that could overflow)
+inline int rows_inner_i(int32_t S, int64_t n, int32_t T, int64_t stride_s, int64_t stride_i) {
+    if (stride_i >= T && stride_s / stride_i >= n) return 1;
+    if (stride_s >= T && stride_i / stride_s >= S) return 0;
+    return -1;
+}
+// The groups' member masks travel as kernel arguments, [groups of the launch][words = (S + 63) / 64]: bit s of a
+// group's mask is scenario s.  Packs the masks of groups g0, g0 + 1, .. -- as many as fit -- and returns their number.
+constexpr int kGroupMaskWords = 448;              // 3.5 KB of arguments
+inline int pack_group_masks(const int32_t *group, int32_t S, int32_t G, int32_t g0, unsigned long long (&member)[kGroupMaskWords]) {
+    const int words = (S + 63) / 64, per = kGroupMaskWords / words, ng = G - g0 < per ? G - g0 : per;
+    for (int i = 0; i < kGroupMaskWords; ++i) member[i] = 0ull;
+    for (int s = 0; s < S; ++s)
+        if (group[s] >= g0 && group[s] < g0 + ng) member[(size_t)(group[s] - g0) * words + s / 64] |= 1ull << (s % 64);
+    return ng;
+}
+
 // ---- DPP cross-lane moves (64-wide wavefront, rows of 16 lanes) ----------
 // dpp_ctrl encodings: quad_perm 0x00-0xFF, row_shl:n 0x100+n, row_shr:n 0x110+n,
 // row_mirror 0x140, row_half_mirror 0x141.  bound_ctrl=1: lanes whose source is
@@ -145,6 +168,43 @@ __device__ __forceinline__ int wave_incl_scan_i(int v) {
     v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);   // row_bcast:15 into rows 1 and 3
     v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);   // row_bcast:31 into rows 2 and 3
     return v;
+}
+
+__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {      // a value every lane holds, into SGPRs
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+    return (unsigned long long)hi << 32 | lo;
+}
+__device__ __forceinline__ double uniform_d(double v) {
+    return __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(v)));
+}
+
+// max / sum of N values over a workgroup of NT threads in a fixed tree (lanes, then the wavefronts across one row of
+// lanes): every thread gets them, the same bits from call to call.  `red`: NT / 64 * kBlockRed doubles.
+constexpr int kBlockRed = 8;                     // values one block reduction carries
+template <int NT, int N, bool SUM>
+__device__ __forceinline__ void block_reduce_multi(double (&v)[N], double *red) {
+    static_assert(N <= kBlockRed && NT / 64 <= 16, "");
+    const int tid = threadIdx.x, wave = tid >> 6;
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = SUM ? wave_sum_d(v[e]) : wave_max_d(v[e]);
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int e = 0; e < N; ++e) red[wave * kBlockRed + e] = v[e];
+    }
+    __syncthreads();
+    // the wavefronts' values across the first NT / 64 lanes of a row of 16, combined by rotations inside the row (one
+    // load per value in flight, not NT / 64), then into SGPRs: every lane holds the same
+    const int lane = tid & 63;
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+        double r = lane < NT / 64 ? red[lane * kBlockRed + e] : (SUM ? 0.0 : -__builtin_inf());
+        r = SUM ? r + dpp_rot_d<0x128>(r) : fmax(r, dpp_rot_d<0x128>(r));          // (all four: every lane of the row
+        r = SUM ? r + dpp_rot_d<0x124>(r) : fmax(r, dpp_rot_d<0x124>(r));          //  ends with the row's total)
+        r = SUM ? r + dpp_rot_d<0x122>(r) : fmax(r, dpp_rot_d<0x122>(r));
+        r = SUM ? r + dpp_rot_d<0x121>(r) : fmax(r, dpp_rot_d<0x121>(r));
+        v[e] = uniform_d(r);
+    }
+    __syncthreads();
 }
 
 // Sum / max over an aligned group of LPA lanes, result in every lane of the group.

@@ -23,9 +23,12 @@
 // them altogether (a workgroup all of whose sets are settled runs pass 0, the neighbour / whisker / flier passes and
 // nothing else).  Counts go to LDS once per distinct address of a wavefront, not once per lane.
 #include "common.h"
-#include "conv_keys.h"
+#include "boxplot.h"
 
 #include <math.h>
+
+// Every product and sum of this file is rounded on its own, as numpy's: no contraction to fused multiply-adds.
+#pragma clang fp contract(off)
 
 namespace revs {
 
@@ -80,9 +83,9 @@ struct ConvWalk {
                     const unsigned u = __float_as_uint(row[(size_t)i * S + c]);
                     if ((u & 0x7F800000u) == 0x7F800000u) cls = kClsBad;
                     else {
-                        key = conv_key(u);
-                        v = conv_val(key);
-                        cls = key < kConvKey0 ? kClsNeg : key == kConvKey0 ? kClsZero : v > eps ? kClsAbove : kClsLow;
+                        key = box_key_f(u);
+                        v = box_val_f(key);
+                        cls = key < kBoxKey0F ? kClsNeg : key == kBoxKey0F ? kClsZero : v > eps ? kClsAbove : kClsLow;
                     }
                 }
             }
@@ -126,16 +129,11 @@ __device__ __forceinline__ void conv_select(ConvShared &sh, const ConvWalk &W, i
         const unsigned nneg = c[kClsNeg], nzero = c[kClsZero], cnt = nneg + nzero + c[kClsLow] + c[kClsAbove];
         sh.count[tid] = cnt;
         for (int e = 0; e < 3; ++e) {
-            const unsigned long long rr = cnt ? (unsigned long long)(cnt - 1) * (unsigned)(e + 1) : 0ull;
-            const unsigned r = (unsigned)(rr >> 2);
-            sh.rank[tid][e] = r; sh.rem4[tid][e] = (unsigned)(rr & 3ull);
-            sh.left[tid][e] = r; sh.eq[tid][e] = 0u; sh.ans[tid][e] = 0u; sh.slot[tid][e] = 0u;
-            unsigned open = cnt ? 1u : 0u;
-            if (cnt && r >= nneg && r < nneg + nzero) {         // the rank falls among the zeros: settled
-                sh.ans[tid][e] = kConvKey0; sh.left[tid][e] = r - nneg; sh.eq[tid][e] = nzero;
-                open = 0u;
-            }
-            sh.open[tid][e] = open;
+            unsigned r;
+            box_rank(cnt, e + 1, r, sh.rem4[tid][e]);
+            sh.rank[tid][e] = r; sh.left[tid][e] = r; sh.eq[tid][e] = 0u; sh.ans[tid][e] = 0u; sh.slot[tid][e] = 0u;
+            const bool open = cnt && !box_settled_at_zero(r, nneg, nzero, sh.ans[tid][e], sh.left[tid][e], sh.eq[tid][e]);
+            sh.open[tid][e] = open ? 1u : 0u;
             if (open) sh.any_open = 1u;
         }
     }
@@ -162,23 +160,9 @@ __device__ __forceinline__ void conv_select(ConvShared &sh, const ConvWalk &W, i
                 const int set = task / 3, e = task - 3 * set;
                 if (!sh.open[set][e]) continue;   // (uniform in the wavefront)
                 const unsigned *h = sh.hist + (set * 3 + (int)sh.slot[set][e]) * 256;
-                const uint4 cc = *reinterpret_cast<const uint4 *>(h + 4 * lane);
-                const unsigned own = cc.x + cc.y + cc.z + cc.w;
-                unsigned incl = own;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) {
-                    const unsigned up = (unsigned)__shfl_up((int)incl, o);
-                    if (lane >= o) incl += up;
-                }
-                const unsigned want = sh.left[set][e], excl = incl - own;
-                if (want >= excl && want < incl) {              // (one lane)
-                    unsigned b = 0, below = excl, cnt = cc.x;
-                    if (want >= below + cnt) { below += cnt; b = 1; cnt = cc.y; }
-                    if (b == 1 && want >= below + cnt) { below += cnt; b = 2; cnt = cc.z; }
-                    if (b == 2 && want >= below + cnt) { below += cnt; b = 3; cnt = cc.w; }
-                    sh.ans[set][e] |= (4u * lane + b) << shift;
-                    sh.left[set][e] = want - below; sh.eq[set][e] = cnt;
-                }
+                unsigned bin, left, eq;
+                pick_bin(*reinterpret_cast<const uint4 *>(h + 4 * lane), sh.left[set][e], bin, left, eq);
+                if (lane == 0) { sh.ans[set][e] |= bin << shift; sh.left[set][e] = left; sh.eq[set][e] = eq; }
             }
             __syncthreads();
             if (pass < 3) {
@@ -199,7 +183,7 @@ __device__ __forceinline__ void conv_select(ConvShared &sh, const ConvWalk &W, i
         const unsigned cnt = sh.count[tid];
         for (int e = 0; e < 3; ++e) {
             const unsigned r = sh.rank[tid][e], cle = r - sh.left[tid][e] + sh.eq[tid][e];      // values <= the statistic
-            sh.need[tid][e] = (cnt && sh.rem4[tid][e] != 0u && r + 1 < cnt && cle <= r + 1) ? 1u : 0u;
+            sh.need[tid][e] = (sh.rem4[tid][e] != 0u && box_next_differs(r, cnt, cle)) ? 1u : 0u;
         }
     }
     __syncthreads();
@@ -214,16 +198,14 @@ __device__ __forceinline__ void conv_select(ConvShared &sh, const ConvWalk &W, i
     __syncthreads();
     if (tid < nsets && sh.count[tid]) {
         for (int e = 0; e < 3; ++e) {
-            const double lo = conv_val(sh.ans[tid][e]);
-            const double hi = sh.need[tid][e] ? conv_val(sh.nb[tid][e]) : lo;
-            sh.q[tid][e] = conv_lerp(lo, hi, 0.25 * (double)sh.rem4[tid][e]);
+            const double lo = box_val_f(sh.ans[tid][e]);
+            const double hi = sh.need[tid][e] ? box_val_f(sh.nb[tid][e]) : lo;
+            sh.q[tid][e] = box_quartile(lo, hi, sh.rem4[tid][e]);
         }
-        const double iqr = conv_sub(sh.q[tid][2], sh.q[tid][0]);
-        sh.lim[tid][0] = conv_sub(sh.q[tid][0], conv_mul(1.5, iqr));
-        sh.lim[tid][1] = conv_addd(sh.q[tid][2], conv_mul(1.5, iqr));
+        box_limits(sh.q[tid][0], sh.q[tid][2], sh.lim[tid][0], sh.lim[tid][1]);
     }
     __syncthreads();
-    // ---- whiskers and fliers, as net_report_kernel's
+    // ---- whiskers and fliers
     W.each([&](unsigned key, double v, int cls, int set, uint32_t) {
         if (cls > kClsBad) {
             if (v >= sh.lim[set][0] && key < sh.wk[set][0]) atomicMin(&sh.wk[set][0], key);
@@ -234,15 +216,15 @@ __device__ __forceinline__ void conv_select(ConvShared &sh, const ConvWalk &W, i
     if (tid < nsets && sh.count[tid]) {
         const double q1 = sh.q[tid][0], q3 = sh.q[tid][2];
         const unsigned k0 = sh.wk[tid][0], k1 = sh.wk[tid][1];
-        const double wlo = (k0 == 0xFFFFFFFFu || conv_val(k0) > q1) ? q1 : conv_val(k0);
-        const double whi = (k1 == 0u || conv_val(k1) < q3) ? q3 : conv_val(k1);
+        const double wlo = box_whisker_lo(q1, k0 != 0xFFFFFFFFu, box_val_f(k0));
+        const double whi = box_whisker_hi(q3, k1 != 0u, box_val_f(k1));
         sh.w[tid][0] = wlo; sh.w[tid][1] = whi;
-        if (conv_val(sh.ext[tid][0]) < wlo || conv_val(sh.ext[tid][1]) > whi) sh.any_fl = 1u;
+        if (box_val_f(sh.ext[tid][0]) < wlo || box_val_f(sh.ext[tid][1]) > whi) sh.any_fl = 1u;
     }
     __syncthreads();
     if (sh.any_fl) {                              // (uniform)
         W.each([&](unsigned, double v, int cls, int set, uint32_t) {
-            conv_add(sh.fl, cls > kClsBad && (v < sh.w[set][0] || v > sh.w[set][1]), (unsigned)set);
+            conv_add(sh.fl, cls > kClsBad && box_is_flier(v, sh.w[set][0], sh.w[set][1]), (unsigned)set);
         });
         __syncthreads();
     }
@@ -258,7 +240,7 @@ __device__ __forceinline__ revs_bill_summary_t conv_record(const ConvShared &sh,
     r.count = (int)sh.count[ls]; r.n_nan = (int)c[kClsBad]; r.n_fliers = 0; r.n_above = (int)c[kClsAbove];
     r.worst_index = r.worst_scenario = -1;
     if (r.count) {
-        r.min = conv_val(sh.ext[ls][0]); r.max = conv_val(sh.ext[ls][1]);
+        r.min = box_val_f(sh.ext[ls][0]); r.max = box_val_f(sh.ext[ls][1]);
         r.q1 = sh.q[ls][0]; r.median = sh.q[ls][1]; r.q3 = sh.q[ls][2];
         r.whisker_lo = sh.w[ls][0]; r.whisker_hi = sh.w[ls][1];
         r.n_fliers = (int)sh.fl[ls];
@@ -286,7 +268,7 @@ __global__ __launch_bounds__(kConvNT) void conv_iter_kernel(ConvIterArgs A) {
     W.n = A.n; W.S = A.S; W.c0 = s0; W.nc = nc; W.eps = A.eps;
     double acc = 0.0;                             // this thread's column, rows ascending
     conv_select(sh, W, (int)nc,
-        [&](double v, int cls, int, uint32_t) { if (cls > kClsBad) acc = conv_addd(acc, v); },
+        [&](double v, int cls, int, uint32_t) { if (cls > kClsBad) acc = acc + v; },
         [&](unsigned key, int cls, int set, uint32_t i) {
             if (cls > kClsBad && key == sh.ext[set][1]) {
                 const int idx = A.index ? A.index[i] : (int)i;
@@ -298,7 +280,7 @@ __global__ __launch_bounds__(kConvNT) void conv_iter_kernel(ConvIterArgs A) {
     sh.part[tid] = acc;
     __syncthreads();
     for (int h = kConvNT / 2; h >= 1; h >>= 1) {
-        if (tid < na && jt < h && jt + h < per) sh.part[tid] = conv_addd(sh.part[tid], sh.part[tid + h * (int)nc]);
+        if (tid < na && jt < h && jt + h < per) sh.part[tid] = sh.part[tid] + sh.part[tid + h * (int)nc];
         __syncthreads();
     }
     if (tid < (int)nc) {
@@ -354,7 +336,7 @@ __global__ __launch_bounds__(kConvNT) void conv_pool_kernel(ConvPoolArgs A) {
                     mk &= mk - 1;
                     const revs_bill_summary_t m = A.iter[(size_t)s * A.K + k];
                     if (!m.count) continue;
-                    r.total = first ? m.total : conv_addd(r.total, m.total);
+                    r.total = first ? m.total : r.total + m.total;
                     if (first || m.max > best) { best = m.max; r.worst_index = m.worst_index; r.worst_scenario = s; }
                     first = false;
                 }
@@ -495,9 +477,9 @@ __global__ __launch_bounds__(256) void conv_final_kernel(ConvFinalArgs A) {
     // the order statistics at the quartiles' lower ranks and the ranks above them
     unsigned rem4[3];
     for (int e = 0; e < 3; ++e) {
-        const unsigned long long rr = (unsigned long long)(N - 1) * (unsigned)(e + 1);
-        const unsigned rk[2] = {(unsigned)(rr >> 2), min((unsigned)(rr >> 2) + 1u, N - 1u)};
-        rem4[e] = (unsigned)(rr & 3ull);
+        unsigned rk[2];
+        box_rank(N, e + 1, rk[0], rem4[e]);
+        rk[1] = min(rk[0] + 1u, N - 1u);
         for (int j = 0; j < 2; ++j) {
             if (sum && rk[j] >= coff[tid] && rk[j] < coff[tid] + sum) {
                 unsigned below = coff[tid];
@@ -510,9 +492,8 @@ __global__ __launch_bounds__(256) void conv_final_kernel(ConvFinalArgs A) {
     }
     __syncthreads();
     if (tid == 0) {
-        for (int e = 0; e < 3; ++e) qv[e] = conv_lerp((double)os[2 * e], (double)os[2 * e + 1], 0.25 * (double)rem4[e]);
-        const double iqr = conv_sub(qv[2], qv[0]);
-        lim[0] = conv_sub(qv[0], conv_mul(1.5, iqr)); lim[1] = conv_addd(qv[2], conv_mul(1.5, iqr));
+        for (int e = 0; e < 3; ++e) qv[e] = box_quartile((double)os[2 * e], (double)os[2 * e + 1], rem4[e]);
+        box_limits(qv[0], qv[2], lim[0], lim[1]);
     }
     __syncthreads();
     for (int b = b0; b < b1; ++b) {
@@ -522,13 +503,13 @@ __global__ __launch_bounds__(256) void conv_final_kernel(ConvFinalArgs A) {
     }
     __syncthreads();
     if (tid == 0) {
-        wh[0] = (wk[0] == 0x7FFFFFFF || (double)wk[0] > qv[0]) ? qv[0] : (double)wk[0];
-        wh[1] = (wk[1] < 0 || (double)wk[1] < qv[2]) ? qv[2] : (double)wk[1];
+        wh[0] = box_whisker_lo(qv[0], wk[0] != 0x7FFFFFFF, (double)wk[0]);
+        wh[1] = box_whisker_hi(qv[2], wk[1] >= 0, (double)wk[1]);
     }
     __syncthreads();
     int f = 0;
     for (int b = b0; b < b1; ++b)
-        if ((double)b < wh[0] || (double)b > wh[1]) f += cnt[b];
+        if (box_is_flier((double)b, wh[0], wh[1])) f += cnt[b];
     if (f) atomicAdd(&nfl, f);
     __syncthreads();
     if (tid == 0) {
@@ -548,8 +529,7 @@ __global__ __launch_bounds__(256) void conv_final_kernel(ConvFinalArgs A) {
 using namespace revs;
 
 static bool conv_sizes_ok(int32_t S, int64_t n, int32_t K, int32_t G) {
-    return S >= 1 && S <= REVS_STUDY_MAX_S && n >= 1 && n < ((int64_t)1 << 31) && (int64_t)S * n < ((int64_t)1 << 31)
-           && K >= 1 && K < 0x7FFFFFFF && G >= 0 && G <= REVS_STUDY_MAX_S;
+    return study_sizes_ok(S, n) && K >= 1 && K < 0x7FFFFFFF && G >= 0 && G <= REVS_STUDY_MAX_S;
 }
 
 // the scratch: int32 cnt[S][K + 1], then uint64 code[S] (16-byte aligned)
@@ -572,8 +552,7 @@ extern "C" int revs_conv_report(int32_t S, int64_t n, int32_t K, const float *hi
     REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
     REVS_REQUIRE(n >= 1, "%s: n=%lld < 1", who, (long long)n);
     REVS_REQUIRE(K >= 1 && K < 0x7FFFFFFF, "%s: K=%d outside 1..2^31-2", who, (int)K);
-    REVS_REQUIRE(n < ((int64_t)1 << 31) && (int64_t)S * n < ((int64_t)1 << 31),
-                 "%s: S*n columns, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
+    REVS_REQUIRE(study_sizes_ok(S, n), "%s: S*n columns, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
     REVS_REQUIRE(ld >= n * S, "%s: ld=%lld < n*S=%lld", who, (long long)ld, (long long)(n * S));
     REVS_REQUIRE(patience >= 1, "%s: patience=%d < 1", who, (int)patience);
     REVS_REQUIRE(eps >= 0.0, "%s: eps=%g is negative or a NaN", who, eps);

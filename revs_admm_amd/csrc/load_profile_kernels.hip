@@ -24,9 +24,12 @@
 // (i, s) a row kernel leaves in scratch), and for both per group through a scenario -> group table.  A digit walk whose
 // tile has no open rank, and a flier walk whose tile has no flier, return at once.
 #include "common.h"
-#include "conv_keys.h"
+#include "boxplot.h"
 
 #include <math.h>
+
+// Every product and sum of this file is rounded on its own, as numpy's: no contraction to fused multiply-adds.
+#pragma clang fp contract(off)
 
 namespace revs {
 
@@ -100,9 +103,9 @@ __device__ __forceinline__ void prof_walk(const ProfArgs &A, int s, int t0, int 
             if (c >= 0) {
                 if ((u[j] & 0x7F800000u) == 0x7F800000u) kind = kPcBad;
                 else {
-                    key = conv_key(u[j]);
-                    v = conv_val(key);
-                    kind = key < kConvKey0 ? kPcNeg : key == kConvKey0 ? kPcZero : kPcPos;
+                    key = box_key_f(u[j]);
+                    v = box_val_f(key);
+                    kind = key < kBoxKey0F ? kPcNeg : key == kBoxKey0F ? kPcZero : kPcPos;
                 }
             }
             f(j, key, v, kind, c, V * col + j, i);
@@ -153,7 +156,7 @@ __global__ __launch_bounds__(kProfNT) void prof_pass0_kernel(ProfArgs A) {
             if (A.part) {
 #pragma unroll
                 for (int cc = 0; cc < REVS_PROFILE_MAX_CLASSES; ++cc)
-                    if (cc == c) acc[j][cc] = conv_addd(acc[j][cc], v);
+                    if (cc == c) acc[j][cc] = acc[j][cc] + v;
             }
         }
     });
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(kProfNT) void prof_pass0_kernel(ProfArgs A) {
     for (int h = kProfNT / 2; h >= 1; h >>= 1) {
         if (rl < h && rl + h < R) {
             for (int k = 0; k < V * nc; ++k)
-                pt[k * kProfNT + tid] = conv_addd(pt[k * kProfNT + tid], pt[k * kProfNT + tid + h * tpr]);
+                pt[k * kProfNT + tid] = pt[k * kProfNT + tid] + pt[k * kProfNT + tid + h * tpr];
         }
         __syncthreads();
     }
@@ -200,30 +203,6 @@ __global__ __launch_bounds__(kProfNT) void prof_pass0_kernel(ProfArgs A) {
             for (int c = 0; c < nc; ++c)
                 A.part[(((int64_t)blockIdx.x * A.S + P.s) * nc + c) * A.T + P.t0 + V * col + j] = pt[(j * nc + c) * kProfNT + tid];
     }
-}
-
-// The bin of a 256-bin histogram (four counts per lane) that holds rank `want`, by one wavefront: every lane gets the
-// bin, the rank inside the bin and the bin's count.
-__device__ __forceinline__ void prof_pick_bin(const uint4 cc, unsigned want, unsigned &bin, unsigned &left, unsigned &eq) {
-    const int lane = threadIdx.x & 63;
-    const unsigned own = cc.x + cc.y + cc.z + cc.w;
-    unsigned incl = own;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = (unsigned)__shfl_up((int)incl, o);
-        if (lane >= o) incl += up;
-    }
-    const unsigned excl = incl - own;
-    const bool hit = want >= excl && want < incl;                 // (one lane: want < the histogram's total)
-    unsigned b = 0, below = excl, cnt = cc.x;
-    if (want >= below + cnt) { below += cnt; b = 1; cnt = cc.y; }
-    if (b == 1 && want >= below + cnt) { below += cnt; b = 2; cnt = cc.z; }
-    if (b == 2 && want >= below + cnt) { below += cnt; b = 3; cnt = cc.w; }
-    const unsigned long long m = __ballot(hit);
-    const int src = m ? (int)__builtin_ctzll(m) : 0;
-    bin = (unsigned)__shfl((int)(4u * lane + b), src);
-    left = (unsigned)__shfl((int)(want - below), src);
-    eq = (unsigned)__shfl((int)cnt, src);
 }
 
 // ---- the pick after pass 0 (A.pass == 0) or after the digit walk of pass 1..3: one wavefront per cell; every lane
@@ -253,19 +232,17 @@ __global__ __launch_bounds__(64) void prof_pick_kernel(ProfArgs A) {
             st.count = cnt;
         }
         for (int e = 0; e < 3; ++e) {
-            const unsigned long long rr = cnt ? (unsigned long long)(cnt - 1) * (unsigned)(e + 1) : 0ull;
-            const unsigned r = (unsigned)(rr >> 2);
-            unsigned ans = 0u, left = r, eq = 0u, open = cnt ? 1u : 0u;
-            if (cnt && r >= nneg && r < nneg + nzero) {         // the rank falls among the zeros: settled
-                ans = kConvKey0; left = r - nneg; eq = nzero; open = 0u;
-            }
+            unsigned r, rem4;
+            box_rank(cnt, e + 1, r, rem4);
+            unsigned ans = 0u, left = r, eq = 0u;
+            const unsigned open = (cnt && !box_settled_at_zero(r, nneg, nzero, ans, left, eq)) ? 1u : 0u;
             if (open) {                           // (uniform)
                 unsigned bin;
-                prof_pick_bin(cc, r, bin, left, eq);
+                pick_bin(cc, r, bin, left, eq);
                 ans = bin << 24;
             }
             if (lane == 0) {
-                st.rank[e] = r; st.rem4[e] = (unsigned)(rr & 3ull);
+                st.rank[e] = r; st.rem4[e] = rem4;
                 st.ans[e] = ans; st.left[e] = left; st.eq[e] = eq; st.open[e] = open;
             }
         }
@@ -279,13 +256,13 @@ __global__ __launch_bounds__(64) void prof_pick_kernel(ProfArgs A) {
             const uint4 cc = *h;
             *h = make_uint4(0u, 0u, 0u, 0u);      // (the next digit walk adds into zeros)
             unsigned bin;
-            prof_pick_bin(cc, left, bin, left, eq);
+            pick_bin(cc, left, bin, left, eq);
             if (lane == 0) { st.ans[e] |= bin << shift; st.left[e] = left; st.eq[e] = eq; }
         }
         if (A.pass == 3 && lane == 0) {
             // the upper neighbour: where the next order statistic is another value
             const unsigned cnt = st.count, r = st.rank[e], cle = r - left + eq;      // cle: values <= the statistic
-            st.need[e] = (cnt && st.rem4[e] != 0u && r + 1 < cnt && cle <= r + 1) ? 1u : 0u;
+            st.need[e] = (st.rem4[e] != 0u && box_next_differs(r, cnt, cle)) ? 1u : 0u;
         }
     }
 }
@@ -381,7 +358,7 @@ __global__ __launch_bounds__(kProfNT) void prof_scan_kernel(ProfArgs A) {
                     if (v <= lim[ls * 2 + 1] && key > o[ls * 4 + 1]) atomicMax(&o[ls * 4 + 1], key);
                 }
             } else {
-                conv_add(o, ok && a[ls * 4] && (v < lim[ls * 2] || v > lim[ls * 2 + 1]), (unsigned)(ls * 4));
+                conv_add(o, ok && a[ls * 4] && box_is_flier(v, lim[ls * 2], lim[ls * 2 + 1]), (unsigned)(ls * 4));
             }
         }
     });
@@ -405,20 +382,18 @@ __global__ __launch_bounds__(256) void prof_cell_kernel(ProfArgs A, int64_t ncel
     if (!st.count) return;
     if (A.pass == 0) {
         for (int e = 0; e < 3; ++e) {
-            const double lo = conv_val(st.ans[e]);
-            const double hi = st.need[e] ? conv_val(~st.nb_inv[e]) : lo;
-            st.q[e] = conv_lerp(lo, hi, 0.25 * (double)st.rem4[e]);
+            const double lo = box_val_f(st.ans[e]);
+            const double hi = st.need[e] ? box_val_f(~st.nb_inv[e]) : lo;
+            st.q[e] = box_quartile(lo, hi, st.rem4[e]);
         }
-        const double iqr = conv_sub(st.q[2], st.q[0]);
-        st.lim[0] = conv_sub(st.q[0], conv_mul(1.5, iqr));
-        st.lim[1] = conv_addd(st.q[2], conv_mul(1.5, iqr));
+        box_limits(st.q[0], st.q[2], st.lim[0], st.lim[1]);
     } else {
         const double q1 = st.q[0], q3 = st.q[2];
         const unsigned k0 = ~st.wk_lo_inv, k1 = st.wk_hi;
-        const double wlo = (k0 == 0xFFFFFFFFu || conv_val(k0) > q1) ? q1 : conv_val(k0);
-        const double whi = (k1 == 0u || conv_val(k1) < q3) ? q3 : conv_val(k1);
+        const double wlo = box_whisker_lo(q1, k0 != 0xFFFFFFFFu, box_val_f(k0));
+        const double whi = box_whisker_hi(q3, k1 != 0u, box_val_f(k1));
         st.w[0] = wlo; st.w[1] = whi;
-        st.any_fl = (conv_val(~st.ext_lo_inv) < wlo || conv_val(st.ext_hi) > whi) ? 1u : 0u;
+        st.any_fl = (box_val_f(~st.ext_lo_inv) < wlo || box_val_f(st.ext_hi) > whi) ? 1u : 0u;
     }
 }
 
@@ -435,7 +410,7 @@ __global__ __launch_bounds__(64) void prof_finish_kernel(ProfArgs A) {
     r.count = (int)st.count; r.n_nan = (int)st.cnt[kPcBad]; r.n_fliers = 0; r.n_above = (int)st.cnt[kPcAbove];
     r.worst_index = r.worst_scenario = -1;
     if (r.count) {
-        r.min = conv_val(~st.ext_lo_inv); r.max = conv_val(st.ext_hi);
+        r.min = box_val_f(~st.ext_lo_inv); r.max = box_val_f(st.ext_hi);
         r.q1 = st.q[0]; r.median = st.q[1]; r.q3 = st.q[2];
         r.whisker_lo = st.w[0]; r.whisker_hi = st.w[1];
         r.n_fliers = (int)st.fl;
@@ -447,9 +422,9 @@ __global__ __launch_bounds__(64) void prof_finish_kernel(ProfArgs A) {
             for (int c = all ? 0 : q; c < (all ? A.ncls : q + 1); ++c) {
                 double acc = 0.0;
                 for (int ch = lane; ch < A.nchunks; ch += 64)
-                    acc = conv_addd(acc, A.part[(((int64_t)ch * A.S + grp) * A.ncls + c) * A.T + t]);
+                    acc = acc + A.part[(((int64_t)ch * A.S + grp) * A.ncls + c) * A.T + t];
                 acc = wave_sum_d(acc);
-                if (A.st[(grp * A.Q + c) * A.T + t].count) { r.total = first ? acc : conv_addd(r.total, acc); first = false; }
+                if (A.st[(grp * A.Q + c) * A.T + t].count) { r.total = first ? acc : r.total + acc; first = false; }
             }
             r.worst_index = 0x7FFFFFFF - (int)st.worst; r.worst_scenario = (int)grp;
         } else {
@@ -461,7 +436,7 @@ __global__ __launch_bounds__(64) void prof_finish_kernel(ProfArgs A) {
                 if (A.group_of[s] != (int)grp) continue;
                 const revs_bill_summary_t m = A.member[((int64_t)s * A.Q + q) * A.T + t];
                 if (!m.count) continue;
-                r.total = first ? m.total : conv_addd(r.total, m.total);
+                r.total = first ? m.total : r.total + m.total;
                 if (first || m.max > best) { best = m.max; r.worst_index = m.worst_index; r.worst_scenario = s; }
                 first = false;
             }
@@ -490,14 +465,14 @@ __global__ __launch_bounds__(256) void prof_rows_kernel(ProfRowArgs A) {
         for (int t = l; t < A.T; t += A.L) {
             const unsigned u = __float_as_uint(p[t]);
             if ((u & 0x7F800000u) == 0x7F800000u) bad = 1u;
-            else best = max(best, conv_key(u));
+            else best = max(best, box_key_f(u));
         }
     }
     for (int o = 1; o < A.L; o <<= 1) {
         best = max(best, (unsigned)__shfl_xor((int)best, o));
         bad |= (unsigned)__shfl_xor((int)bad, o);
     }
-    if (row < A.rows && l == 0) A.peaks[s * A.n + i] = bad ? __builtin_nanf("") : (float)conv_val(best);
+    if (row < A.rows && l == 0) A.peaks[s * A.n + i] = bad ? __builtin_nanf("") : (float)box_val_f(best);
 }
 
 // ---- the day figures of every (scenario, set) from the records the call wrote
@@ -519,7 +494,7 @@ __global__ __launch_bounds__(256) void prof_day_kernel(ProfDayArgs A) {
         if (!m.count) continue;
         if (!d.slots || m.total > d.peak) { d.peak = m.total; d.peak_slot = t; }
         if (!d.slots || m.total < d.valley) { d.valley = m.total; d.valley_slot = t; }
-        energy = conv_addd(energy, m.total);
+        energy = energy + m.total;
         ++d.slots;
     }
     if (d.slots) {
@@ -554,8 +529,7 @@ struct ProfLayout {
     int64_t state, h0, hg, zeroed, part, peaks, table, slot_rec, peak_rec, total;
 };
 static bool prof_layout(int32_t S, int64_t n, int32_t T, int32_t C, int32_t G, ProfLayout &L) {
-    if (!(S >= 1 && S <= REVS_STUDY_MAX_S && T >= 1 && T <= REVS_MAX_T && n >= 1 && n < ((int64_t)1 << 31)
-          && (int64_t)S * n < ((int64_t)1 << 31) && C >= 0 && C <= REVS_PROFILE_MAX_CLASSES && G >= 0 && G <= S))
+    if (!(study_sizes_ok(S, n) && T >= 1 && T <= REVS_MAX_T && C >= 0 && C <= REVS_PROFILE_MAX_CLASSES && G >= 0 && G <= S))
         return false;
     const int64_t ncls = C ? C : 1, Q = C + 1, NG = S > G ? S : G, chunks = (n + kProfChunk - 1) / kProfChunk;
     L.state = 0;
@@ -633,13 +607,10 @@ extern "C" int revs_load_profile(int32_t S, int64_t n, int32_t T, const float *g
     REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
     REVS_REQUIRE(T >= 1 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
     REVS_REQUIRE(n >= 1, "%s: n=%lld < 1", who, (long long)n);
-    REVS_REQUIRE(n < ((int64_t)1 << 31) && (int64_t)S * n < ((int64_t)1 << 31),
-                 "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
+    REVS_REQUIRE(study_sizes_ok(S, n), "%s: S*n rows, 2^31 or more (S=%d, n=%lld)", who, (int)S, (long long)n);
     REVS_REQUIRE(C >= 0 && C <= REVS_PROFILE_MAX_CLASSES, "%s: C=%d outside 0..%d", who, (int)C, REVS_PROFILE_MAX_CLASSES);
     REVS_REQUIRE((cls != nullptr) == (C > 0), "%s: cls and C=%d disagree (cls = NULL needs C = 0, classes need cls)", who, (int)C);
-    const bool inner_i = stride_i >= T && stride_s / stride_i >= n;
-    const bool inner_s = stride_s >= T && stride_i / stride_s >= S;
-    REVS_REQUIRE(inner_i || inner_s, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
+    REVS_REQUIRE(rows_inner_i(S, n, T, stride_s, stride_i) >= 0, "%s: rows overlap under stride_s=%lld, stride_i=%lld (S=%d, n=%lld, T=%d)", who,
                  (long long)stride_s, (long long)stride_i, (int)S, (long long)n, (int)T);
     REVS_REQUIRE(above == above, "%s: above is a NaN", who);
     REVS_REQUIRE(g, "%s: null pointer argument g", who);

@@ -19,6 +19,7 @@
 // reduction) and ONE barrier each, on values that never leave the registers.  A bitonic sort of the same 16 384
 // doubles is 55 barrier-separated stages per quantity with 128 KB of LDS traffic in each.
 #include "common.h"
+#include "boxplot.h"
 #include "tree_body.h"
 
 #include <math.h>
@@ -84,58 +85,14 @@ struct NetArgs {
 
 constexpr unsigned long long kNoKey = ~0ull;     // an entry left out of the summary (no trial key is above 2^63)
 constexpr unsigned long long kNanKey = ~0ull - 1;    // staged only: a rated line / masked node whose value is a NaN
-constexpr int kNetRed = 8;                       // values one block reduction carries
 
-// doubles behind the scans' LDS: kNetRed per wavefront for the reductions, two count buffers of 16 bytes per wavefront
+// doubles behind the scans' LDS: kBlockRed per wavefront for the reductions, two count buffers of 16 bytes per wavefront
 __host__ __device__ inline size_t net_lds_bytes(int n) {
     const TreeShape sh = tree_shape(n);
-    return tree_lds_bytes(n) + sizeof(double) * (size_t)(sh.nt / 64) * (kNetRed + 4);
-}
-
-__device__ __forceinline__ unsigned long long uniform_u64(unsigned long long v) {      // a value every lane holds, into SGPRs
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return (unsigned long long)hi << 32 | lo;
-}
-__device__ __forceinline__ double uniform_d(double v) {
-    return __longlong_as_double((long long)uniform_u64((unsigned long long)__double_as_longlong(v)));
-}
-
-// max / sum of N values over the workgroup, every thread gets them; `red`: NT / 64 * kNetRed doubles.  Sums are of
-// counts (exact in doubles: any order gives the same bits).
-template <int NT, int N, bool SUM>
-__device__ __forceinline__ void block_reduce_multi(double (&v)[N], double *red) {
-    static_assert(N <= kNetRed, "");
-    const int tid = threadIdx.x, wave = tid >> 6;
-#pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = SUM ? wave_sum_d(v[e]) : wave_max_d(v[e]);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) red[wave * kNetRed + e] = v[e];
-    }
-    __syncthreads();
-    // the wavefronts' values across the first NT / 64 lanes of a row of 16, combined by rotations inside the row (one
-    // load per value in flight, not NT / 64), then into SGPRs: every lane holds the same
-    const int lane = tid & 63;
-#pragma unroll
-    for (int e = 0; e < N; ++e) {
-        double r = lane < NT / 64 ? red[lane * kNetRed + e] : (SUM ? 0.0 : -__builtin_inf());
-        r = SUM ? r + dpp_rot_d<0x128>(r) : fmax(r, dpp_rot_d<0x128>(r));          // (all four: every lane of the row
-        r = SUM ? r + dpp_rot_d<0x124>(r) : fmax(r, dpp_rot_d<0x124>(r));          //  ends with the row's total)
-        r = SUM ? r + dpp_rot_d<0x122>(r) : fmax(r, dpp_rot_d<0x122>(r));
-        r = SUM ? r + dpp_rot_d<0x121>(r) : fmax(r, dpp_rot_d<0x121>(r));
-        v[e] = uniform_d(r);
-    }
-    __syncthreads();
+    return tree_lds_bytes(n) + sizeof(double) * (size_t)(sh.nt / 64) * (kBlockRed + 4);
 }
 
 __device__ __forceinline__ double key_val(unsigned long long k) { return __longlong_as_double((long long)k); }   // kNoKey: a NaN
-
-// numpy.percentile's linear interpolation between the order statistics a <= b at fraction t (_lerp), without
-// contraction to fused multiply-adds: the same roundings as numpy's
-__device__ __forceinline__ double np_lerp(double a, double b, double t) {
-    const double d = __dsub_rn(b, a);
-    return t >= 0.5 ? __dsub_rn(b, __dmul_rn(d, __dsub_rn(1.0, t))) : __dadd_rn(a, __dmul_rn(d, t));
-}
 
 // flow_j = C[end_j] - C[j] at this thread's positions (a), C the inclusive prefix of the injections in preorder.
 // se[i]: the low half of pack (src + 1 | end << 16).  Ends behind a barrier: every read of C is done.
@@ -236,7 +193,7 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A0) {
     const int jl = act ? j0 : 0;                                    // (threads beyond the tree load position 0's data, unused)
     double *base = lds + 2, *red0 = lds + 2 + NT * IPT, *red1 = red0 + NT / 64;
     double *red = red1 + NT / 64;                                   // block_reduce_multi's
-    unsigned long long *cbuf = reinterpret_cast<unsigned long long *>(red + (NT / 64) * kNetRed);   // [2][NT / 64][2]
+    unsigned long long *cbuf = reinterpret_cast<unsigned long long *>(red + (NT / 64) * kBlockRed);   // [2][NT / 64][2]
     // Registers: the 1024 x 16 shape has 128 per thread, and IPT doubles are 2 IPT of them.  The packed indices are
     // held as the half a phase needs; and where IPT = 16 the loading keys are not carried through the voltage
     // scans beside a, b and those indices -- the flow scan is run again behind them (the same bits: its order is
@@ -501,18 +458,15 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A0) {
 #pragma unroll
     for (int e = 0; e < 6; ++e) {
         const double lo = key_val(ans[e]);
-        const bool last = rank[e] + 1 >= kcnt[e / 3];               // (numpy clips the upper index to k - 1)
+        const bool last = rank[e] + 1 >= kcnt[e / 3];               // (numpy clips the upper index to k - 1; the rule
+                                                                    //  is boxplot.h's box_next_differs: keep them in step)
         const double hi = (last || (int)cle[e] > rank[e] + 1) ? lo : -nxt[e];
-        qv[e] = np_lerp(lo, hi, 0.25 * (double)rem[e]);
+        qv[e] = box_quartile(lo, hi, (unsigned)rem[e]);
     }
     // ---- whiskers: the farthest datum within 1.5 IQR of the box (matplotlib.cbook.boxplot_stats), then the fliers
     double lim[4], wk[4] = {ninf, ninf, ninf, ninf};                // -whisker_lo, whisker_hi of {loading, volt}
 #pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const double iqr = __dsub_rn(qv[3 * q + 2], qv[3 * q]);
-        lim[2 * q] = __dsub_rn(qv[3 * q], __dmul_rn(1.5, iqr));
-        lim[2 * q + 1] = __dadd_rn(qv[3 * q + 2], __dmul_rn(1.5, iqr));
-    }
+    for (int q = 0; q < 2; ++q) box_limits(qv[3 * q], qv[3 * q + 2], lim[2 * q], lim[2 * q + 1]);
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
         const double l = key_val(lkey[i]), v = key_val(vkey[i]);    // (a NaN for an entry left out: every test fails)
@@ -525,14 +479,14 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A0) {
     double wlo[2], whi[2], fl[2] = {0.0, 0.0};
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        wlo[q] = (wk[2 * q] == ninf || -wk[2 * q] > qv[3 * q]) ? qv[3 * q] : -wk[2 * q];
-        whi[q] = (wk[2 * q + 1] == ninf || wk[2 * q + 1] < qv[3 * q + 2]) ? qv[3 * q + 2] : wk[2 * q + 1];
+        wlo[q] = box_whisker_lo(qv[3 * q], wk[2 * q] != ninf, -wk[2 * q]);
+        whi[q] = box_whisker_hi(qv[3 * q + 2], wk[2 * q + 1] != ninf, wk[2 * q + 1]);
     }
 #pragma unroll
     for (int i = 0; i < IPT; ++i) {
         const double l = key_val(lkey[i]), v = key_val(vkey[i]);
-        fl[0] += (l < wlo[0] || l > whi[0]) ? 1.0 : 0.0;
-        fl[1] += (v < wlo[1] || v > whi[1]) ? 1.0 : 0.0;
+        fl[0] += box_is_flier(l, wlo[0], whi[0]) ? 1.0 : 0.0;
+        fl[1] += box_is_flier(v, wlo[1], whi[1]) ? 1.0 : 0.0;
     }
     block_reduce_multi<NT, 2, true>(fl, red);
 
@@ -567,37 +521,23 @@ __global__ __launch_bounds__(NT) void net_report_kernel(NetArgs A0) {
 
 
 // ---- the pooled selection (revs_net_study, second launch): one workgroup per (slot, quantity, group) over the staged
-// keys of the group's scenarios.  The k-th smallest key by digits of 8 bits from the top: a pass counts, among the keys
-// that share the prefix found so far, the next digit's 256 values in LDS; the three quartile ranks keep a prefix each
-// and share a histogram while their prefixes agree.  The counts are integers: LDS atomics in any order give the same
-// bits.  The last pass leaves, for free, the number of keys below and equal to each order statistic.
+// keys of the group's scenarios: pass 0 here, then box_select64 (boxplot.h).
 constexpr int kPoolNT = 1024;
-constexpr int kPoolMaskWords = 448;               // member bit masks of the groups of one launch (3.5 KB of arguments)
 struct PoolArgs {
     const unsigned long long *stage;              // [2][T][S][n]
     const int32_t *nop;                           // node_of_pos, or NULL
     revs_net_pooled_t *out;                       // [G][2][T]
     int32_t S, T, n, n_out, g0, words;
     double vmin, vmax;
-    unsigned long long member[kPoolMaskWords];    // [groups of this launch][words]: bit s of a group's mask: scenario s
+    unsigned long long member[kGroupMaskWords];   // [groups of this launch][words]: bit s of a group's mask: scenario s
 };
 
-// one count into h[d] per matching lane: by the first matching lane alone when the wavefront's digits agree (the common
-// case in the top passes, where 64 atomics on one address would queue)
-__device__ __forceinline__ void pool_hist_add(unsigned *h, bool match, unsigned d) {
-    const unsigned long long m = __ballot(match);
-    if (m == 0ull) return;
-    const int first = (int)__builtin_ctzll(m);
-    const unsigned d0 = (unsigned)__builtin_amdgcn_readlane((int)d, first);
-    if (__ballot(match && d == d0) == m) {
-        if ((int)(threadIdx.x & 63) == first) atomicAdd(h + d0, (unsigned)__popcll(m));
-    } else if (match) {
-        atomicAdd(h + d, 1u);
-    }
-}
-
-// f(key, scenario, position) over every staged key of the group, every thread the same number of times (threads past
-// the row's end see kNoKey): the callers' lane masks and reductions stay whole
+// f(ordered key, ok, value, scenario, position) over every staged key of the group, every thread the same number of
+// times (threads past the row's end see kNoKey): the callers' lane masks and reductions stay whole.  A staged value is
+// a non-negative double, +0.0 for -0.0: its bits with the top bit set are its ordered key.  kNoKey and kNanKey come
+// with that bit and lose it: not ok, a key below every ordered key of the sample -- no prefix of theirs is a prefix of
+// an order statistic -- and a NaN for the value, which fails every test.  (All of this rests on the staged values
+// being non-negative, as the parent's raw-bit keys did: a negative one would come with the top bit, too.)
 template <class F>
 __device__ __forceinline__ void pool_for_each(const PoolArgs &A, const unsigned long long *member, const unsigned long long *rows, F f) {
     for (int w = 0; w < A.words; ++w) {
@@ -610,19 +550,17 @@ __device__ __forceinline__ void pool_for_each(const PoolArgs &A, const unsigned 
                 const int j = jb + 2 * (int)threadIdx.x;
                 TreeU2 k{{kNoKey, kNoKey}};
                 if (j < A.n) k = *reinterpret_cast<const TreeU2 *>(row + j);       // (n is even: j + 1 < n)
-                f(k.v[0], s, j);
-                f(k.v[1], s, j + 1);
+                f(k.v[0] ^ 1ull << 63, (k.v[0] >> 63) == 0ull, key_val(k.v[0]), s, j);
+                f(k.v[1] ^ 1ull << 63, (k.v[1] >> 63) == 0ull, key_val(k.v[1]), s, j + 1);
             }
         }
     }
 }
 
 __global__ __launch_bounds__(kPoolNT) void net_pool_kernel(PoolArgs A) {
-    __shared__ alignas(16) unsigned hist[3 * 256];
-    __shared__ double red[(kPoolNT / 64) * kNetRed];
-    __shared__ unsigned found[3][4];              // per rank: digit, rank left inside the bin, the bin's count
+    __shared__ BoxSelect<kPoolNT> sh;
     constexpr int NT = kPoolNT;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int t = (int)blockIdx.x, q = (int)blockIdx.y, gl = (int)blockIdx.z;
     const unsigned long long *member = A.member + (size_t)gl * A.words;
     const unsigned long long *rows = A.stage + ((int64_t)q * A.T + t) * A.S * A.n;
@@ -630,25 +568,29 @@ __global__ __launch_bounds__(kPoolNT) void net_pool_kernel(PoolArgs A) {
     const double vmin = A.vmin, vmax = A.vmax;
     // a value's excursion: the loading itself / the distance outside (negative: inside) the voltage band
     auto exc = [&](double v) { return q ? fmax(vmin - v, v - vmax) : v; };
+    auto walk = [&](auto f) { pool_for_each(A, member, rows, f); };
+    // (for the selection every element is "ok": the key and the value of one that is not keep it out by themselves,
+    //  which spares the digit passes a second condition per count)
+    auto walk_keys = [&](auto f) {
+        pool_for_each(A, member, rows, [&](unsigned long long k, bool, double v, int s, int j) { f(k, true, v, s, j); });
+    };
 
-    for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
+    for (int i = tid; i < 3 * 256; i += NT) sh.hist[i] = 0u;
     __syncthreads();
     // ---- pass 0: counts and extremes, and the top digit's histogram (one prefix: the empty one)
     double s[3] = {0.0, 0.0, 0.0};                // values, NaNs, violations
     double x[3] = {ninf, ninf, ninf};             // -min, max, largest excursion
-    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
-        const bool ok = (k >> 63) == 0ull;
-        const double v = key_val(k);
+    walk([&](unsigned long long k, bool ok, double v, int, int) {
         s[0] += ok ? 1.0 : 0.0;
-        s[1] += k == kNanKey ? 1.0 : 0.0;
+        s[1] += k == (kNanKey ^ 1ull << 63) ? 1.0 : 0.0;
         if (ok) {
             s[2] += (q ? (v < vmin || v > vmax) : v > 1.0) ? 1.0 : 0.0;
             x[0] = fmax(x[0], -v); x[1] = fmax(x[1], v); x[2] = fmax(x[2], exc(v));
         }
-        pool_hist_add(hist, ok, (unsigned)(k >> 56));
+        hist_add(sh.hist, ok, (unsigned)(k >> 56));
     });
-    block_reduce_multi<NT, 3, true>(s, red);
-    block_reduce_multi<NT, 3, false>(x, red);
+    block_reduce_multi<NT, 3, true>(s, sh.red);
+    block_reduce_multi<NT, 3, false>(x, sh.red);
     const int kcnt = (int)s[0];
     revs_net_pooled_t r;
     const double nan = __builtin_nan("");
@@ -661,115 +603,22 @@ __global__ __launch_bounds__(kPoolNT) void net_pool_kernel(PoolArgs A) {
         if (tid == 0) *out = r;
         return;
     }
-    // ---- the quartiles' lower order statistics: rank (k - 1) e / 4, e = 1, 2, 3
-    int rank[3], rem4[3];
-    unsigned left[3], eq[3] = {0u, 0u, 0u};       // rank left among the keys that share the prefix; keys equal to ans
-    unsigned long long ans[3] = {0ull, 0ull, 0ull};
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const long long rr = (long long)(kcnt - 1) * (e + 1);
-        rank[e] = (int)(rr >> 2); rem4[e] = (int)(rr & 3);
-        left[e] = (unsigned)rank[e];
-    }
-#pragma unroll 1
-    for (int pass = 0; pass < 8; ++pass) {
-        const int shift = 56 - 8 * pass;
-        // ranks whose prefixes agree share a histogram (the prefixes ascend with the ranks: equal ones are adjacent)
-        int slot[3] = {0, 0, 0};
-        if (pass > 0) {
-            slot[1] = ans[1] == ans[0] ? 0 : 1;
-            slot[2] = ans[2] == ans[1] ? slot[1] : 2;
-            const bool own1 = slot[1] == 1, own2 = slot[2] == 2;
-            const unsigned long long p0 = ans[0] >> (shift + 8), p1 = ans[1] >> (shift + 8), p2 = ans[2] >> (shift + 8);
-            pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
-                const unsigned long long pk = k >> (shift + 8);
-                const unsigned d = (unsigned)(k >> shift) & 0xFFu;
-                pool_hist_add(hist, pk == p0, d);
-                if (own1) pool_hist_add(hist + 256, pk == p1, d);
-                if (own2) pool_hist_add(hist + 512, pk == p2, d);
-            });
-        }
-        __syncthreads();
-        // the bin that holds each rank: wavefront e for rank e, four bins per lane, a prefix sum across the lanes
-        if (wave < 3) {
-            const unsigned *h = hist + 256 * slot[wave];
-            const uint4 c = *reinterpret_cast<const uint4 *>(h + 4 * lane);
-            const unsigned own = c.x + c.y + c.z + c.w;
-            unsigned incl = own;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned up = (unsigned)__shfl_up((int)incl, o);
-                if (lane >= o) incl += up;
-            }
-            const unsigned want = left[wave], excl = incl - own;
-            if (want >= excl && want < incl) {    // (one lane: the bins' counts sum to more than the rank left)
-                unsigned b = 0, below = excl, cnt = c.x;
-                if (want >= below + cnt) { below += cnt; b = 1; cnt = c.y; }
-                if (b == 1 && want >= below + cnt) { below += cnt; b = 2; cnt = c.z; }
-                if (b == 2 && want >= below + cnt) { below += cnt; b = 3; cnt = c.w; }
-                found[wave][0] = 4u * lane + b; found[wave][1] = want - below; found[wave][2] = cnt;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            ans[e] = uniform_u64(ans[e] | (unsigned long long)found[e][0] << shift);       // (every lane holds the same)
-            left[e] = __builtin_amdgcn_readfirstlane(found[e][1]); eq[e] = __builtin_amdgcn_readfirstlane(found[e][2]);
-        }
-        __syncthreads();                          // (every read of hist and found is done)
-        for (int i = tid; i < 3 * 256; i += NT) hist[i] = 0u;
-        __syncthreads();
-    }
-    // ---- the upper neighbours (the smallest key above each), and the worst entry: lowest scenario, then lowest index
-    double nxt[3] = {ninf, ninf, ninf};
+    // ---- the selection; in its neighbour walk the worst entry: the largest excursion, lowest scenario, then lowest index
     double wcode = ninf, vworst = nan;            // -(scenario * 65536 + caller's index): exact in a double
-    pool_for_each(A, member, rows, [&](unsigned long long k, int sidx, int j) {
-        if ((k >> 63) != 0ull) return;
-        const double v = key_val(k);
-#pragma unroll
-        for (int e = 0; e < 3; ++e)
-            if (k > ans[e]) nxt[e] = fmax(nxt[e], -v);
+    const BoxFigures b = box_select64(sh, kcnt, walk_keys, [&](unsigned long long, bool, double v, int sidx, int j) {
         if (exc(v) == x[2]) {
             const int nd = A.nop ? A.nop[j] : j;
             const double code = -((double)sidx * 65536.0 + (double)nd);
             if (code > wcode) { wcode = code; vworst = v; }
         }
     });
-    block_reduce_multi<NT, 3, false>(nxt, red);
     double wc[1] = {wcode};
-    block_reduce_multi<NT, 1, false>(wc, red);
-    double qv[3];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const double lo = key_val(ans[e]);
-        const int cle = rank[e] - (int)left[e] + (int)eq[e];        // keys <= the order statistic
-        const bool last = rank[e] + 1 >= kcnt;
-        const double hi = (last || cle > rank[e] + 1) ? lo : -nxt[e];
-        qv[e] = np_lerp(lo, hi, 0.25 * (double)rem4[e]);
-    }
-    // ---- whiskers and fliers, as net_report_kernel's
-    const double iqr = __dsub_rn(qv[2], qv[0]);
-    const double lim0 = __dsub_rn(qv[0], __dmul_rn(1.5, iqr)), lim1 = __dadd_rn(qv[2], __dmul_rn(1.5, iqr));
-    double wk[2] = {ninf, ninf};
-    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
-        const double v = key_val(k);              // (a NaN for an entry left out: every test fails)
-        if (v >= lim0) wk[0] = fmax(wk[0], -v);
-        if (v <= lim1) wk[1] = fmax(wk[1], v);
-    });
-    block_reduce_multi<NT, 2, false>(wk, red);
-    const double wlo = (wk[0] == ninf || -wk[0] > qv[0]) ? qv[0] : -wk[0];
-    const double whi = (wk[1] == ninf || wk[1] < qv[2]) ? qv[2] : wk[1];
-    double fl[1] = {0.0};
-    pool_for_each(A, member, rows, [&](unsigned long long k, int, int) {
-        const double v = key_val(k);
-        fl[0] += (v < wlo || v > whi) ? 1.0 : 0.0;
-    });
-    block_reduce_multi<NT, 1, true>(fl, red);
+    block_reduce_multi<NT, 1, false>(wc, sh.red);
     if (tid == 0) {
         const long long code = (long long)-wc[0];
-        r.min = -x[0]; r.q1 = qv[0]; r.median = qv[1]; r.q3 = qv[2]; r.max = x[1];
-        r.whisker_lo = wlo; r.whisker_hi = whi;
-        r.n_fliers = (int)fl[0];
+        r.min = -x[0]; r.q1 = b.q[0]; r.median = b.q[1]; r.q3 = b.q[2]; r.max = x[1];
+        r.whisker_lo = b.wlo; r.whisker_hi = b.whi;
+        r.n_fliers = b.n_fliers;
         r.worst_scenario = (int)(code >> 16); r.worst_index = (int)(code & 0xFFFF);
         if (q == 0) r.worst_value = x[1];
         *out = r;
@@ -890,18 +739,12 @@ extern "C" int revs_net_study(int32_t S, int32_t m, int32_t T, const revs_tree_t
                                       bands ? B : 0, flow_out, loading_out, volt_out, summary_out, band_count_out,
                                       pooled ? scratch : nullptr, stream);
     if (rc2 != REVS_OK || !pooled) return rc2;
-    // the groups' member masks travel as kernel arguments: as many groups per launch as kPoolMaskWords holds
     PoolArgs P;
     P.stage = (const unsigned long long *)scratch; P.nop = node_of_pos; P.out = pooled_out;
     P.S = S; P.T = T; P.n = tree->n; P.n_out = n_out; P.words = (S + 63) / 64;
     P.vmin = vmin; P.vmax = vmax;
-    const int per = kPoolMaskWords / P.words;
-    for (int g0 = 0; g0 < G; g0 += per) {
-        const int ng = G - g0 < per ? G - g0 : per;
-        for (int i = 0; i < kPoolMaskWords; ++i) P.member[i] = 0ull;
-        for (int s = 0; s < S; ++s)
-            if (group[s] >= g0 && group[s] < g0 + ng)
-                P.member[(size_t)(group[s] - g0) * P.words + s / 64] |= 1ull << (s % 64);
+    for (int g0 = 0, ng; g0 < G; g0 += ng) {
+        ng = pack_group_masks(group, S, G, g0, P.member);
         P.g0 = g0;
         hipLaunchKernelGGL(net_pool_kernel, dim3(T, 2, ng), dim3(kPoolNT), 0, (hipStream_t)stream, P);
         REVS_CHECK_LAUNCH(who);

@@ -302,3 +302,26 @@ def test_invariants(gpu_lib):
                 assert r.dev is None or same_bits(r.dev, a.dev)
                 assert r.summary_dev is None or (same_bits(r.summary_dev, a.summary_dev) and same_bits(r.summary_bill, a.summary_bill))
                 assert r.pooled_dev is None or (same_bits(r.pooled_dev, a.pooled_dev) and same_bits(r.pooled_bill, a.pooled_bill))
+
+
+@pytest.mark.parametrize("n", [1, 2, 1025])
+@pytest.mark.parametrize("case", ["all_equal", "first_digit"])
+def test_records_ranks_share_or_part(gpu_lib, n, case):
+    """The selection where the three ranks share a prefix through all eight digits (every value equal) and where they
+    part at the first (both signs, magnitudes 2^-900 .. 2^900): rows of 1, 2 and 1025 entries, three scenarios in pools
+    of two and of one."""
+    rng = np.random.default_rng(60 + n)
+    if case == "all_equal":
+        bill, base = np.full((3, n), 3.25), [1, 0, -1]
+    else:
+        bill = rng.choice([-1.0, 1.0], (3, n)) * 2.0 ** rng.integers(-900, 901, (3, n)).astype(np.float64)
+        base = [-1, -1, -1]                          # (no deviations: their quotients would overflow)
+    r = check(gpu_lib, bill, base, None, None, [0, 0, 1], f"{case}, n={n}")
+    assert r.pooled_bill["count"].tolist() == [2 * n, n]
+    assert same_bits(r.pooled_bill[1], r.summary_bill[2])
+    if case == "all_equal":
+        for k in ("min", "q1", "median", "q3", "max", "whisker_lo", "whisker_hi"):
+            assert (r.pooled_bill[k] == 3.25).all() and (r.summary_bill[k] == 3.25).all(), k
+        assert (r.pooled_bill["n_fliers"] == 0).all() and (r.pooled_dev["q1"][0] == 0.0)
+    elif n == 1025:
+        assert r.pooled_bill["q1"][0] < 0.0 < r.pooled_bill["q3"][0]       # (another sign: another first digit)

@@ -206,6 +206,21 @@ def test_summary_is_exact(gpu_lib, case):
         assert np.array_equal(rep.summary_volt["median"], rep.volt[1234])
 
 
+def test_datum_on_the_whisker_limit(gpu_lib):
+    """numpy rounds 1.5 (q3 - q1) and then the sum: a loading equal to that limit is the upper whisker, not a flier."""
+    from revs_admm_amd.network import report_for_tree
+    from whisker_case import datum_on_the_upper_limit
+    par, er, cons, p, rating, hival = datum_on_the_upper_limit()
+    rep = report_for_tree(par, er, cons, p, rating=rating, vset=1.0)
+    assert rep.loading[8, 0] == hival and rep.loading[:8, 0].max() < hival       # (the input is what it was made to be)
+    b = nr.box_stats(rep.loading[:, 0])
+    assert b["whisker_hi"] == hival and b["n_fliers"] == int((rep.loading[:, 0] < b["whisker_lo"]).sum())
+    g = rep.summary_loading[0]
+    print(f"upper limit {hival!r}: whisker_hi {g['whisker_hi']!r}, fliers {g['n_fliers']} (numpy {b['n_fliers']})")
+    assert g["whisker_hi"] == hival and g["n_fliers"] == b["n_fliers"]
+    check_summary(rep, rating, None, 9)
+
+
 @pytest.mark.parametrize("tag", ["dis_a90_r4800", "cen_a90_r4800", "ind_a90_r4800"])
 def test_stored_results_of_the_reference(gpu_lib, golden, golden_net, tag):
     """The report of the reference's own stored schedules: the dense restatement's figures (recomputed here, not

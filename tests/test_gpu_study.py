@@ -378,3 +378,54 @@ def test_a_study_leaves_engines_alone(gpu_lib):
     assert all(np.array_equal(x, y) for x, y in zip(state(a), state(b)))
     after = b.network_report(rating=rating, nodes=nodes)
     assert after.volt.tobytes() == ref.volt.tobytes() and after.summary_loading.tobytes() == ref.summary_loading.tobytes()
+
+
+def test_pool_with_a_datum_on_the_whisker_limit(gpu_lib):
+    """test_gpu_network.test_datum_on_the_whisker_limit's feeder as a pool of two equal scenarios: every value twice,
+    the same quartiles, the same limit -- the two largest loadings are the upper whisker, not fliers."""
+    from revs_admm_amd.study import study_report
+    from whisker_case import datum_on_the_upper_limit
+    par, er, cons, p, rating, hival = datum_on_the_upper_limit()
+    rep = study_report(par, er, cons, np.stack([p, p]), groups=[0, 0], rating=rating, bands=(), arrays=True)
+    assert (rep.loading[:, 8, 0] == hival).all() and rep.loading[:, :8, 0].max() < hival
+    g = rep.pooled_loading[0, 0]
+    print(f"upper limit {hival!r}: pooled whisker_hi {g['whisker_hi']!r}, fliers {g['n_fliers']}")
+    assert g["count"] == 18 and g["whisker_hi"] == hival
+    assert g["n_fliers"] == int((rep.loading[:, :, 0] < g["whisker_lo"]).sum())
+    sr.check_pooled(rep, rating, None)
+    for s in range(2):
+        check_summary(scenario(rep, s), rating, None, 9)
+
+
+@pytest.mark.parametrize("M", [1, 2, 1025])
+@pytest.mark.parametrize("case", ["all_equal", "first_digit"])
+def test_pool_ranks_share_or_part(gpu_lib, M, case):
+    """The pooled selection where the three ranks share a prefix through all eight digits (every value equal) and
+    where they part at the first (loadings 2^120 apart; voltages of 0, 2^-18 and 1/2): star feeders of 1, 2 and 1025
+    lines -- below, at and above one pass of the workgroup over a row -- three scenarios in pools of two and of one."""
+    from revs_admm_amd.study import study_report
+    rng = np.random.default_rng(40 + M)
+    par, cons = np.full(M, -1, np.int64), np.arange(M)
+    if case == "all_equal":
+        p = np.full((3, M, 2), 1.25)
+        er, rating = np.full(M, 2.0 ** -7), np.full(M, 2.0)      # (powers of two: every sum of the scans is exact)
+    else:
+        p = np.round(rng.uniform(0.5, 2.0, (3, M, 2)) * 1024.0) / 1024.0
+        rating = 2.0 ** (120.0 * rng.integers(-1, 2, M))
+        x = np.array([0.0, 2.0 ** -36, 0.25])[rng.integers(0, 3, M)]      # vset^2 - drop at scenario 0, slot 0
+        er = (1.0 - x) / (2.0 * p[0, :, 0])
+        p[1:] = p[0]                                 # (the same drops in every scenario)
+        p[:, :, 1] = p[:, :, 0]
+    rep = study_report(par, er, cons, p, groups=[0, 0, 1], rating=rating, bands=(), arrays=True)
+    sr.check_pooled(rep, rating, None)
+    check_pools_of_one(rep)
+    assert (rep.pooled_loading["count"] == np.array([[2 * M] * 2, [M] * 2])).all()
+    if case == "all_equal":
+        for rec, val in ((rep.pooled_loading, rep.loading), (rep.pooled_volt, rep.volt)):
+            for k in ("min", "q1", "median", "q3", "max", "whisker_lo", "whisker_hi"):
+                assert (rec[k] == val[0, 0, 0]).all(), k
+            assert (rec["n_fliers"] == 0).all()
+    elif M == 1025:
+        top = lambda a: a.view(np.uint64) >> np.uint64(56)
+        pl = rep.pooled_loading[0, 0]
+        assert top(pl["q1"]) < top(pl["median"]) < top(pl["q3"])             # (they did part at the first digit)
