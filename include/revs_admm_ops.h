@@ -11,7 +11,8 @@
  * and revs_net_across (per node and per line, the statistics across the scenarios of a group), then the bill and the
  * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at,
  * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence -- and
- * last revs_charge_report: what the chargers do, per EV and per slot.
+ * revs_charge_report: what the chargers do, per EV and per slot, and last revs_net_headroom: how much more charging
+ * every node could take in every slot, and what limits it.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -843,6 +844,59 @@ int revs_charge_report(int32_t S, int64_t n, int32_t T, const float *p, int64_t 
                        const revs_home_t *homes, const double *tariff, double on_frac, double short_tol,
                        revs_charge_row_t *row_rec, revs_charge_slot_t *slot_rec, revs_charge_day_t *day_rec,
                        int32_t *hist, double *val_out, uint8_t *keep_out, void *scratch, void *stream);
+
+/* ---- headroom report: spare charger power per node and slot (csrc/headroom_kernels.hip) -------------
+ * How much more constant power x node i could draw in slot t before something it affects reaches its limit: the nodal
+ * hosting capacity, in closed form on the tree.  Positions j = 0 .. tree->n - 1 are feeder_tree's preorder positions.
+ * Host-prepared per position (feeder.headroom_aux), DEVICE arrays in a HOST struct:
+ *   parent_pos int32[n]  position of j's parent, -1 when j hangs off the substation
+ *   wc double[n]         wc[j] = (parent_pos[j] >= 0 ? wc[parent_pos[j]] : 0.0) + w[j], one forward loop in preorder:
+ *                        wc[lca(i, j)] = R[i][j]
+ *   jump uint16[n_jump][n]  jump[r][j] = position of j's 2^(r + 1)-th ancestor, 0xFFFF: none; n_jump = the smallest count
+ *                        with 2^(n_jump + 1) > the forest's depth (roots at depth 0; 0 and a NULL jump for depth <= 1): the
+ *                        two passes below take n_jump + 1 rounds instead of one per level
+ * Per (scenario s, slot t), with drop and flow what revs_net_report's scans give at every position (the same bits):
+ *   slack of a limit node (limit_mask[j] != 0; NULL: every position with a row)   s[j] = drop_max - drop[j]
+ *   A[a] = min of s[j] over the limit nodes in a's subtree (+inf: none);  B[a] = rating[a] - flow[a] where rating[a] > 0
+ *   headroom x[i] = max(0, min over the ancestors-or-self a of i of { A[a] / wc[a] where wc[a] > 0, B[a] where rated }),
+ *                   +inf when no term exists; IEEE double operations, minima exact
+ *   limiter: the shallowest a that attains the minimum (before the clamp), its voltage term before its thermal one:
+ *            limiter_out = node_of_pos[a] | kind << 30, kind 0 voltage ("the subtree below a holds the node that reaches
+ *            the limit first") / 1 thermal ("the line above a"); -1: unlimited (or a limiter without a caller-side index)
+ * A slot whose node_g holds a non-finite value at a row of the tree: every headroom a NaN, every limiter -1, the summary
+ * count 0 and n_nan = the nodes summarised; drop_out / flow_out are what the scans give.  (Finite injections whose drops
+ * overflow are outside the contract.)
+ *   headroom_out double[S][n_out][T], limiter_out int32[S][n_out][T], drop_out / flow_out double[S][n_out][T]
+ *   summary_out revs_net_summary_t[S][T] over the positions with out_mask != 0 (NULL: all) and a caller-side index: the
+ *                box-plot record of the finite headrooms (a second launch, box_select64); +inf values are left out and
+ *                counted in reserved[0], NaNs in n_nan; n_violations = values < need; worst_value = the smallest headroom,
+ *                worst_index = the lowest caller-side index that attains it
+ *   day_out     revs_headroom_day_t[S][n_out]: over the slots that are no NaN, the smallest headroom, its earliest slot
+ *                and the number of slots with x < need; all NaN: min NaN, slot -1
+ * rating, node_of_pos, n_out: as revs_net_report's.  Any output may be NULL, not all.  Enqueues only (up to three
+ * launches on `stream`): capturable, no allocation, no synchronisation.  REVS_EINVAL before any launch: S outside
+ * 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; m outside 1..65535; a null node_g; a tree over REVS_TREE_MAX, not padded or
+ * NULL; n_out outside 1..tree->n; a null aux, parent_pos or wc; n_jump outside 0..REVS_HEADROOM_MAX_JUMP, a NULL jump with
+ * n_jump > 0; drop_max or need not finite, need < 0; every output NULL; summary_out or day_out without a 16-byte aligned
+ * scratch of revs_net_headroom_scratch bytes (8 S T tree_n: the headrooms by position; 0 for a bad size). */
+#define REVS_HEADROOM_MAX_JUMP 13
+typedef struct {
+    const int32_t *parent_pos;
+    const double *wc;
+    const uint16_t *jump;
+    int32_t n_jump;
+} revs_headroom_aux_t;
+typedef struct {
+    double min;                       /* the day's smallest headroom (NaN: every slot is one) */
+    int32_t slot;                     /* its earliest slot; -1 */
+    int32_t n_short;                  /* slots with x < need */
+} revs_headroom_day_t;                /* 16 bytes */
+int64_t revs_net_headroom_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_headroom(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const revs_headroom_aux_t *aux_host,
+                      const double *node_g, const double *rating, const uint8_t *limit_mask, const uint8_t *out_mask,
+                      const int32_t *node_of_pos, int32_t n_out, double drop_max, double need, double *headroom_out,
+                      int32_t *limiter_out, double *drop_out, double *flow_out, revs_net_summary_t *summary_out,
+                      revs_headroom_day_t *day_out, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
     load_profile   the demand curve of a schedule: load per slot by class of residence, peaks, load factor, diversity
     charging       what the chargers do: ChargingReport, charging_report / charging_report_device -- sessions, waits,
                    chargers on per slot, state of charge at departure and cost per EV
+    headroom       AdmmEngine.headroom_report: spare charger power per node and slot, and what limits it
     drawing        the reference's compute_flows / compute_voltage over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

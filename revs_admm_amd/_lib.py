@@ -100,6 +100,11 @@ class Tree(C.Structure):
     _fields_ = [("n", C.c_int32), ("pack", C.c_void_p), ("w", C.c_void_p)]
 
 
+class HeadroomAux(C.Structure):
+    """revs_headroom_aux_t"""
+    _fields_ = [("parent_pos", C.c_void_p), ("wc", C.c_void_p), ("jump", C.c_void_p), ("n_jump", C.c_int32)]
+
+
 class StreamState(C.Structure):
     """revs_stream_state_t"""
     _fields_ = [("p_est", C.c_void_p * 3), ("p_sch", C.c_void_p * 2), ("gamma", C.c_void_p * 2),
@@ -167,6 +172,11 @@ CHARGE_DAY_DTYPE = np.dtype([("peak_power", "<f8"), ("energy", "<f8"), ("coincid
                              ("n_under", "<i4"), ("n_never", "<i4"), ("n_interrupted", "<i4"), ("n_outside", "<i4")])
 assert CHARGE_DAY_DTYPE.itemsize == 64
 CHARGE_EV, CHARGE_UNDER, CHARGE_NONFINITE = 1, 2, 4      # bits of revs_charge_row_t.flags
+
+# numpy mirror of revs_headroom_day_t (include/revs_admm_ops.h)
+HEADROOM_DAY_DTYPE = np.dtype([("min", "<f8"), ("slot", "<i4"), ("n_short", "<i4")])
+assert HEADROOM_DAY_DTYPE.itemsize == 16
+HEADROOM_MAX_JUMP = 13   # REVS_HEADROOM_MAX_JUMP
 
 
 class RevsError(RuntimeError):
@@ -315,6 +325,9 @@ SIGNATURES = {
     "revs_charge_report_scratch": (_i64, [_i32, _i64, _i32]),
     "revs_charge_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _i64, _p, _p, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_op_dual_step_pending": (C.c_int, [_i32, _p, _p, _p, _p, _p, _f64, _f64, _p, _i32, _p, _p, _p]),
+    "revs_net_headroom_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_headroom": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _p, _p, _i32, _f64,
+                                    _f64, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
 DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 feeder; 80 / 128: 11.2 ms against 9.5, r05)

@@ -123,3 +123,18 @@ class EnsembleReportMixin:
         return [NetworkReport(pick(rep.flow, s), pick(rep.loading, s), pick(rep.volt, s), rep.summary_loading[s],
                               rep.summary_volt[s], rep.node_p[s], rep.vset, rep.vmin, rep.vmax)
                 for s in range(self.S_count)]
+
+    def headroom_reports(self, need=None, rating=None, limit_nodes=None, nodes=None, arrays=True, profile=None,
+                         add_load=False, out=None) -> list:
+        """AdmmEngine.headroom_report for every scenario -> S headroom.HeadroomReports from one node-sum launch and one
+        revs_net_headroom over all S (scenario s: the bits of the single engine's report on it).  need: None, the
+        largest charger rating among all scenarios' records.  profile / add_load: see node_sums -- the default reports
+        P_sch alone; out: a contiguous (S, tree nodes, T) float64 tensor on the device that receives the headrooms and
+        stays there (revs_net_across takes it as it is).  The run's state is read, never written."""
+        from . import headroom
+        tree, tree_host, n_nodes = self._report_tree()
+        if need is None:
+            need = headroom.default_need(self)
+        node_g = self.node_sums(profile, add_load)
+        return headroom.native_headroom_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, need,
+                                               rating, limit_nodes, nodes, self.vset, self.vlow, arrays, out)

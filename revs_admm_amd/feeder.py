@@ -95,6 +95,38 @@ def tree_report_host(tree, p, n_nodes=None):
     return out_f, out_d
 
 
+def headroom_aux(tree):
+    """Host-side preparation of revs_headroom_aux_t (include/revs_admm_ops.h) from the dict of feeder_tree, by preorder
+    position: dict(parent_pos int32[n], wc float64[n], jump uint16[n_jump][n], n_jump, depth int32[n]).
+
+    parent_pos[j]  position of j's parent, -1 when j hangs off the substation (read off `end`: the nearest earlier
+                   position whose subtree [a, end_a) holds j)
+    wc[j]          (wc[parent_pos[j]] if parent_pos[j] >= 0 else 0.0) + w[j], one forward loop in preorder, parents
+                   first, in exactly that order of additions: wc[lca(i, j)] = R[i][j]
+    jump[r][j]     position of j's 2^(r + 1)-th ancestor, 0xFFFF: none; n_jump: the smallest count with
+                   2^(n_jump + 1) > the forest's depth -- the headroom kernel's passes take n_jump + 1 rounds"""
+    n, end, w = int(tree["n"]), np.asarray(tree["end"], np.int64), np.asarray(tree["w"], np.float64)
+    parent = np.full(n, -1, np.int64)
+    depth = np.zeros(n, np.int32)
+    wc = np.zeros(n, np.float64)
+    stack = []
+    for j in range(n):
+        while stack and end[stack[-1]] <= j:
+            stack.pop()
+        if stack:
+            parent[j] = stack[-1]
+            depth[j] = depth[stack[-1]] + 1
+        wc[j] = (wc[parent[j]] if parent[j] >= 0 else 0.0) + w[j]
+        stack.append(j)
+    n_jump = max(int(depth.max(initial=0)).bit_length() - 1, 0)
+    jump = np.full((n_jump, n), 0xFFFF, np.uint16)
+    anc = parent.copy()                                    # the 2^r-th ancestors, r = 0
+    for r in range(n_jump):
+        anc = np.where(anc >= 0, anc[np.maximum(anc, 0)], -1)
+        jump[r] = np.where(anc >= 0, anc, 0xFFFF).astype(np.uint16)
+    return dict(parent_pos=parent.astype(np.int32), wc=wc, jump=jump, n_jump=n_jump, depth=depth)
+
+
 def tree_from_R(R, rtol=1e-12):
     """Recover a radial feeder from its LinDistFlow matrix alone (reference lpsolver.py:17-26, 184-189: callers
     of the solver hold R = 2 F D F^T restricted to the residence nodes, not the network).  For a radial feeder

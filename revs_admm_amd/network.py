@@ -135,6 +135,27 @@ def report_for_tree(parent, edge_r, cons_of, node_p, rating=None, nodes=None, vs
                           nodes, vset, vmin, vmax, arrays)
 
 
+def profile_node_sums(e, profile, who):
+    """The (M, T) float64 node sums of a home profile of engine e on the device, all-reduced over the ranks: what
+    network_report and headroom_report scan (profile: see network_report)."""
+    if profile is None:
+        load, prof = e.load, e.P_sch
+    else:
+        load = None
+        if isinstance(profile, torch.Tensor):
+            prof = profile
+        else:
+            prof = e._up(np.ascontiguousarray(np.asarray(profile, np.float32)[e.perm]))
+        if prof.dtype != torch.float32 or tuple(prof.shape) != (e.n, e.T) or not prof.is_contiguous():
+            raise ValueError(f"{who}: profile must be a contiguous float32 ({e.n}, {e.T}) array")
+    node_g = torch.zeros(e.M, e.T, dtype=torch.float64, device=e.dev)
+    if e.sweep_n:     # (node sums over node_ptr: load and profile read as n rows of T columns)
+        check(e.lib.revs_net_node_sums(e.M, e.T, ptr(e.node_ptr), ptr(load), ptr(prof), ptr(node_g), e.stream),
+              "revs_net_node_sums")
+    e._allreduce(node_g)
+    return node_g
+
+
 class NetworkMixin:
     def network_report(self, profile=None, rating=None, nodes=None, arrays=True) -> NetworkReport:
         """Line flows, line loading and node voltages of a home profile over the whole feeder, per slot, and their
@@ -156,20 +177,6 @@ class NetworkMixin:
             raise ValueError("network_report needs the feeder as a tree: pass feeder=(parent, edge_r, cons_of) to "
                              "AdmmEngine (without it the engine recovers one from Rn only for the Newton operator "
                              "up to 4096 rows, and only when Rn is a radial feeder's matrix)")
-        if profile is None:
-            load, prof = self.load, self.P_sch
-        else:
-            load = None
-            if isinstance(profile, torch.Tensor):
-                prof = profile
-            else:
-                prof = self._up(np.ascontiguousarray(np.asarray(profile, np.float32)[self.perm]))
-            if prof.dtype != torch.float32 or tuple(prof.shape) != (self.n, self.T) or not prof.is_contiguous():
-                raise ValueError(f"network_report: profile must be a contiguous float32 ({self.n}, {self.T}) array")
-        node_g = torch.zeros(self.M, self.T, dtype=torch.float64, device=self.dev)
-        if self.sweep_n:     # (node sums over node_ptr: load and profile read as n rows of T columns)
-            check(self.lib.revs_net_node_sums(self.M, self.T, ptr(self.node_ptr), ptr(load), ptr(prof), ptr(node_g),
-                                              self.stream), "revs_net_node_sums")
-        self._allreduce(node_g)
+        node_g = profile_node_sums(self, profile, "network_report")
         return run_report(self.lib, self.dev, self.stream, self._tree, self._tree_host, self._tree_nodes, node_g,
                           rating, nodes, self.vset, self.vlow, self.vhigh, arrays)

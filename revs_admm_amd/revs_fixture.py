@@ -124,7 +124,7 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, bills=False, convergence=None, load_profile=False, charging=False, **opt):
+              across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -176,7 +176,11 @@ class REVS:
         records), pooled by the report's groups, costs under `tariff`; an ensemble's scenarios are read from the
         ensembles' own S on the device, the other methods' power is uploaded once as float32 (opt charging_on_frac,
         charging_short_tol: the report's thresholds, 0.0 and 1e-6 by default; the row records are read back with opt
-        arrays)."""
+        arrays).  headroom=need (kW): StudyReport.headroom, every scenario's headroom.HeadroomReport -- per node and
+        slot the extra constant power that still fits under opt vmin and the line ratings, and what limits it -- over
+        the nodes that carry residences, summarised over `community`, n_short against `need`; one launch for all
+        scenarios, on the device_report path from the buffer on the device (its arrays are read back with opt
+        arrays).  None: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -298,6 +302,12 @@ class REVS:
                                           groups=[order.index(c) for c in combos],
                                           on_frac=opt.get("charging_on_frac", 0.0),
                                           short_tol=opt.get("charging_short_tol", 1e-6), rows=bool(opt.get("arrays", False)))
+
+        def headroom_reports(node_g):
+            from .headroom import headroom_report_device
+            return headroom_report_device(node_g, feeder=(parent, edge_r, cons_of), need=float(headroom), rating=node_rating,
+                                          nodes=[pos[h] for h in community], vset=opt.get("report_vset", 1.0),
+                                          vmin=opt.get("vmin", 0.95), arrays=opt.get("arrays", False))
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -320,6 +330,8 @@ class REVS:
                 rep.load_profile_rows = prof_rows
             if charging:
                 rep.charging = charging_report()
+            if headroom is not None:
+                rep.headroom = headroom_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -336,6 +348,9 @@ class REVS:
             rep.load_profile_rows = prof_rows
         if charging:
             rep.charging = charging_report()
+        if headroom is not None:
+            import torch
+            rep.headroom = headroom_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -103,6 +103,7 @@ class StudyReport:
     load_profile: object | None = None
     load_profile_rows: list | None = None
     charging: object | None = None
+    headroom: list | None = None
 
     @property
     def n_groups(self):
