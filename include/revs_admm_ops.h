@@ -11,8 +11,9 @@
  * and revs_net_across (per node and per line, the statistics across the scenarios of a group), then the bill and the
  * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at,
  * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence -- and
- * revs_charge_report: what the chargers do, per EV and per slot, and last revs_net_headroom: how much more charging
- * every node could take in every slot, and what limits it.
+ * revs_charge_report: what the chargers do, per EV and per slot, revs_net_headroom: how much more charging
+ * every node could take in every slot, and what limits it, and last revs_net_losses: what the feeder loses carrying a
+ * schedule, per line, per node at the margin, per slot and per day.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -897,6 +898,88 @@ int revs_net_headroom(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_h
                       const int32_t *node_of_pos, int32_t n_out, double drop_max, double need, double *headroom_out,
                       int32_t *limiter_out, double *drop_out, double *flow_out, revs_net_summary_t *summary_out,
                       revs_headroom_day_t *day_out, void *scratch, void *stream);
+
+/* ---- loss report: line losses, marginal loss per node, energy and cost (csrc/losses_kernels.hip) ------
+ * What the feeder loses carrying a schedule: a closed form on top of the network report's scans.  Positions j = 0 ..
+ * tree->n - 1 are feeder_tree's preorder positions.  Per (scenario s, slot t), every operation an IEEE double operation
+ * rounded on its own (no fused multiply-add), with flow[j] and drop[j] what revs_net_report's scans give at every position
+ * (the same bits), inj[j] the gathered node sum (+0.0 at a position without a row), w[j] = tree->w[j] = 2 r[j], and
+ * vset2 = vset vset formed by the caller:
+ *   den[j]  = vset2 - drop[j]
+ *   loss[j] = ((0.5 w[j]) flow[j]) flow[j] / den[j]    power lost on the line above j (the receiving-end form of the
+ *                                                      branch-flow loss r P^2 / v); a zero-resistance line loses 0
+ *   c[j]    = (w[j] flow[j]) / den[j]
+ *   mlf[i]  = sum of c[a] over the ancestors-or-self a of i: the extra loss per extra unit drawn at i with den held fixed
+ *             (dimensionless), computed in the drop scan's form -- the prefix of c in preorder minus the prefix of c in
+ *             end-order below cle -- so its bits depend on the launch shape; it is within 2 n 2^-53 sum |c| of any order
+ * Bad slot: a row's injection is not finite, or den[j] > 0 fails at a position with a caller-side index (the collapse
+ * that revs_net_report shows as a NaN voltage).  Then every loss, every mlf and every double of the slot record is a NaN
+ * (all four class_total included), mlf_max_index -1, n_bad 1, the summary has count 0 and n_nan = the lines summarised;
+ * drop_out / flow_out are what the scans give.  One flag for the workgroup; nothing traps.
+ * Sums over positions (total, delivered, class_total[k]): each is the root of ONE fixed binary tree -- the values laid out
+ * by position, +0.0 where the position is padding, masked out or not of class k, the array padded with +0.0 to the next
+ * power of two, then level by level x[i] = x[2i] + x[2i + 1] -- so the bits depend neither on the launch shape nor on
+ * the order of the scans.
+ *   total          sum of loss over the lines with line_mask[j] != 0 (NULL: all) and a caller-side index
+ *   delivered      sum of inj
+ *   class_total[k] sum of loss over the positions with line_class[j] == k (uint8 per position), k < C <= 4; NULL: C = 0
+ * Outputs, any may be NULL, not all:
+ *   loss_out, mlf_out, drop_out, flow_out   double[S][n_out][T] in the caller's node order (node_of_pos, n_out as
+ *                  revs_net_report's)
+ *   summary_out    revs_net_summary_t[S][T]: the box-plot record of the losses of the lines with line_mask and a
+ *                  caller-side index (a second launch, box_select64 and the rules of boxplot.h); NaNs are left out and
+ *                  counted in n_nan; worst_value = the largest loss, worst_index = the lowest caller-side index that
+ *                  attains it; n_violations = lines with loss > loss_max (kW; +inf allowed)
+ *   slot_out       revs_loss_slot_t[S][T]: total, delivered, class_total (entries k >= C are 0), mlf_max = the largest
+ *                  mlf over the positions with node_mask[j] != 0 (NULL: all) and a caller-side index, mlf_max_index the
+ *                  lowest index that attains it (-1 and a NaN mlf_max when there is none), n_bad
+ *   line_day_out   revs_loss_line_day_t[S][n_out]: energy = the line's losses summed from +0.0 in ascending slot order,
+ *                  then multiplied once by slot_hours; peak / peak_slot = the largest loss and its earliest slot; a bad
+ *                  slot makes energy and peak NaN and peak_slot -1
+ *   day_out        revs_loss_day_t[S]: energy, delivered, class_energy[4] by the same rule over the slot totals; cost =
+ *                  the sum from +0.0 in slot order of the rounded products total[t] cost[t], multiplied once by
+ *                  slot_hours (cost: DEVICE double[T]; NULL: a NaN); peak / peak_slot = the largest slot total and its
+ *                  earliest slot (NaN / -1 with a bad slot); n_bad_slots; top_index[8] / top_energy[8] = the eight
+ *                  summarised lines (line_mask, caller-side index) of largest day energy in descending order, NaNs left
+ *                  out, ties to the lowest caller index, unused entries -1 / NaN
+ * Enqueues only (up to four launches on `stream`): capturable, no allocation, no synchronisation.  REVS_EINVAL before any
+ * launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; m outside 1..65535; a null node_g; a tree over
+ * REVS_TREE_MAX, not padded or NULL; n_out outside 1..tree->n; vset2 or slot_hours not finite and > 0; loss_max not > 0
+ * (+inf allowed, a NaN refused); C outside 0..4; line_class NULL with C > 0; every output NULL; summary_out, line_day_out
+ * or day_out without a 16-byte aligned scratch of revs_net_losses_scratch bytes (8 S T tree_n: the losses by position,
+ * + 64 S T: the slot records, + 8 S tree_n: the lines' day energies; 0 for a bad size). */
+typedef struct {
+    double total;                     /* kW lost on the summarised lines */
+    double delivered;                 /* sum of the injections */
+    double class_total[4];            /* kW lost per class of line; entries >= C are 0 */
+    double mlf_max;                   /* the largest marginal loss factor over the masked nodes */
+    int32_t mlf_max_index;            /* the lowest caller-side index that attains it; -1 */
+    int32_t n_bad;                    /* 1: a bad slot, every double above a NaN */
+} revs_loss_slot_t;                   /* 64 bytes */
+typedef struct {
+    double energy;                    /* (sum over the slots of loss) slot_hours */
+    double peak;                      /* the largest loss of the day */
+    int32_t peak_slot;                /* its earliest slot; -1 with a bad slot */
+    int32_t reserved;
+} revs_loss_line_day_t;               /* 24 bytes */
+typedef struct {
+    double energy, delivered;         /* (sum over the slots of total / delivered) slot_hours */
+    double class_energy[4];
+    double cost;                      /* (sum over the slots of total[t] cost[t]) slot_hours; NaN without cost */
+    double peak;                      /* the largest slot total */
+    double top_energy[8];             /* day energies of the lines top_index, descending; NaN: unused */
+    int32_t top_index[8];             /* caller-side indices; -1: unused */
+    int32_t peak_slot;
+    int32_t n_bad_slots;
+    int32_t reserved[6];
+} revs_loss_day_t;                    /* 192 bytes */
+int64_t revs_net_losses_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const double *node_g,
+                    const uint8_t *line_mask, const uint8_t *node_mask, const uint8_t *line_class, int32_t C,
+                    const int32_t *node_of_pos, int32_t n_out, double vset2, double slot_hours, double loss_max,
+                    const double *cost, double *loss_out, double *mlf_out, double *drop_out, double *flow_out,
+                    revs_net_summary_t *summary_out, revs_loss_slot_t *slot_out, revs_loss_line_day_t *line_day_out,
+                    revs_loss_day_t *day_out, void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

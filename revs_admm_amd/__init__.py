@@ -9,7 +9,8 @@
     charging       what the chargers do: ChargingReport, charging_report / charging_report_device -- sessions, waits,
                    chargers on per slot, state of charge at departure and cost per EV
     headroom       AdmmEngine.headroom_report: spare charger power per node and slot, and what limits it
-    drawing        the reference's compute_flows / compute_voltage over it (no figures)
+    losses         AdmmEngine.loss_report: line losses, marginal loss per node, the day's lost energy and its cost
+    drawing        the reference's compute_flows / compute_voltage / compute_losses over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)
 

@@ -178,6 +178,18 @@ HEADROOM_DAY_DTYPE = np.dtype([("min", "<f8"), ("slot", "<i4"), ("n_short", "<i4
 assert HEADROOM_DAY_DTYPE.itemsize == 16
 HEADROOM_MAX_JUMP = 13   # REVS_HEADROOM_MAX_JUMP
 
+# numpy mirrors of revs_loss_slot_t, revs_loss_line_day_t, revs_loss_day_t (include/revs_admm_ops.h)
+LOSS_SLOT_DTYPE = np.dtype([("total", "<f8"), ("delivered", "<f8"), ("class_total", "<f8", (4,)), ("mlf_max", "<f8"),
+                            ("mlf_max_index", "<i4"), ("n_bad", "<i4")])
+assert LOSS_SLOT_DTYPE.itemsize == 64
+LOSS_LINE_DAY_DTYPE = np.dtype([("energy", "<f8"), ("peak", "<f8"), ("peak_slot", "<i4"), ("reserved", "<i4")])
+assert LOSS_LINE_DAY_DTYPE.itemsize == 24
+LOSS_DAY_DTYPE = np.dtype([("energy", "<f8"), ("delivered", "<f8"), ("class_energy", "<f8", (4,)), ("cost", "<f8"),
+                           ("peak", "<f8"), ("top_energy", "<f8", (8,)), ("top_index", "<i4", (8,)), ("peak_slot", "<i4"),
+                           ("n_bad_slots", "<i4"), ("reserved", "<i4", (6,))])
+assert LOSS_DAY_DTYPE.itemsize == 192
+LOSS_MAX_CLASSES = 4
+
 
 class RevsError(RuntimeError):
     pass
@@ -328,6 +340,9 @@ SIGNATURES = {
     "revs_net_headroom_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_headroom": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _p, _p, _i32, _f64,
                                     _f64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_losses_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_losses": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _p, _i32, _f64, _f64, _f64, _p,
+                                  _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
 DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 feeder; 80 / 128: 11.2 ms against 9.5, r05)

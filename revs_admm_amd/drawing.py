@@ -1,9 +1,10 @@
 """The two power-flow functions of the reference's drawing.py (lines 29-78) over the GPU network report:
 
-    from revs_admm_amd.drawing import compute_flows, compute_voltage
+    from revs_admm_amd.drawing import compute_flows, compute_voltage, compute_losses
 
 Same arguments and the same dicts back -- {edge: loading per slot} over graph.edges, {node: voltage per slot} over
-the non-substation nodes -- so the code that feeds the reference's box plots runs unchanged.  The figures
+the non-substation nodes -- so the code that feeds the reference's box plots runs unchanged.  compute_losses is the
+third of the kind, over the loss report: {edge: kW lost per slot}.  The figures
 themselves (matplotlib, seaborn, geopandas) are outside the project.
 
 Line ratings are the caller's data: an edge attribute `rating` (kVA) on the graph, or `rating=` as a mapping from
@@ -16,7 +17,7 @@ import numpy as np
 from .lpsolver import feeder_arrays
 from .network import report_for_tree
 
-__all__ = ["compute_flows", "compute_voltage"]
+__all__ = ["compute_flows", "compute_voltage", "compute_losses"]
 
 
 def _edge_ratings(graph, rating):
@@ -71,3 +72,18 @@ def compute_voltage(graph, p_sch, vset=1.0, device="cuda:0"):
     parent, edge_r, cons_of = feeder_arrays(graph, res)
     rep = report_for_tree(parent, edge_r, cons_of, P, vset=vset, device=device)
     return {n: rep.volt[i].tolist() for i, n in enumerate(nonsub)}
+
+
+def compute_losses(graph, p_sch, vset=1.0, device="cuda:0"):
+    """Next to compute_flows / compute_voltage: {edge: [kW lost on the line per slot]} in graph.edges order, the
+    loss report's r P^2 / v at the line's receiving end (losses.report_for_tree)."""
+    from .losses import report_for_tree as loss_report
+    res, nonsub, P = _node_profile(graph, p_sch)
+    parent, edge_r, cons_of = feeder_arrays(graph, res)
+    pos = {n: i for i, n in enumerate(nonsub)}
+    rep = loss_report(parent, edge_r, cons_of, P, vset=vset, device=device)
+    out = {}
+    for u, v in graph.edges:                      # (the tree node below the edge, as line_nodes finds it)
+        down = pos.get(v, -1) >= 0 and parent[pos[v]] == pos.get(u, -1)
+        out[(u, v)] = rep.loss[pos[v] if down else pos[u]].tolist()
+    return out

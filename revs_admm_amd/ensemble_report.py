@@ -138,3 +138,18 @@ class EnsembleReportMixin:
         node_g = self.node_sums(profile, add_load)
         return headroom.native_headroom_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, need,
                                                rating, limit_nodes, nodes, self.vset, self.vlow, arrays, out)
+
+    def loss_reports(self, lines=None, nodes=None, classes=None, cost=None, slot_hours=None, loss_max=float("inf"),
+                     arrays=True, profile=None, add_load=False, out=None) -> list:
+        """AdmmEngine.loss_report for every scenario -> S losses.LossReports from one node-sum launch and one
+        revs_net_losses over all S (scenario s: the bits of the single engine's report on it).  cost: None, the
+        ensemble's own tariff.  profile / add_load: see node_sums -- the default reports P_sch alone; out: a contiguous
+        (S, tree nodes, T) float64 tensor on the device that receives the losses and stays there (revs_net_across takes
+        it as it is).  The run's state is read, never written."""
+        from . import losses
+        tree, tree_host, n_nodes = self._report_tree()
+        if cost is None:
+            cost = self.cost.to(torch.float64)
+        node_g = self.node_sums(profile, add_load)
+        return losses.native_losses_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, lines, nodes,
+                                           classes, cost, slot_hours, loss_max, self.vset, arrays, out)

@@ -124,7 +124,8 @@ class REVS:
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
-              across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, **opt):
+              across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
+              **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -180,7 +181,11 @@ class REVS:
         slot the extra constant power that still fits under opt vmin and the line ratings, and what limits it -- over
         the nodes that carry residences, summarised over `community`, n_short against `need`; one launch for all
         scenarios, on the device_report path from the buffer on the device (its arrays are read back with opt
-        arrays).  None: nothing of it runs."""
+        arrays).  None: nothing of it runs.  losses=True or a dict of loss_report_device's options (lines, nodes,
+        classes, slot_hours, loss_max, cost): StudyReport.losses, every scenario's losses.LossReport -- per line and
+        slot the power lost, per node the marginal loss factor, the day's lost energy and its cost under `tariff` --
+        summarised over every line unless lines= says otherwise; one launch for all scenarios on either path (its
+        arrays are read back with opt arrays).  False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -308,6 +313,13 @@ class REVS:
             return headroom_report_device(node_g, feeder=(parent, edge_r, cons_of), need=float(headroom), rating=node_rating,
                                           nodes=[pos[h] for h in community], vset=opt.get("report_vset", 1.0),
                                           vmin=opt.get("vmin", 0.95), arrays=opt.get("arrays", False))
+
+        def loss_reports(node_g):
+            from .losses import loss_report_device
+            kw = dict(cost=np.asarray(tariff, np.float64))
+            kw.update(losses if isinstance(losses, dict) else {})
+            return loss_report_device(node_g, feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
+                                      arrays=opt.get("arrays", False), **kw)
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -332,6 +344,8 @@ class REVS:
                 rep.charging = charging_report()
             if headroom is not None:
                 rep.headroom = headroom_reports(buf)
+            if losses is True or isinstance(losses, dict):
+                rep.losses = loss_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -351,6 +365,9 @@ class REVS:
         if headroom is not None:
             import torch
             rep.headroom = headroom_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if losses is True or isinstance(losses, dict):
+            import torch
+            rep.losses = loss_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

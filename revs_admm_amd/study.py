@@ -104,6 +104,7 @@ class StudyReport:
     load_profile_rows: list | None = None
     charging: object | None = None
     headroom: list | None = None
+    losses: list | None = None
 
     @property
     def n_groups(self):
