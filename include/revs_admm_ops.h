@@ -12,8 +12,9 @@
  * convergence report, revs_rule_schedule: the schedules nobody optimised, for the reports to be pointed at,
  * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence -- and
  * revs_charge_report: what the chargers do, per EV and per slot, revs_net_headroom: how much more charging
- * every node could take in every slot, and what limits it, and last revs_net_losses: what the feeder loses carrying a
- * schedule, per line, per node at the margin, per slot and per day.
+ * every node could take in every slot, and what limits it, revs_net_losses: what the feeder loses carrying a
+ * schedule, per line, per node at the margin, per slot and per day, and last revs_xf_report: what a schedule does to the
+ * service transformers -- load ratio, top-oil and hot-spot temperature per slot, loss of insulation life per day.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -980,6 +981,98 @@ int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_hos
                     const double *cost, double *loss_out, double *mlf_out, double *drop_out, double *flow_out,
                     revs_net_summary_t *summary_out, revs_loss_slot_t *slot_out, revs_loss_line_day_t *line_day_out,
                     revs_loss_day_t *day_out, void *scratch, void *stream);
+
+/* ---- transformer report: loading, hot-spot and loss of life of the service transformers (csrc/transformer_kernels.hip,
+ * DESIGN.md 3.17) --------------------------------------------------------------------------------------------------------
+ * K transformers, each serving a list of rows of the node sums node_g (double[S][m][T], revs_net_node_sums' layout):
+ * xf_ptr int32[K + 1] and xf_rows int32[nnz] in CSR form, rows ascending within a transformer, a row in at most one list
+ * (rows in no list are ignored); rated_kw double[K] = rated kVA x power factor; ambient double[T] in deg C -- all DEVICE
+ * arrays.  It needs no feeder tree.  One thermal model per call (IEEE C57.91 Clause 7: top-oil and winding rises that
+ * follow their ultimate values exponentially, Arrhenius ageing), every value a parameter.  Per (scenario, transformer k,
+ * slot t), every operation that is no pow / exp one IEEE double operation rounded on its own (no fused multiply-add):
+ *   load  = g[row][t] summed from +0.0 over k's rows in list order
+ *   ratio = |load| / rated_kw[k]
+ *   u_to  = dto_r pow((ratio ratio loss_ratio + 1) / (loss_ratio + 1), n)         the ultimate top-oil rise
+ *   u_w   = dhs_r pow(ratio ratio, m)                                             the ultimate winding rise over top oil
+ *   `substeps` sub-steps of slot_hours / substeps each:
+ *       x = u_to + (x - u_to) decay_to;  y = u_w + (y - u_w) decay_w;  hot = (ambient[t] + x) + y;
+ *       acc += exp(aging_B / (theta_ref + 273) - aging_B / (hot + 273))           (acc from +0.0)
+ *   top_oil[t] = x, hot_spot[t] = hot of the last sub-step, faa[t] = acc / substeps
+ * decay_to = exp(-slot_hours / (substeps tau_to)) and decay_w likewise are formed by the caller (decay_w = 0: the winding
+ * follows at once).  cyclic = 0: x = to0, y = w0 before slot 0.  cyclic = 1 (the day repeats): the T substeps sub-steps
+ * run once from x = y = 0 while aN = the product of the decay_to (awN: of the decay_w) is multiplied up from 1.0; the
+ * real pass starts from x_end / (1 - aN), y_end / (1 - awN).  The state is sampled at the end of each sub-step.
+ * A transformer is BAD in a scenario when a row of its list is not finite in some slot, its rated_kw is not finite and
+ * > 0, or a listed row lies outside 0..m-1 (such a row is never read and adds nothing to load): load and ratio keep their
+ * per-slot values, top_oil / hot_spot / faa and every double of its day record are NaN, its counts 0 and its slots -1.
+ * A transformer without rows has load 0 and is valid.  xf_ptr entries are clamped to 0..nnz.
+ *   load_out, ratio_out, top_oil_out, hot_out, faa_out   double[S][K][T]
+ *   xf_day_out     revs_xf_day_t[S][K]: peak_ratio / peak_hot and their earliest slots; energy_kwh = the |load| summed
+ *                  from +0.0 in slot order, times slot_hours once; age_hours = the faa summed likewise, times slot_hours;
+ *                  lol_percent = 100 age_hours / normal_life_hours; feqa = age_hours / (T slot_hours); n_over_slots =
+ *                  slots with ratio > over_ratio, n_hot_slots = slots with hot_spot > hot_limit
+ *   sum_ratio_out, sum_hot_out   revs_net_summary_t[S][T]: the box-plot record over the K transformers of the ratios
+ *                  (n_violations: ratio > over_ratio) and of the hot-spots (n_violations: hot > hot_limit), NaNs counted
+ *                  in n_nan and left out; worst_value the largest value, worst_index the lowest transformer that has it
+ *   fleet_out      revs_xf_fleet_t[S]: n_xf = K; n_nan = transformers whose lol_percent is a NaN; n_overloaded / n_hot /
+ *                  n_aging = transformers with n_over_slots > 0 / n_hot_slots > 0 / feqa > 1; lol_sum, energy_kwh and the
+ *                  sum behind feqa_mean = (sum of age_hours) / ((K T) slot_hours) are each the root of one binary tree
+ *                  over the day records' values by transformer index, padded with +0.0 to a power of two (the values are
+ *                  >= +0.0 or NaN, so a padding zero changes no bit; a NaN record makes them NaN); lol_max = top_lol[0];
+ *                  top_index[8] / top_lol[8] = the eight transformers of largest lol_percent in descending order, NaNs
+ *                  left out, ties to the lowest index, unused entries -1 / NaN
+ * Every output may be NULL.  Enqueues only (up to four launches on `stream`): capturable, no allocation, no
+ * synchronisation.  REVS_EINVAL before any launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; m or K outside
+ * 1..65535; nnz outside 0..m; a null node_g, xf_ptr, rated_kw, ambient or model, a null xf_rows with nnz > 0; a model
+ * value that is not finite, dto_r, dhs_r, loss_ratio, n, m, aging_B or normal_life_hours not > 0, theta_ref not > -273;
+ * substeps outside 1..16; a decay outside [0, 1); slot_hours not finite and > 0; cyclic not 0 or 1; to0 or w0 not finite
+ * with cyclic = 0; over_ratio or hot_limit a NaN; every output NULL; sum_ratio_out, sum_hot_out or fleet_out without a
+ * 16-byte aligned scratch of revs_xf_report_scratch bytes (16 S T K: the ratios and hot-spots by slot, + 64 S K: the day
+ * records; 0 for a bad size). */
+typedef struct {
+    double dto_r;                     /* top-oil rise over ambient at rated load, K (55) */
+    double dhs_r;                     /* winding hot-spot rise over top oil at rated load, K (25) */
+    double loss_ratio;                /* load loss / no-load loss at rated load (5) */
+    double n;                         /* top-oil exponent (0.8) */
+    double m;                         /* winding exponent (0.8) */
+    double aging_B;                   /* Arrhenius constant, K (15000) */
+    double theta_ref;                 /* hot-spot at which the ageing factor is 1, deg C (110) */
+    double normal_life_hours;         /* insulation life at theta_ref, h (180000) */
+} revs_xf_model_t;                    /* 64 bytes */
+typedef struct {
+    double peak_ratio;                /* the largest load ratio of the day */
+    double peak_hot;                  /* the largest hot-spot, deg C */
+    double energy_kwh;                /* (sum over the slots of |load|) slot_hours */
+    double age_hours;                 /* (sum over the slots of faa) slot_hours: insulation life used */
+    double lol_percent;               /* 100 age_hours / normal_life_hours */
+    double feqa;                      /* age_hours / (T slot_hours): the equivalent ageing factor */
+    int32_t peak_ratio_slot;          /* the earliest slot of peak_ratio; -1: a bad transformer */
+    int32_t peak_hot_slot;
+    int32_t n_over_slots;             /* slots with ratio > over_ratio */
+    int32_t n_hot_slots;              /* slots with hot_spot > hot_limit */
+} revs_xf_day_t;                      /* 64 bytes */
+typedef struct {
+    double lol_sum;                   /* sum of lol_percent over the transformers */
+    double lol_max;                   /* the largest lol_percent (NaN: none) */
+    double energy_kwh;                /* sum of energy_kwh */
+    double feqa_mean;                 /* (sum of age_hours) / ((n_xf T) slot_hours) */
+    double top_lol[8];                /* lol_percent of the transformers top_index, descending; NaN: unused */
+    int32_t top_index[8];             /* -1: unused */
+    int32_t n_xf;
+    int32_t n_nan;                    /* bad transformers: their day records are NaN */
+    int32_t n_overloaded;             /* transformers with n_over_slots > 0 */
+    int32_t n_hot;                    /* transformers with n_hot_slots > 0 */
+    int32_t n_aging;                  /* transformers with feqa > 1 */
+    int32_t reserved[3];
+} revs_xf_fleet_t;                    /* 160 bytes */
+int64_t revs_xf_report_scratch(int32_t S, int32_t T, int32_t K);
+int revs_xf_report(int32_t S, int32_t m, int32_t T, int32_t K, int32_t nnz, const double *node_g, const int32_t *xf_ptr,
+                   const int32_t *xf_rows, const double *rated_kw, const double *ambient, const revs_xf_model_t *model,
+                   double slot_hours, int32_t substeps, double decay_to, double decay_w, int32_t cyclic, double to0,
+                   double w0, double over_ratio, double hot_limit, double *load_out, double *ratio_out,
+                   double *top_oil_out, double *hot_out, double *faa_out, revs_net_summary_t *sum_ratio_out,
+                   revs_net_summary_t *sum_hot_out, revs_xf_day_t *xf_day_out, revs_xf_fleet_t *fleet_out, void *scratch,
+                   void *stream);
 
 #ifdef __cplusplus
 }

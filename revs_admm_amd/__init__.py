@@ -10,6 +10,7 @@
                    chargers on per slot, state of charge at departure and cost per EV
     headroom       AdmmEngine.headroom_report: spare charger power per node and slot, and what limits it
     losses         AdmmEngine.loss_report: line losses, marginal loss per node, the day's lost energy and its cost
+    transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
     drawing        the reference's compute_flows / compute_voltage / compute_losses over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

@@ -100,6 +100,12 @@ class Tree(C.Structure):
     _fields_ = [("n", C.c_int32), ("pack", C.c_void_p), ("w", C.c_void_p)]
 
 
+class XfModel(C.Structure):
+    """revs_xf_model_t"""
+    _fields_ = [("dto_r", C.c_double), ("dhs_r", C.c_double), ("loss_ratio", C.c_double), ("n", C.c_double),
+                ("m", C.c_double), ("aging_B", C.c_double), ("theta_ref", C.c_double), ("normal_life_hours", C.c_double)]
+
+
 class HeadroomAux(C.Structure):
     """revs_headroom_aux_t"""
     _fields_ = [("parent_pos", C.c_void_p), ("wc", C.c_void_p), ("jump", C.c_void_p), ("n_jump", C.c_int32)]
@@ -189,6 +195,17 @@ LOSS_DAY_DTYPE = np.dtype([("energy", "<f8"), ("delivered", "<f8"), ("class_ener
                            ("n_bad_slots", "<i4"), ("reserved", "<i4", (6,))])
 assert LOSS_DAY_DTYPE.itemsize == 192
 LOSS_MAX_CLASSES = 4
+
+# numpy mirrors of revs_xf_day_t and revs_xf_fleet_t (include/revs_admm_ops.h)
+XF_DAY_DTYPE = np.dtype([("peak_ratio", "<f8"), ("peak_hot", "<f8"), ("energy_kwh", "<f8"), ("age_hours", "<f8"),
+                         ("lol_percent", "<f8"), ("feqa", "<f8"), ("peak_ratio_slot", "<i4"), ("peak_hot_slot", "<i4"),
+                         ("n_over_slots", "<i4"), ("n_hot_slots", "<i4")])
+assert XF_DAY_DTYPE.itemsize == 64
+XF_FLEET_DTYPE = np.dtype([("lol_sum", "<f8"), ("lol_max", "<f8"), ("energy_kwh", "<f8"), ("feqa_mean", "<f8"),
+                           ("top_lol", "<f8", (8,)), ("top_index", "<i4", (8,)), ("n_xf", "<i4"), ("n_nan", "<i4"),
+                           ("n_overloaded", "<i4"), ("n_hot", "<i4"), ("n_aging", "<i4"), ("reserved", "<i4", (3,))])
+assert XF_FLEET_DTYPE.itemsize == 160
+XF_MAX_SUBSTEPS = 16
 
 
 class RevsError(RuntimeError):
@@ -343,6 +360,9 @@ SIGNATURES = {
     "revs_net_losses_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_losses": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _p, _i32, _f64, _f64, _f64, _p,
                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
+                                 _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
 DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 feeder; 80 / 128: 11.2 ms against 9.5, r05)

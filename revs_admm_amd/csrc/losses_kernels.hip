@@ -27,6 +27,7 @@
 // [S][n] that the later launches read.
 #include "common.h"
 #include "boxplot.h"
+#include "fixed_tree.h"       // pair_tree, arg_better, wave_argmax
 #include "tree_body.h"
 
 #include <math.h>
@@ -59,20 +60,6 @@ template <int NT, int IPT>
 constexpr size_t loss_lds_doubles() { return (2 + (size_t)NT * IPT + 2 * (NT / 64) + 1) / 2 * 2; }
 inline size_t loss_lds_bytes(int n) { return (tree_lds_doubles_even(n) + kLossRedDoubles) * sizeof(double); }
 
-// the root of the fixed binary tree over N consecutive values: x[i] = x[2i] + x[2i + 1], level by level
-template <int N>
-__device__ __forceinline__ double loss_pair_tree(const double (&x)[N]) {
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) y[i] = x[i];
-#pragma unroll
-    for (int w = N; w > 1; w >>= 1) {
-#pragma unroll
-        for (int i = 0; i < w / 2; ++i) y[i] = y[2 * i] + y[2 * i + 1];
-    }
-    return y[0];
-}
-
 // head_flow_scan (headroom_kernels.hip: net_flow_scan with the finiteness test) with one addition: inj_root = the
 // pair-tree sum of the thread's gathered injections.
 template <int NT, int IPT>
@@ -89,7 +76,7 @@ __device__ __forceinline__ void loss_flow_scan(const LossArgs &A, int t, double 
         a[i] = ok ? v : 0.0;
         bad |= !(a[i] - a[i] == 0.0);
     }
-    inj_root = loss_pair_tree<IPT>(a);
+    inj_root = pair_tree<IPT>(a);
 #pragma unroll
     for (int i = 1; i < IPT; ++i) a[i] += a[i - 1];
     const double cex = block_excl_offset<NT>(a[IPT - 1], red0);
@@ -188,19 +175,6 @@ __device__ __forceinline__ void loss_path_scan(const TreeArgs &tr, bool act, int
 
 // Everything below rounds each operation on its own (the contract's IEEE operations): no product is fused into a sum.
 #pragma clang fp contract(off)
-
-// (value, index) pairs ordered for the arg-max: the larger value, then the lower index; index -1: no candidate
-__device__ __forceinline__ void loss_better(double &bv, int &bi, double ov, int oi) {
-    if (oi >= 0 && (bi < 0 || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
-}
-__device__ __forceinline__ void loss_wave_argmax(double &bv, int &bi) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double ov = __shfl_xor(bv, o);
-        const int oi = __shfl_xor(bi, o);
-        loss_better(bv, bi, ov, oi);
-    }
-}
 
 template <int NT, int IPT>
 __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
@@ -340,7 +314,7 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
         for (int i = 0; i < kLossChunk; ++i) {
             const double v = badslot ? nan : a[c + i];
             if (A.mlf && nd[i] >= 0) A.mlf[(int64_t)nd[i] * T + t] = v;
-            if (((nm >> (8 * i)) & 0xFFull) != 0ull && v == v) loss_better(bv, bi, v, nd[i]);
+            if (((nm >> (8 * i)) & 0xFFull) != 0ull && v == v) arg_better(bv, bi, v, nd[i]);
         }
         LOSS_FENCE();
     }
@@ -354,7 +328,7 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
             for (int q = 0; q < kLossSums; ++q) root[q] += __shfl_xor(root[q], o);
         }
     }
-    loss_wave_argmax(bv, bi);
+    wave_argmax(bv, bi);
     const int lane = tid & 63, wave = tid >> 6, W = P > 64 ? P / 64 : 1;
     if (lane == 0) {
         if (wave < W) {
@@ -371,7 +345,7 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
     } else if (tid == 64) {
         double v = mred[0];
         int ix = ired[0];
-        for (int w = 1; w < NT / 64; ++w) loss_better(v, ix, mred[w], ired[w]);
+        for (int w = 1; w < NT / 64; ++w) arg_better(v, ix, mred[w], ired[w]);
         mred[0] = v; ired[0] = ix;
     }
     __syncthreads();
@@ -544,13 +518,13 @@ __global__ __launch_bounds__(kLossDayNT) void loss_day_kernel(LossDayArgs A) {
             int nd = A.nop ? A.nop[j] : j;
             nd = (nd >= 0 && nd < A.n_out && (!A.mask || A.mask[j] != 0)) ? nd : -1;
             const double v = en[j];
-            if (nd >= 0 && v == v && (v < pv || (v == pv && nd > pi))) loss_better(bv, bi, v, nd);
+            if (nd >= 0 && v == v && (v < pv || (v == pv && nd > pi))) arg_better(bv, bi, v, nd);
         }
-        loss_wave_argmax(bv, bi);
+        wave_argmax(bv, bi);
         if (lane == 0) { mv[wave] = bv; mi[wave] = bi; }
         __syncthreads();
         bv = mv[0]; bi = mi[0];
-        for (int w = 1; w < kLossDayNT / 64; ++w) loss_better(bv, bi, mv[w], mi[w]);
+        for (int w = 1; w < kLossDayNT / 64; ++w) arg_better(bv, bi, mv[w], mi[w]);
         __syncthreads();                           // (every read of mv / mi is done)
         if (tid == 0) { rec.top_index[k] = bi; rec.top_energy[k] = bi >= 0 ? bv : nan; }
         if (bi >= 0) { pv = bv; pi = bi; }

@@ -32,6 +32,7 @@ from .charging import ChargingMixin
 from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
 from .headroom import HeadroomMixin, HeadroomReport  # noqa: F401  (re-exported)
 from .losses import LossMixin, LossReport  # noqa: F401  (re-exported)
+from .transformers import TransformerMixin, TransformerReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
 from .steady_state import SteadyStateMixin
@@ -205,7 +206,7 @@ def _on_current_stream(fn):
 
 
 class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
-                 LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin):
+                 LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin, TransformerMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

@@ -153,3 +153,18 @@ class EnsembleReportMixin:
         node_g = self.node_sums(profile, add_load)
         return losses.native_losses_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, lines, nodes,
                                            classes, cost, slot_hours, loss_max, self.vset, arrays, out)
+
+    def transformer_reports(self, xf_of, rated_kva, pf=0.95, ambient=30.0, model=None, slot_hours=None, substeps=1,
+                            initial="cyclic", over_ratio=1.0, hot_limit=110.0, arrays=True, profile=None, add_load=False,
+                            out=None) -> list:
+        """AdmmEngine.transformer_report for every scenario -> S transformers.TransformerReports from one node-sum launch
+        and one revs_xf_report over all S (scenario s: the bits of the single engine's report on it).  xf_of: per node
+        row, the transformer it belongs to or -1; the rest as transformers.transformer_report_device.  profile /
+        add_load: see node_sums -- the default reports P_sch alone; out: a contiguous (S, K, T) float64 tensor on the
+        device that receives the hot-spots and stays there.  It needs no feeder tree.  The run's state is read, never
+        written."""
+        from . import transformers
+        node_g = self.node_sums(profile, add_load)
+        return transformers.transformer_report_device(node_g, xf_of, rated_kva, pf, ambient, model, slot_hours, substeps,
+                                                      initial, over_ratio, hot_limit, arrays, out, lib=self.lib,
+                                                      stream=self.stream)

@@ -125,7 +125,7 @@ class REVS:
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              **opt):
+              transformers=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -185,7 +185,13 @@ class REVS:
         classes, slot_hours, loss_max, cost): StudyReport.losses, every scenario's losses.LossReport -- per line and
         slot the power lost, per node the marginal loss factor, the day's lost energy and its cost under `tariff` --
         summarised over every line unless lines= says otherwise; one launch for all scenarios on either path (its
-        arrays are read back with opt arrays).  False: nothing of it runs."""
+        arrays are read back with opt arrays).  False: nothing of it runs.  transformers=True or a dict of
+        transformer_report_device's options (xf_of, rated_kva, pf, ambient, model, slot_hours, substeps, initial,
+        over_ratio, hot_limit): StudyReport.transformers, every scenario's transformers.TransformerReport -- per service
+        transformer the load ratio, the top-oil and hot-spot temperatures and the day's loss of insulation life.  Without
+        xf_of the owners come from the graph's labels (transformers.rows_by_transformer), without rated_kva the ratings
+        from transformers.size_ratings of each transformer's base-load peak (at the dict's pf); one launch for all
+        scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -320,6 +326,20 @@ class REVS:
             kw.update(losses if isinstance(losses, dict) else {})
             return loss_report_device(node_g, feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
                                       arrays=opt.get("arrays", False), **kw)
+
+        def transformer_reports(node_g):
+            from .transformers import rows_by_transformer, size_ratings, transformer_report_device
+            kw = dict(transformers if isinstance(transformers, dict) else {})
+            if "xf_of" not in kw:
+                kw["xf_of"] = rows_by_transformer(dist, res)[1]
+            if "rated_kva" not in kw:
+                xf_of = np.asarray(kw["xf_of"], np.int64)
+                base = np.zeros((int(xf_of.max(initial=-1)) + 1, len(tariff)))
+                np.add.at(base, xf_of[xf_of >= 0], np.array([all_homes[h] for h in res], np.float64)[xf_of >= 0])
+                kw["rated_kva"] = size_ratings(base.max(axis=1), pf=kw.get("pf", 0.95))
+            return transformer_report_device(node_g, kw.pop("xf_of"), kw.pop("rated_kva"),
+                                             arrays=opt.get("arrays", False), **kw)
+        want_xf = transformers is True or isinstance(transformers, dict)
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -346,6 +366,8 @@ class REVS:
                 rep.headroom = headroom_reports(buf)
             if losses is True or isinstance(losses, dict):
                 rep.losses = loss_reports(buf)
+            if want_xf:
+                rep.transformers = transformer_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -368,6 +390,9 @@ class REVS:
         if losses is True or isinstance(losses, dict):
             import torch
             rep.losses = loss_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if want_xf:
+            import torch
+            rep.transformers = transformer_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -82,7 +82,8 @@ class StudyReport:
     load_profile.LoadProfileReport of REVS.study(load_profile=True), else None; its rows are load_profile_rows: the
     study's labels, then one row dict(method="load", adoption, rating, seed) per case -- the base load under that case's
     EV homes.  charging: the charging.ChargingReport of REVS.study(charging=True) over the study's scenarios, else
-    None."""
+    None.  headroom / losses / transformers: every scenario's headroom.HeadroomReport / losses.LossReport /
+    transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -105,6 +106,7 @@ class StudyReport:
     charging: object | None = None
     headroom: list | None = None
     losses: list | None = None
+    transformers: list | None = None
 
     @property
     def n_groups(self):
