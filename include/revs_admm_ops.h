@@ -425,6 +425,61 @@ int revs_newton_chain_accept(int32_t T, const double *s0, const double *s1, doub
                              int32_t amax, int32_t kadd, int32_t chain_few, int32_t *nsup_sum,
                              int32_t *nsup_max);
 
+/* ---- the folded chain's operator launch on its own (csrc/newton_kernels.hip: op_chain_kv_kernel) -------------
+ * What revs_plan_chain_fold_run issues between two sweeps, for the kernel tests to call in isolation
+ * (tests/test_gpu_chain_kv.py).  One side = one evaluation judged by the tree form: its node sums pnq (es = 1: planar
+ * double[3][m][T] = p | N | q, the evaluation kernel's; es = 4: double[T][m][4] = {p, N, q, 0} per slot and node,
+ * slot-major, the folded sweep's), the multipliers y double[m][T], scratch for the rows (vfull, viol double[m][T],
+ * partial double[T][4]: the two sides run in ONE launch and need separate scratch), the candidate lists and the stats
+ * block its selection fills (as revs_op_dual_select's), tagged `seq`.
+ *   e1: rows, selection, small model and step into y_trial (revs_op_dual_tree_select_model_step's outputs: k_full, yhat,
+ *       info, y_trial; lin_out[8 t] the linear term), then the shifts of the trial: sh_a / sh_b [t * m + node] (slot-major)
+ *       = (R^T y_trial)[node][t] / kappa, summed over the slot's list in list order (sh_a) and over the rows that carry a
+ *       multiplier in ascending row order (sh_b: the order the next selection would list them in; equal to sh_a bit for
+ *       bit where the two orders agree).  A slot with more than 8 candidates: info = -999, y_trial's column = y's.
+ *   e2 (has_e2 != 0): rows and selection only, by the first T workgroups (the verdict of the trial before); e1's stats
+ *       then get their tag by a plain store.  fwd_src / fwd_dst (both or neither; has_e2 only): double[T][8] blocks,
+ *       entries 0..3 of every slot copied from src to dst in front of e2's tag.  clr0 / clr1: double[4 m T] arrays
+ *       cleared by the verdict half (NULL: none; ignored without e2).
+ *   prev_cidx / prev_ccnt (NULL: unknown -- every column of y is gathered): the candidate lists of the launch whose step
+ *       produced e1.y (= e2.y).
+ * What the kernel relies on and does NOT check:
+ *   list padding       the previous lists are what a selection leaves, padding included (index 0 beyond the count, all
+ *                      of a slot flagged -1): lanes 0..7 of a slot's wavefronts read prev_cidx[t][lane] and y at that
+ *                      row whatever the count is.
+ *   support on the list  every row of e1.y (and e2.y) with a multiplier is on its slot's previous list, when one is
+ *                      given: the slot's multipliers are read through the list alone.
+ *   sh_b               holds m T + 32 T doubles (a tuning build writes its stamps behind the shifts).
+ *   untouched rows     rows without a position in the tree (y = 0 there) are not written in y_trial.
+ * tree: the 256 x 8 shape (at most REVS_TREE_SWEEP_MAX nodes); m <= REVS_CHAIN_FOLD_MAX_M; T <= 256. */
+typedef struct {
+    const double *pnq, *y;
+    double *vfull, *viol, *partial;
+    int64_t *cand_idx;
+    int32_t *cand_cnt;
+    double *cand_val, *stats;
+    double seq;
+    int32_t es, reserved;
+} revs_chain_kv_side_t;
+typedef struct {
+    int32_t m, T, kadd, has_e2;
+    const revs_tree_t *tree;
+    double vlo, vhi, kappa, delta, scale, eps;
+    int32_t max_pivots, reserved;
+    revs_chain_kv_side_t e1, e2;
+    const double *R;
+    double *k_full, *yhat;
+    int32_t *info;
+    double *y_trial, *lin_out;
+    double *clr0, *clr1;
+    double *sh_a, *sh_b;
+    const int64_t *prev_cidx;
+    const int32_t *prev_ccnt;
+    const double *fwd_src;
+    double *fwd_dst;
+} revs_chain_kv_t;
+int revs_op_chain_kv(const revs_chain_kv_t *c, void *stream);
+
 /* ---- the model problem beyond REVS_DUAL_AMAX rows per slot (csrc/newton_big.hip) ------------------------------
  * The dual Newton path above holds REVS_DUAL_AMAX = 128 candidate rows per slot (its factor lives in LDS).  The reference
  * hands Gurobi every row (lpsolver.py:183-194); a slot with 129 ... REVS_DUAL_AMAX_BIG binding rows stays on the Newton

@@ -100,6 +100,25 @@ class Tree(C.Structure):
     _fields_ = [("n", C.c_int32), ("pack", C.c_void_p), ("w", C.c_void_p)]
 
 
+class ChainKvSide(C.Structure):
+    """revs_chain_kv_side_t"""
+    _fields_ = [("pnq", C.c_void_p), ("y", C.c_void_p), ("vfull", C.c_void_p), ("viol", C.c_void_p),
+                ("partial", C.c_void_p), ("cand_idx", C.c_void_p), ("cand_cnt", C.c_void_p), ("cand_val", C.c_void_p),
+                ("stats", C.c_void_p), ("seq", C.c_double), ("es", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ChainKv(C.Structure):
+    """revs_chain_kv_t"""
+    _fields_ = [("m", C.c_int32), ("T", C.c_int32), ("kadd", C.c_int32), ("has_e2", C.c_int32),
+                ("tree", C.POINTER(Tree)), ("vlo", C.c_double), ("vhi", C.c_double), ("kappa", C.c_double),
+                ("delta", C.c_double), ("scale", C.c_double), ("eps", C.c_double), ("max_pivots", C.c_int32),
+                ("reserved", C.c_int32), ("e1", ChainKvSide), ("e2", ChainKvSide), ("R", C.c_void_p),
+                ("k_full", C.c_void_p), ("yhat", C.c_void_p), ("info", C.c_void_p), ("y_trial", C.c_void_p),
+                ("lin_out", C.c_void_p), ("clr0", C.c_void_p), ("clr1", C.c_void_p), ("sh_a", C.c_void_p),
+                ("sh_b", C.c_void_p), ("prev_cidx", C.c_void_p), ("prev_ccnt", C.c_void_p), ("fwd_src", C.c_void_p),
+                ("fwd_dst", C.c_void_p)]
+
+
 class XfModel(C.Structure):
     """revs_xf_model_t"""
     _fields_ = [("dto_r", C.c_double), ("dhs_r", C.c_double), ("loss_ratio", C.c_double), ("n", C.c_double),
@@ -307,6 +326,7 @@ SIGNATURES = {
     "revs_op_dual_tree_select_model_step": (C.c_int, [_i32, _i32, C.POINTER(Tree), _p, _p, _f64, _f64, _i32, _p,
                                                       _p, _p, _p, _p, _p, _p, _f64, _p, _f64, _f64, _i32, _p, _p,
                                                       _p, _f64, _f64, _p, _p, _p]),
+    "revs_op_chain_kv": (C.c_int, [C.POINTER(ChainKv), _p]),
     "revs_newton_chain_accept": (C.c_int, [_i32, _p, _p, _f64, _f64, _i32, _i32, _i32, _p, _p]),
     "revs_tree_voltage": (C.c_int, [_i32, _i32, C.POINTER(Tree), _p, _f64, _f64, _p, _p, _p]),
     "revs_comm_unique_id": (C.c_int, [_p]),

@@ -101,7 +101,7 @@ struct ChainKv {
     int32_t *info;
     double *y_trial, *lin_out;
     double *clr0, *clr1;
-    double *sh_a, *sh_b;     // out: the shifts R^T y_trial / kappa (double[m][T]) in list order / in row order
+    double *sh_a, *sh_b;     // out: the shifts R^T y_trial / kappa, slot-major (sh[t * m + node]), in list order / in row order
     // the candidate lists of the launch whose step produced e1.y (= e2.y): every row that carries a
     // multiplier is on them, so the slots need not gather the multipliers' columns (NULL: unknown)
     const int64_t *prev_cidx = nullptr;

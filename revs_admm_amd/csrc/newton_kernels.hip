@@ -2248,6 +2248,31 @@ extern "C" int revs_op_dual_tree_select_model_step(
     return REVS_OK;
 }
 
+// chain_kv_launch behind the C ABI: the tree by the entry points' one predicate, everything else is checked there
+extern "C" int revs_op_chain_kv(const revs_chain_kv_t *c, void *stream) {
+    const TreeArgs tr = tree_args(c ? c->tree : nullptr);
+    REVS_REQUIRE(c && tree_sweep_ok(tr), "revs_op_chain_kv: bad argument (" REVS_TREE_FORM_MSG ")",
+                 REVS_TREE_FORM_ARGS(tr, REVS_TREE_SWEEP_MAX));
+    auto side = [](const revs_chain_kv_side_t &s) {
+        ChainKvSide o{s.pnq, s.y, s.vfull, s.viol, s.partial, s.cand_idx, s.cand_cnt, s.cand_val, s.stats, s.seq};
+        o.es = s.es;
+        return o;
+    };
+    ChainKv k{};
+    k.m = c->m; k.T = c->T; k.kadd = c->kadd; k.has_e2 = c->has_e2;
+    k.tree = tr;
+    k.vlo = c->vlo; k.vhi = c->vhi; k.kappa = c->kappa; k.delta = c->delta; k.scale = c->scale; k.eps = c->eps;
+    k.max_pivots = c->max_pivots;
+    k.e1 = side(c->e1); k.e2 = side(c->e2);
+    k.R = c->R; k.k_full = c->k_full; k.yhat = c->yhat; k.info = c->info;
+    k.y_trial = c->y_trial; k.lin_out = c->lin_out;
+    k.clr0 = c->clr0; k.clr1 = c->clr1;
+    k.sh_a = c->sh_a; k.sh_b = c->sh_b;
+    k.prev_cidx = c->prev_cidx; k.prev_ccnt = c->prev_ccnt;
+    k.fwd_src = c->fwd_src; k.fwd_dst = c->fwd_dst;
+    return chain_kv_launch(k, stream);
+}
+
 // One evaluation of the dual function as a single host call (the driver's steady state is
 // host-bound otherwise: five launches of 3-12 us each).  phase bit 0: R^T y (when use_y)
 // and the home pass; phase bit 1: R p, row bookkeeping (one launch with tile_counters and

@@ -13,8 +13,9 @@ which branch of csrc/select_body.h a slot takes follows from M and from the colu
 (c) the tree rows kernels in front of it, handing over through LDS (tree <= 2048 nodes, 3 m doubles fit), through
 global memory in the same workgroup (they do not fit) or to a launch of its own (larger trees); (d)
 dual_select_body<false> inside the residence sweep's launch, fed by the restatement itself; (e) the 512-row lists of
-csrc/newton_big.hip.  chain_rows_select_body (the folded chain's own selection) and revs_op_dual_select_model_step keep
-their bit-for-bit tests against the general loop and against (a)."""
+csrc/newton_big.hip.  chain_rows_select_body (the folded chain's own selection) and revs_op_dual_tree_select_model_step
+are held to a restatement built on this one, branch by branch, in tests/test_gpu_chain_kv.py (columns:
+tests/chain_cases.py); revs_op_dual_select_model_step to its parts in tests/test_gpu_newton.py."""
 import ctypes as C
 import functools
 

@@ -56,10 +56,33 @@ def test_every_shape_entry_points_refuse_a_malformed_tree(lib, name):
     assert b"16392" in lib.revs_last_error() and b"16384" in lib.revs_last_error()
 
 
+def _chain_kv(lib, tr):
+    """revs_op_chain_kv with every argument but the tree acceptable (both sides, lists of the launch before given)"""
+    from revs_admm_amd import _lib
+    side = lambda base: _lib.ChainKvSide(P, P, base, P, P, P, P, P, P, 1.0, 4, 0)
+    c = _lib.ChainKv(m=4, T=24, kadd=4, has_e2=1, vlo=0.95, vhi=1.05, kappa=1.0, delta=0.0, scale=1.0, eps=1e-8,
+                     max_pivots=8, e1=side(P), e2=side(P + 16), R=P, k_full=P, yhat=P, info=P, y_trial=P + 16, lin_out=P,
+                     sh_a=P, sh_b=P + 16, prev_cidx=P, prev_ccnt=P)
+    if tr is not None:
+        c.tree = C.pointer(tr._obj)         # (tr: what C.byref returned)
+    return lib.revs_op_chain_kv(C.byref(c), None)
+
+
+SWEEP_SHAPE = {
+    "revs_op_dual_tree_select_model_step": lambda lib, tr: lib.revs_op_dual_tree_select_model_step(
+        4, 24, tr, P, P, 0.95, 1.05, 4, P, P, P, P, P, P, P, 1.0, P, 1.0, 0.0, 8, P, P, P, 1.0, 1e-8, P + 16, P, None),
+    "revs_op_chain_kv": _chain_kv,
+}
+
+
 def test_sweep_shape_entry_point_refuses_a_malformed_tree(lib):
-    """revs_op_dual_tree_select_model_step holds the 256 x 8 shape only: at most REVS_TREE_SWEEP_MAX = 2048 nodes."""
-    call = lambda lib, tr: lib.revs_op_dual_tree_select_model_step(
-        4, 24, tr, P, P, 0.95, 1.05, 4, P, P, P, P, P, P, P, 1.0, P, 1.0, 0.0, 8, P, P, P, 1.0, 1e-8, P + 16, P, None)
-    for what, kw in dict(BAD_TREES, **{"n=2056 (over REVS_TREE_SWEEP_MAX)": dict(n=2056)}).items():
-        assert _refused(lib, call, _tree(**kw)), (what, lib.revs_last_error())
-    assert call(lib, _tree(n=2056)) == -1 and b"2056" in lib.revs_last_error() and b"2048" in lib.revs_last_error()
+    """revs_op_dual_tree_select_model_step and revs_op_chain_kv hold the 256 x 8 shape only: at most
+    REVS_TREE_SWEEP_MAX = 2048 nodes."""
+    for name, call in sorted(SWEEP_SHAPE.items()):
+        for what, kw in dict(BAD_TREES, **{"n=2056 (over REVS_TREE_SWEEP_MAX)": dict(n=2056)}).items():
+            assert _refused(lib, call, _tree(**kw)), (name, what, lib.revs_last_error())
+        assert call(lib, _tree(n=2056)) == -1 and b"2056" in lib.revs_last_error() and b"2048" in lib.revs_last_error()
+
+
+def test_chain_kv_refuses_a_null_descriptor(lib):
+    assert lib.revs_op_chain_kv(None, None) == -1 and b"revs_op_chain_kv" in lib.revs_last_error()
