@@ -333,21 +333,24 @@ def pdhg_steps(h: Homes, tau_scale=0.25, sigma_scale=4.0):
 
 def home_solve_relaxed_pdhg(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0,
                             iters=2000, tol=1e-7, check=8,
-                            tau_scale=None, sigma_scale=None, dtype=np.float64, full_rows=True):
+                            tau_scale=None, sigma_scale=None, dtype=np.float64, full_rows=True, x0=None, y0=None):
     """PDHG (Chambolle-Pock) on the relaxed home QP, restating the HIP kernel's
     iteration so the two can be compared step for step.  x = p/rating in [0,w];
         x+ = clip((x - tau (K^T y + b)) / (1 + tau), 0, w)
         y+ = v - sigma clip(v / sigma, lo, hi),  v = y + sigma K (2 x+ - x)
     rows j = 0..T-1 of K x are s_{j+1} - init; lo_j = 0 (j < T-1), lo_{T-1} =
     max(0.9, init) - init, hi_j = 1 - init.  Stops when the largest change of x
-    over a block of `check` iterations' last step falls below tol."""
+    over a block of `check` iterations' last step falls below tol.
+    x0 (N,T), y0 (N,): the presolved form's warm start (full_rows=False) -- the kernel's when it carries its multiplier:
+    x0 = (P_sch - LOAD) / rating, clipped to the window's box, and the terminal row's multiplier."""
     dt = dtype
     q = home_linear_term(cost, h, p_est, p_sch, gamma, kappa)
     rate = np.where(h.ev, h.rating, 1.0)
     b = (q / (kappa * rate[:, None])).astype(dt)
     w = h.window().astype(dt)
     if not full_rows:
-        return _pdhg_presolved(h, b, w, iters, tol, check, tau_scale or 0.5, sigma_scale or 2.0, dt)
+        return _pdhg_presolved(h, b, w, iters, tol, check, tau_scale or 0.5, sigma_scale or 2.0, dt, x0, y0)
+    assert x0 is None and y0 is None
     tau, sig, delta = pdhg_steps(h, tau_scale or 0.25, sigma_scale or 4.0)
     tau, sig, delta = (tau.astype(dt)[:, None], sig.astype(dt)[:, None],
                        delta.astype(dt)[:, None])
@@ -379,7 +382,7 @@ def home_solve_relaxed_pdhg(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0,
     return p, _soc(h, p), p + h.LOAD, n_it
 
 
-def _pdhg_presolved(h: Homes, b, w, iters, tol, check, tau_scale, sigma_scale, dt):
+def _pdhg_presolved(h: Homes, b, w, iters, tol, check, tau_scale, sigma_scale, dt, x0=None, y0=None):
     """PDHG on the presolved home QP (the kernel's default): with p >= 0 the SOC is
     nondecreasing, so of init <= s_t <= 1, s_T >= 0.9 only the terminal rows can bind;
     K is the single row delta*1^T (||K|| = delta sqrt(T_w)) and the dual one scalar."""
@@ -389,8 +392,8 @@ def _pdhg_presolved(h: Homes, b, w, iters, tol, check, tau_scale, sigma_scale, d
     tau, sig = dt(tau_scale) / nK, dt(sigma_scale) / nK
     lo = (np.maximum(SOC_TARGET, h.initial) - h.initial).astype(dt)[:, None]
     hi = (SOC_MAX - h.initial).astype(dt)[:, None]
-    x = np.zeros(b.shape, dt)
-    y = np.zeros((h.N, 1), dt)
+    x = np.zeros(b.shape, dt) if x0 is None else np.clip(np.asarray(x0, dt), 0, w)
+    y = np.zeros((h.N, 1), dt) if y0 is None else np.where(h.ev, np.asarray(y0, dt), dt(0))[:, None]
     done = ~h.ev.copy()
     n_it = np.zeros(h.N, np.int64)
     one = dt(1.0)
