@@ -13,8 +13,9 @@
  * revs_load_profile: the demand curve of any of them -- load per slot, peaks and diversity, by class of residence -- and
  * revs_charge_report: what the chargers do, per EV and per slot, revs_net_headroom: how much more charging
  * every node could take in every slot, and what limits it, revs_net_losses: what the feeder loses carrying a
- * schedule, per line, per node at the margin, per slot and per day, and last revs_xf_report: what a schedule does to the
- * service transformers -- load ratio, top-oil and hot-spot temperature per slot, loss of insulation life per day.
+ * schedule, per line, per node at the margin, per slot and per day, revs_xf_report: what a schedule does to the
+ * service transformers -- load ratio, top-oil and hot-spot temperature per slot, loss of insulation life per day -- and
+ * last revs_flex_report: how much of the charging can still be moved, up and down, per EV, node and slot.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -1128,6 +1129,80 @@ int revs_xf_report(int32_t S, int32_t m, int32_t T, int32_t K, int32_t nnz, cons
                    double *top_oil_out, double *hot_out, double *faa_out, revs_net_summary_t *sum_ratio_out,
                    revs_net_summary_t *sum_hot_out, revs_xf_day_t *xf_day_out, revs_xf_fleet_t *fleet_out, void *scratch,
                    void *stream);
+
+/* ---- flexibility report: up and down reserve per EV, node and slot (csrc/flex_kernels.hip) ----------
+ * How much of a schedule's charging can still be moved, where and when, without a car leaving under target: a closed
+ * form of the charger power (revs_charge_report's p, strides and homes, under the same rules) and the records.
+ * Energy is in kW x slots (soc[t + 1] = soc[t] + p[t] / capacity).
+ *
+ * Per row (residence i, scenario s) with ev != 0, the record's fields widened to double, every double operation rounded
+ * on its own, no fused multiply-add, every comparison with a NaN false, min2(a, b) = (b < a) ? b : a:
+ *   ws = clamp(start, 0, T), we = clamp(end, 0, T), W = max(we - ws, 0) (revs_rule_schedule's window);
+ *   r = rating, c = capacity, i0 = initial, tgt = (i0 > 0.9) ? i0 : 0.9;
+ *   E_lo = (tgt - i0) c, E_hi = (1.0 - i0) c (revs_rule_schedule's expressions);
+ *   done(t) = sum of (double) p[u], u < t: one accumulator from +0.0, u ascending; energy = done(T);
+ *   A(t) = (double) max(we - max(t + 1, ws), 0) r: what full-rate charging in the window slots after t can still deliver.
+ * For a window slot ws <= t < we, d = (double) p[t]:
+ *   up[t], the largest extra power in slot t that leaves the state of charge at or below 1 after the slot:
+ *     m = min2(r - d, (E_hi - done(t)) - d);  up = (m > 0) ? ((m < r) ? m : r) : 0
+ *   down[t], the largest cut in slot t after which full-rate charging in every later window slot still reaches the target:
+ *     m = ((done(t) + d) + A(t)) - E_lo;  q = (d < r) ? d : r;  down = (m > 0 && q > 0) ? min2(q, m) : 0
+ *   integral != 0 (on/off chargers), with the m and q above:
+ *     up = (up >= r) ? r : 0;  down = (d > on_frac r && m >= d && q > 0) ? q : 0
+ * Outside the window both are 0.  By construction 0 <= up, down <= r and neither is a NaN for any finite r: a NaN, +-inf
+ * or negative power only sets the flag.
+ *
+ * row_rec [S][n]: up_energy, down_energy: the sums over t ascending from +0.0; n_up, n_down: the slots with a value > 0;
+ *   laxity = (double) W - E_lo / r: the slots of freedom the car has at all (r <= 0: what IEEE gives); ready: the
+ *   smallest t in 0..T for which tgt - (i0 + done(t) / c) > short_tol is false (the charging report's under-target test
+ *   along the day), -1: none; slack = we - ready (it may be negative), 0 when ready == -1.  flags: bit 0 ev != 0; bit 1
+ *   ready == -1; bit 2 some p[t] is not finite; bit 3 E_lo > (double) W r (cannot be served whatever the schedule);
+ *   bit 4 ready > we.  A row with ev == 0 gets zeros, ready = -1, flags 0; its p is not read.
+ * slot_rec[s][t] ([S][T]) over the EV rows: n_plugged (ws <= t < we), n_up, n_down (rows with a value > 0), up, down:
+ *   sums in a fixed order, the same bits from call to call.
+ * day_rec[s] ([S]), a function of the slot and row records of the same call whether or not they are asked for:
+ *   up_energy, down_energy: the slots' sums added, t ascending from +0.0; peak_up / peak_up_slot, peak_down /
+ *   peak_down_slot by a scan from slot 0 that moves on `>` only, both slots -1 without an EV; n_ev, n_never_ready (bit
+ *   1), n_unservable (bit 3), n_late (bit 4), n_rigid (EV rows with n_up == 0 && n_down == 0).
+ * hist: int32[S][2][T + 1]: [0] of ready (rows with ready >= 0), [1] of slack (rows with ready >= 0 and 0 <= slack <= T).
+ * node_up, node_down: double[S][m][T], asked for together and with node_ptr: device int64[m + 1], CSR offsets of the
+ *   rows sorted by node (node_ptr[0] = 0, node_ptr[m] = n, ascending; rows outside are left out).  Node j, slot t: the
+ *   sum of revs_q36(up[t]) over the node's rows (rounding to a multiple of 2^-36; numpy: (x + 98304.0) - 98304.0 and a
+ *   plain sum).  Every addition is exact while ratings stay below 2^15 kW and a node's sum below 2^17 kW, so any order
+ *   of summation gives the same bits; beyond, the result is unspecified.  A node without rows gets +0.0.
+ * val_out: double[4][S][n]: up_energy, down_energy, (double) slack, laxity; a NaN where the row is no EV or flags bit 2
+ *   is set, and for slack where ready == -1.  keep_out: uint8[S][n], 1 for EV rows without bit 2.  The two are what
+ *   revs_bill_study (base = -1) takes: the box-plot records come from that selection.
+ * Any output may be NULL, not all; the others are the same bytes.  Reads p, homes, node_ptr; writes the outputs and the
+ * scratch.  A thread owns a row and walks its slots in chunks of revs_flex_report_chunk() staged through LDS, done(t) in
+ * a register: one pass over p; the scenario is grid.y.  Slot counts: wavefront ballots, LDS counters, one global integer
+ * atomic per (workgroup, slot, counter); slot sums: per-workgroup partials in the scratch, folded in a fixed order by a
+ * second kernel; a third derives the day records.  Node sums: LDS accumulators over the consecutive rows of a node, one
+ * global f64 add per (workgroup, node, slot) into the zeroed output -- the only floating-point atomics, all exact.  No
+ * grid-wide barrier, a fixed sequence of launches and memsets on one stream; the call only enqueues.  REVS_EINVAL
+ * before any launch: everything revs_charge_report refuses; one node output without the other; a node output without
+ * node_ptr or with m < 1; m S T >= 2^31.  scratch: revs_flex_report_scratch bytes (<= 0 for sizes the report refuses). */
+typedef struct {
+    double up_energy, down_energy, laxity, energy;
+    int32_t ready, slack, n_up, n_down, flags;
+    int32_t reserved[3];
+} revs_flex_row_t;                    /* 64 bytes */
+typedef struct {
+    int32_t n_plugged, n_up, n_down, reserved;
+    double up, down;
+} revs_flex_slot_t;                   /* 32 bytes */
+typedef struct {
+    double up_energy, down_energy, peak_up, peak_down;
+    int32_t peak_up_slot, peak_down_slot, n_ev, n_never_ready, n_unservable, n_late, n_rigid, reserved;
+} revs_flex_day_t;                    /* 64 bytes */
+int32_t revs_flex_report_chunk(void);
+int64_t revs_flex_report_scratch(int32_t S, int64_t n, int32_t T);
+int revs_flex_report(int32_t S, int64_t n, int32_t T, const float *p, int64_t stride_s, int64_t stride_i,
+                     const revs_home_t *homes, int32_t integral, double on_frac, double short_tol,
+                     const int64_t *node_ptr, int32_t m,
+                     revs_flex_row_t *row_rec, revs_flex_slot_t *slot_rec, revs_flex_day_t *day_rec, int32_t *hist,
+                     double *node_up, double *node_down, double *val_out, uint8_t *keep_out,
+                     void *scratch, void *stream);
 
 #ifdef __cplusplus
 }

@@ -11,6 +11,8 @@
     headroom       AdmmEngine.headroom_report: spare charger power per node and slot, and what limits it
     losses         AdmmEngine.loss_report: line losses, marginal loss per node, the day's lost energy and its cost
     transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
+    flexibility    how much charging can still be moved: FlexReport, flexibility_report / flexibility_report_device -- up and
+                   down reserve per EV, node and slot, the slot a car is ready at and the slack it leaves
     drawing        the reference's compute_flows / compute_voltage / compute_losses over it (no figures)
     synthetic      synthetic feeders / residences for benchmarks and tests
     build          compiles csrc/*.hip into librevs_admm.so (gfx950)

@@ -198,6 +198,21 @@ CHARGE_DAY_DTYPE = np.dtype([("peak_power", "<f8"), ("energy", "<f8"), ("coincid
 assert CHARGE_DAY_DTYPE.itemsize == 64
 CHARGE_EV, CHARGE_UNDER, CHARGE_NONFINITE = 1, 2, 4      # bits of revs_charge_row_t.flags
 
+# numpy mirrors of revs_flex_row_t, revs_flex_slot_t and revs_flex_day_t (include/revs_admm_ops.h)
+FLEX_ROW_DTYPE = np.dtype([("up_energy", "<f8"), ("down_energy", "<f8"), ("laxity", "<f8"), ("energy", "<f8"),
+                           ("ready", "<i4"), ("slack", "<i4"), ("n_up", "<i4"), ("n_down", "<i4"), ("flags", "<i4"),
+                           ("reserved", "<i4", (3,))])
+assert FLEX_ROW_DTYPE.itemsize == 64
+FLEX_SLOT_DTYPE = np.dtype([("n_plugged", "<i4"), ("n_up", "<i4"), ("n_down", "<i4"), ("reserved", "<i4"),
+                            ("up", "<f8"), ("down", "<f8")])
+assert FLEX_SLOT_DTYPE.itemsize == 32
+FLEX_DAY_DTYPE = np.dtype([("up_energy", "<f8"), ("down_energy", "<f8"), ("peak_up", "<f8"), ("peak_down", "<f8"),
+                           ("peak_up_slot", "<i4"), ("peak_down_slot", "<i4"), ("n_ev", "<i4"), ("n_never_ready", "<i4"),
+                           ("n_unservable", "<i4"), ("n_late", "<i4"), ("n_rigid", "<i4"), ("reserved", "<i4")])
+assert FLEX_DAY_DTYPE.itemsize == 64
+# bits of revs_flex_row_t.flags
+FLEX_EV, FLEX_NEVER_READY, FLEX_NONFINITE, FLEX_UNSERVABLE, FLEX_LATE = 1, 2, 4, 8, 16
+
 # numpy mirror of revs_headroom_day_t (include/revs_admm_ops.h)
 HEADROOM_DAY_DTYPE = np.dtype([("min", "<f8"), ("slot", "<i4"), ("n_short", "<i4")])
 assert HEADROOM_DAY_DTYPE.itemsize == 16
@@ -383,6 +398,10 @@ SIGNATURES = {
     "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
                                  _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_flex_report_chunk": (_i32, []),
+    "revs_flex_report_scratch": (_i64, [_i32, _i64, _i32]),
+    "revs_flex_report": (C.c_int, [_i32, _i64, _i32, _p, _i64, _i64, _p, _i32, _f64, _f64, _p, _i32, _p, _p, _p, _p, _p, _p,
+                                   _p, _p, _p, _p]),
 }
 DUAL_AMAX = 128          # REVS_DUAL_AMAX
 DUAL_FEW = 48            # REVS_DUAL_FEW (16 / 32: the same times on the 121144 feeder; 80 / 128: 11.2 ms against 9.5, r05)

@@ -29,6 +29,7 @@ from .feeder import feeder_tree, tree_from_R, tree_voltage_host  # noqa: F401  (
 from .certificate import Certificate, CertificateMixin  # noqa: F401  (re-exported)
 from .load_profile import LoadProfileMixin
 from .charging import ChargingMixin
+from .flexibility import FlexMixin, FlexReport  # noqa: F401  (re-exported)
 from .network import NetworkMixin, NetworkReport  # noqa: F401  (re-exported)
 from .headroom import HeadroomMixin, HeadroomReport  # noqa: F401  (re-exported)
 from .losses import LossMixin, LossReport  # noqa: F401  (re-exported)
@@ -206,7 +207,7 @@ def _on_current_stream(fn):
 
 
 class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
-                 LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin, TransformerMixin):
+                 LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin, TransformerMixin, FlexMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

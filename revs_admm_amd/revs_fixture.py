@@ -125,7 +125,7 @@ class REVS:
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              transformers=False, **opt):
+              transformers=False, flexibility=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -191,7 +191,12 @@ class REVS:
         transformer the load ratio, the top-oil and hot-spot temperatures and the day's loss of insulation life.  Without
         xf_of the owners come from the graph's labels (transformers.rows_by_transformer), without rated_kva the ratings
         from transformers.size_ratings of each transformer's base-load peak (at the dict's pf); one launch for all
-        scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs."""
+        scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs.
+        flexibility=True: StudyReport.flexibility, the flexibility.FlexReport of every method's charger power -- per EV
+        and slot how much charging could still be added or shed without the car leaving under target -- from the same
+        buffer and records as charging=True, pooled by the report's groups, for the charger of opt mode (opt
+        flexibility_on_frac, flexibility_short_tol: 0.0 and 1e-6 by default; the row records are read back with opt
+        arrays; no node arrays: those are AdmmEngine.flexibility_report's, over the engine's nodes)."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -221,7 +226,8 @@ class REVS:
             node_rating = line_nodes(dist, opt.get("line_rating"), parent, nonsub)[0]
         # deferred: (position in profiles, homes) of the ensemble's scenarios; owners: every scenario's EV homes
         labels, profiles, deferred, owners = [], [], [], []
-        charge_p, charge_rec = [], []              # charging=True: every scenario's charger power (None: deferred), records
+        want_p = bool(charging or flexibility)
+        charge_p, charge_rec = [], []              # charging / flexibility: every scenario's charger power (None: deferred), records
         for adoption in adoptions:
             for rating in ratings:
                 for seed in seeds:
@@ -233,7 +239,7 @@ class REVS:
                     for method in methods:
                         labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
                         owners.append(ev_homes)
-                        if charging:
+                        if want_p:
                             charge_rec.append(homes_to_arrays(homes, res)[1])
                             charge_p.append(None)
                         if method == "distributed" and ensemble:
@@ -252,7 +258,7 @@ class REVS:
                         else:
                             P_res, P_ev = self.get_individual_optimal(tariff, homes)[:2]
                         profiles.append(np.array([P_res[h] for h in res], np.float64))
-                        if charging:
+                        if want_p:
                             charge_p[-1] = np.array([P_ev[h] for h in res], np.float32)
         conv_rep, charge_dev = None, None
         if deferred:
@@ -263,8 +269,8 @@ class REVS:
                                    return_certificates=certify, return_node_sums=device_report,
                                    return_convergence=convergence,
                                    convergence_groups=self._deferred_groups(labels, keys, [i for i, _ in deferred]),
-                                   convergence_patience=opt.get("patience", 8), return_charging=charging)
-            if charging:
+                                   convergence_patience=opt.get("patience", 8), return_charging=want_p)
+            if want_p:
                 *head, charge_dev = sols
                 sols = tuple(head) if len(head) > 1 else head[0]
             if convergence is not None:
@@ -300,19 +306,31 @@ class REVS:
             prof_rows = [dict(lab) for lab in labels] + [dict(method="load", adoption=c[0], rating=c[1], seed=c[2])
                                                          for c in cases]
 
-        def charging_report():
+        def charger_power():
             import torch
-            from .charging import charging_report_device
             dev = torch.device(self.device)
             buf = torch.empty(len(res), len(labels), len(tariff), dtype=torch.float32, device=dev)
             where = {i: k for k, (i, _) in enumerate(deferred)}
             for s, p in enumerate(charge_p):
                 buf[:, s].copy_(charge_dev[:, where[s]] if p is None else torch.from_numpy(p))
             rec = np.ascontiguousarray(np.stack(charge_rec, axis=1)).view(np.uint8).reshape(-1)
-            return charging_report_device(buf, torch.from_numpy(rec).to(dev), tariff,
+            return buf, torch.from_numpy(rec).to(dev)
+
+        def charging_report():
+            from .charging import charging_report_device
+            return charging_report_device(*charger_power(), tariff,
                                           groups=[order.index(c) for c in combos],
                                           on_frac=opt.get("charging_on_frac", 0.0),
                                           short_tol=opt.get("charging_short_tol", 1e-6), rows=bool(opt.get("arrays", False)))
+
+        def flexibility_report():
+            from .baselines import CHARGERS
+            from .flexibility import flexibility_report_device
+            return flexibility_report_device(*charger_power(), CHARGERS[opt.get("mode", "binary")],
+                                             groups=[order.index(c) for c in combos],
+                                             on_frac=opt.get("flexibility_on_frac", 0.0),
+                                             short_tol=opt.get("flexibility_short_tol", 1e-6),
+                                             rows=bool(opt.get("arrays", False)), nodes=False)
 
         def headroom_reports(node_g):
             from .headroom import headroom_report_device
@@ -368,6 +386,8 @@ class REVS:
                 rep.losses = loss_reports(buf)
             if want_xf:
                 rep.transformers = transformer_reports(buf)
+            if flexibility:
+                rep.flexibility = flexibility_report()
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -393,6 +413,8 @@ class REVS:
         if want_xf:
             import torch
             rep.transformers = transformer_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if flexibility:
+            rep.flexibility = flexibility_report()
         return labels, rep
 
     @staticmethod

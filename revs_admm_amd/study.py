@@ -83,7 +83,8 @@ class StudyReport:
     study's labels, then one row dict(method="load", adoption, rating, seed) per case -- the base load under that case's
     EV homes.  charging: the charging.ChargingReport of REVS.study(charging=True) over the study's scenarios, else
     None.  headroom / losses / transformers: every scenario's headroom.HeadroomReport / losses.LossReport /
-    transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None."""
+    transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None.  flexibility: the
+    flexibility.FlexReport of REVS.study(flexibility=True) over the study's scenarios, else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -107,6 +108,7 @@ class StudyReport:
     headroom: list | None = None
     losses: list | None = None
     transformers: list | None = None
+    flexibility: object | None = None
 
     @property
     def n_groups(self):
