@@ -5,16 +5,15 @@ its target state of charge and what the charging cost it -- from the charger pow
 ensemble's (n, S, T), the p of a rule schedule.  Only records are read back.  Drawing stays outside the project."""
 from __future__ import annotations
 
-import math
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from . import _lib, baselines
-from ._lib import BILL_DTYPE, CHARGE_DAY_DTYPE, CHARGE_ROW_DTYPE, CHARGE_SLOT_DTYPE, HOME_DTYPE, check, ptr
-from .bills import check_groups
+from . import _lib, baselines, row_reports as rr
+from ._lib import CHARGE_DAY_DTYPE, CHARGE_ROW_DTYPE, CHARGE_SLOT_DTYPE, check, ptr
 
+WHO = "charging report"
 QUANTITIES = ("energy", "cost", "soc_end", "wait")
 POOLED_SLOT_DTYPE = np.dtype([(k, "<i8") for k in ("n_ev", "n_plugged", "n_on", "n_full", "n_starts")])
 
@@ -69,12 +68,7 @@ class ChargingReport:
 def check_charge_args(S, n, T, tariff, groups, on_frac, short_tol, index=None):
     """The checks of a charging report, before the library is loaded -> (tariff float64 (T,) or None, group ids int32
     (S,), G, on_frac, short_tol, index int32 (n,) or None).  A tariff that is a tensor on the device passes as it is."""
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"charging report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    if not 1 <= T <= _lib.MAX_T:
-        raise ValueError(f"charging report: {T} slots outside 1..{_lib.MAX_T}")
-    if n < 1 or S * n >= 2 ** 31:
-        raise ValueError(f"charging report: {S} scenarios x {n} residences outside 1..2^31 - 1 rows")
+    rr.check_sizes(WHO, S, n, T)
     if isinstance(tariff, torch.Tensor):
         if tariff.dtype != torch.float64 or tuple(tariff.shape) != (T,) or not tariff.is_contiguous():
             raise ValueError(f"charging report: a tariff on the device must be a contiguous float64 tensor ({T},)")
@@ -82,32 +76,7 @@ def check_charge_args(S, n, T, tariff, groups, on_frac, short_tol, index=None):
         tariff = np.ascontiguousarray(tariff, np.float64)
         if tariff.shape != (T,):
             raise ValueError(f"charging report: the tariff must have one price per slot ({T}), got {tariff.shape}")
-    on_frac, short_tol = float(on_frac), float(short_tol)
-    if math.isnan(on_frac) or on_frac < 0:
-        raise ValueError(f"charging report: on_frac={on_frac} is negative or a NaN")
-    if math.isnan(short_tol) or short_tol < 0:
-        raise ValueError(f"charging report: short_tol={short_tol} is negative or a NaN")
-    gid, G = check_groups(S, groups)
-    if G > S:
-        raise ValueError(f"charging report: group ids up to {G - 1} for {S} scenarios")
-    if index is not None:
-        index = np.asarray(index)
-        if index.shape != (n,) or not np.issubdtype(index.dtype, np.integer) or index.min() < 0 \
-                or index.max() >= 2 ** 31 - 1:
-            raise ValueError(f"charging report: index must be {n} integers in 0..2^31 - 2")
-        index = np.ascontiguousarray(index, np.int32)
-    return tariff, gid, G, on_frac, short_tol, index
-
-
-def _check_tensor(p):
-    if not isinstance(p, torch.Tensor) or p.dtype != torch.float32 or p.dim() not in (2, 3):
-        raise ValueError("charging report: the power must be a float32 tensor (residences, slots) or (residences, "
-                         "scenarios, slots)")
-    if p.dim() == 2:
-        p = p.unsqueeze(1)
-    if p.numel() == 0 or p.stride(2) != 1:
-        raise ValueError(f"charging report: the power is empty or its slots are not contiguous, {tuple(p.shape)}")
-    return p
+    return (tariff,) + rr.check_row_args(WHO, S, n, groups, on_frac, short_tol, index)
 
 
 def charging_report_device(p, homes, tariff=None, index=None, groups=None, on_frac=0.0, short_tol=1e-6, rows=True,
@@ -126,20 +95,10 @@ def charging_report_device(p, homes, tariff=None, index=None, groups=None, on_fr
               not written at all.
     order     None, or an int64 tensor on the device: the rows are reported in the order i -> order[i] (row records,
               and the box records' totals: those are sums in the order of the rows)."""
-    p = _check_tensor(p)
+    p = rr.check_tensor(WHO, "power", p)
     n, S, T = p.shape
     tariff, gid, G, on_frac, short_tol, index = check_charge_args(S, n, T, tariff, groups, on_frac, short_tol, index)
-    if rows not in (True, False, "device"):
-        raise ValueError(f'charging report: rows must be True, False or "device", got {rows!r}')
-    dev = p.device
-    if dev.type != "cuda":
-        raise ValueError(f"charging report: the power lies on {dev}; the report runs on the GPU")
-    if not isinstance(homes, torch.Tensor) or homes.dtype != torch.uint8 or homes.numel() != n * S * HOME_DTYPE.itemsize \
-            or not homes.is_contiguous() or homes.device != dev:
-        raise ValueError(f"charging report: homes must hold {n * S} records of {HOME_DTYPE.itemsize} bytes (uint8, "
-                         f"contiguous) on {dev}")
-    stride_i = p.stride(0) if n > 1 else S * max(p.stride(1), T)
-    stride_s = p.stride(1) if S > 1 else n * stride_i
+    dev = rr.check_on_device(WHO, p, homes, rows=rows)
     with torch.cuda.device(dev):
         lb = lib or _lib.load()
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
@@ -156,37 +115,16 @@ def charging_report_device(p, homes, tariff=None, index=None, groups=None, on_fr
         if nbytes <= 0:
             raise ValueError(f"charging report: no scratch size for S={S}, {n} residences, T={T}")
         d_scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        check(lb.revs_charge_report(S, n, T, ptr(p), stride_s, stride_i, ptr(homes), ptr(d_tariff), on_frac, short_tol,
+        check(lb.revs_charge_report(S, n, T, ptr(p), *rr.strides(p), ptr(homes), ptr(d_tariff), on_frac, short_tol,
                                     ptr(d_row), ptr(d_slot), ptr(d_day), ptr(d_hist), ptr(d_val), ptr(d_keep),
                                     ptr(d_scratch), st), "revs_charge_report")
-        if order is not None:
-            d_val, d_keep = d_val.index_select(2, order), d_keep.index_select(1, order)
-            if d_row is not None:
-                d_row = d_row.view(S, n, -1).index_select(1, order).contiguous().view(-1)
-        # the box records: the selection the bill report has (revs_bill_study, no baseline: base = -1), once a quantity
-        rec = BILL_DTYPE.itemsize
-        d_sum = torch.empty(4, S, 2 * rec, **u8)
-        d_pool = torch.empty(4, G, 2 * rec, **u8) if G else None
-        sel = torch.empty(int(lb.revs_bill_study_scratch(S, n)) // 8, dtype=torch.float64, device=dev)
-        h_base, h_group = np.full(S, -1, np.int32), np.ascontiguousarray(gid, np.int32)
-        for q in range(4):
-            check(lb.revs_bill_study(S, n, ptr(d_val[q]), h_base.ctypes.data, ptr(d_keep), ptr(d_index),
-                                     h_group.ctypes.data if G else None, G, None, ptr(d_sum[q]),
-                                     ptr(d_pool[q]) if G else None, ptr(sel), st), "revs_bill_study")
-        box = d_sum.cpu().numpy().reshape(-1).view(BILL_DTYPE).reshape(4, S, 2)[:, :, 0]
-        pool = d_pool.cpu().numpy().reshape(-1).view(BILL_DTYPE).reshape(4, G, 2)[:, :, 0] if G \
-            else np.zeros((4, 0), BILL_DTYPE)
+        d_val, d_keep, d_row = rr.reorder(order, d_val, d_keep, d_row)
+        box, pool = rr.box_records(lb, st, d_val, d_keep, d_index, gid, G)
         slot = d_slot.cpu().numpy().view(CHARGE_SLOT_DTYPE).reshape(S, T)
         day = d_day.cpu().numpy().view(CHARGE_DAY_DTYPE).reshape(S)
         hist = d_hist.cpu().numpy()
         row = d_row.cpu().numpy().view(CHARGE_ROW_DTYPE).reshape(S, n) if rows is True else None
-    pslot = np.zeros((G, T), POOLED_SLOT_DTYPE)
-    phist = np.zeros((G, 3, T + 1), np.int64)
-    for g in range(G):
-        m = gid == g
-        for k in POOLED_SLOT_DTYPE.names:
-            pslot[k][g] = slot[k][m].astype(np.int64).sum(0)
-        phist[g] = hist[m].astype(np.int64).sum(0)
+    pslot, phist = rr.pooled_counts(slot, hist, gid, G, POOLED_SLOT_DTYPE)
     return ChargingReport(row, slot, day, hist, *(box[q].copy() for q in range(4)), *(pool[q].copy() for q in range(4)),
                           pslot, phist, gid.astype(np.int64), int(G), on_frac, short_tol,
                           d_row if rows == "device" else None)
@@ -196,21 +134,8 @@ def charging_report(p, records, tariff=None, groups=None, on_frac=0.0, short_tol
                     device="cuda:0") -> ChargingReport:
     """charging_report_device for charger power held on the host: p (S, n, T) -- or (n, T) for one schedule -- and
     records HOME_DTYPE (S, n) -- or (n,) -- uploaded once, as float32 in the layout (n, S, T) with the records [n][S]."""
-    a = np.asarray(p)
-    records = np.asarray(records)
-    if a.ndim == 2:
-        a = a[None]
-    if records.ndim == 1:
-        records = records[None]
-    if a.ndim != 3 or a.size == 0:
-        raise ValueError(f"charging report: p must be (residences, slots) or (scenarios, residences, slots), got {a.shape}")
-    S, n, T = a.shape
-    if records.dtype != HOME_DTYPE or records.shape != (S, n):
-        raise ValueError(f"charging report: records must be HOME_DTYPE (scenarios, residences) = {(S, n)}, got "
-                         f"{records.dtype} {records.shape}")
+    S, n, T, h, hr = rr.host_rows(WHO, p, records)
     check_charge_args(S, n, T, None if isinstance(tariff, torch.Tensor) else tariff, groups, on_frac, short_tol)
-    h = np.ascontiguousarray(a.transpose(1, 0, 2), np.float32)
-    hr = np.ascontiguousarray(records.T).view(np.uint8).reshape(-1)
     from .engine import _dev_check
     dev = _dev_check(device)
     with torch.cuda.device(dev):
@@ -237,32 +162,15 @@ class ChargingMixin:
         device before they are summarised, so they are bit for bit what charging_report() gives on result()'s S); the
         slots' power and the day's energy and cost are sums in the ENGINE's order: within the summation bound of those.
         Nothing is uploaded, nothing but records is read back; the run's state is read, never written."""
-        shape = self._rule_shape()
-        n, T = shape[0], shape[-1]
-        S = shape[1] if len(shape) == 3 else 1
-        if isinstance(profile, str) and profile not in baselines.POLICIES:
-            raise ValueError(f"charging report: profile must be None, one of {sorted(baselines.POLICIES)} or a tensor on "
-                             f"the device, got {profile!r}")
+        S, n, T = rr.engine_sizes(WHO, self, profile)
+        charger = self.mode if charger is None else charger
         if isinstance(profile, str):
-            baselines.rule_args(profile, fill, self.mode if charger is None else charger)
+            baselines.rule_args(profile, fill, charger)
         host_tariff = None if isinstance(tariff, str) or isinstance(tariff, torch.Tensor) else tariff
         if isinstance(tariff, str) and tariff != "engine":
             raise ValueError(f'charging report: tariff must be "engine", None or one price per slot, got {tariff!r}')
         check_charge_args(S, n, T, host_tariff, groups, on_frac, short_tol)              # (before any launch)
-        if profile is None:
-            if self._sc_iteration != self.iteration:
-                raise RuntimeError("charging report: the last iteration did not write the charger power (run_steps() and "
-                                   "step(write_sc=False) leave it out): take one step(), or pass a profile")
-            p = self.S.view(shape)
-        elif isinstance(profile, str):
-            p = baselines.rule_schedule_device(self.homes, self.load.view(self.sweep_n, self.sweep_T), profile, fill,
-                                               self.mode if charger is None else charger, want="p",
-                                               stream=self.stream)[0].view(shape)
-        else:
-            p = profile
-            if not isinstance(p, torch.Tensor) or tuple(p.shape) != tuple(shape) or p.device != self.S.device:
-                raise ValueError(f"charging report: a power tensor must be {tuple(shape)} on {self.S.device}, the engine's "
-                                 f"residence order")
+        p = rr.engine_power(WHO, self, profile, fill, charger)
         if isinstance(tariff, str):
             assert self.cost.numel() == T
             tariff = self.cost.double()

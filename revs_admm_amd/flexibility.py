@@ -11,10 +11,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, baselines
-from ._lib import BILL_DTYPE, FLEX_DAY_DTYPE, FLEX_ROW_DTYPE, FLEX_SLOT_DTYPE, HOME_DTYPE, check, ptr
-from .charging import _check_tensor, check_charge_args
+from . import _lib, baselines, row_reports as rr
+from ._lib import FLEX_DAY_DTYPE, FLEX_ROW_DTYPE, FLEX_SLOT_DTYPE, check, ptr
 
+WHO = "flexibility report"
 QUANTITIES = ("up_energy", "down_energy", "slack", "laxity")
 POOLED_SLOT_DTYPE = np.dtype([(k, "<i8") for k in ("n_plugged", "n_up", "n_down")])
 
@@ -61,6 +61,11 @@ class FlexReport:
         return self.slot["down"].copy()
 
 
+def _check_args(S, n, T, groups, on_frac, short_tol, index=None):
+    rr.check_sizes(WHO, S, n, T)
+    return rr.check_row_args(WHO, S, n, groups, on_frac, short_tol, index)
+
+
 def flexibility_report_device(p, homes, integral, node_ptr=None, index=None, groups=None, on_frac=0.0, short_tol=1e-6,
                               rows=True, nodes=True, order=None, lib=None, stream=None) -> FlexReport:
     """The report of charger power that lies on the device: p a float32 tensor (n, S, T) or (n, T) whose slots are
@@ -71,20 +76,10 @@ def flexibility_report_device(p, homes, integral, node_ptr=None, index=None, gro
     node_ptr  None, or an int64 tensor (m + 1,) on the device: the CSR offsets of the rows sorted by node.  With it and
               nodes=True / "device" the node arrays are reported.
     index, groups, on_frac, short_tol, rows, order: as in charging_report_device."""
-    p = _check_tensor(p)
+    p = rr.check_tensor(WHO, "power", p)
     n, S, T = p.shape
-    _, gid, G, on_frac, short_tol, index = check_charge_args(S, n, T, None, groups, on_frac, short_tol, index)
-    if rows not in (True, False, "device"):
-        raise ValueError(f'flexibility report: rows must be True, False or "device", got {rows!r}')
-    if nodes not in (True, False, "device"):
-        raise ValueError(f'flexibility report: nodes must be True, False or "device", got {nodes!r}')
-    dev = p.device
-    if dev.type != "cuda":
-        raise ValueError(f"flexibility report: the power lies on {dev}; the report runs on the GPU")
-    if not isinstance(homes, torch.Tensor) or homes.dtype != torch.uint8 or homes.numel() != n * S * HOME_DTYPE.itemsize \
-            or not homes.is_contiguous() or homes.device != dev:
-        raise ValueError(f"flexibility report: homes must hold {n * S} records of {HOME_DTYPE.itemsize} bytes (uint8, "
-                         f"contiguous) on {dev}")
+    gid, G, on_frac, short_tol, index = _check_args(S, n, T, groups, on_frac, short_tol, index)
+    dev = rr.check_on_device(WHO, p, homes, rows=rows, nodes=nodes)
     m = 0
     if node_ptr is not None and nodes:
         if not isinstance(node_ptr, torch.Tensor) or node_ptr.dtype != torch.int64 or node_ptr.dim() != 1 \
@@ -93,8 +88,6 @@ def flexibility_report_device(p, homes, integral, node_ptr=None, index=None, gro
         m = node_ptr.numel() - 1
         if m * S * T >= 2 ** 31:
             raise ValueError(f"flexibility report: {m} nodes x {S} scenarios x {T} slots, 2^31 cells or more")
-    stride_i = p.stride(0) if n > 1 else S * max(p.stride(1), T)
-    stride_s = p.stride(1) if S > 1 else n * stride_i
     with torch.cuda.device(dev):
         lb = lib or _lib.load()
         st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
@@ -112,39 +105,18 @@ def flexibility_report_device(p, homes, integral, node_ptr=None, index=None, gro
         if nbytes <= 0:
             raise ValueError(f"flexibility report: no scratch size for S={S}, {n} residences, T={T}")
         d_scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        check(lb.revs_flex_report(S, n, T, ptr(p), stride_s, stride_i, ptr(homes), 1 if integral else 0, on_frac, short_tol,
+        check(lb.revs_flex_report(S, n, T, ptr(p), *rr.strides(p), ptr(homes), 1 if integral else 0, on_frac, short_tol,
                                   ptr(node_ptr) if m else None, m, ptr(d_row), ptr(d_slot), ptr(d_day), ptr(d_hist),
                                   ptr(d_nup), ptr(d_ndn), ptr(d_val), ptr(d_keep), ptr(d_scratch), st), "revs_flex_report")
-        if order is not None:
-            d_val, d_keep = d_val.index_select(2, order), d_keep.index_select(1, order)
-            if d_row is not None:
-                d_row = d_row.view(S, n, -1).index_select(1, order).contiguous().view(-1)
-        # the box records: the selection the bill report has (revs_bill_study, no baseline: base = -1), once a quantity
-        rec = BILL_DTYPE.itemsize
-        d_sum = torch.empty(4, S, 2 * rec, **u8)
-        d_pool = torch.empty(4, G, 2 * rec, **u8) if G else None
-        sel = torch.empty(int(lb.revs_bill_study_scratch(S, n)) // 8, dtype=torch.float64, device=dev)
-        h_base, h_group = np.full(S, -1, np.int32), np.ascontiguousarray(gid, np.int32)
-        for q in range(4):
-            check(lb.revs_bill_study(S, n, ptr(d_val[q]), h_base.ctypes.data, ptr(d_keep), ptr(d_index),
-                                     h_group.ctypes.data if G else None, G, None, ptr(d_sum[q]),
-                                     ptr(d_pool[q]) if G else None, ptr(sel), st), "revs_bill_study")
-        box = d_sum.cpu().numpy().reshape(-1).view(BILL_DTYPE).reshape(4, S, 2)[:, :, 0]
-        pool = d_pool.cpu().numpy().reshape(-1).view(BILL_DTYPE).reshape(4, G, 2)[:, :, 0] if G \
-            else np.zeros((4, 0), BILL_DTYPE)
+        d_val, d_keep, d_row = rr.reorder(order, d_val, d_keep, d_row)
+        box, pool = rr.box_records(lb, st, d_val, d_keep, d_index, gid, G)
         slot = d_slot.cpu().numpy().view(FLEX_SLOT_DTYPE).reshape(S, T)
         day = d_day.cpu().numpy().view(FLEX_DAY_DTYPE).reshape(S)
         hist = d_hist.cpu().numpy()
         row = d_row.cpu().numpy().view(FLEX_ROW_DTYPE).reshape(S, n) if rows is True else None
         if m and nodes is True:
             d_nup, d_ndn = d_nup.cpu().numpy(), d_ndn.cpu().numpy()
-    pslot = np.zeros((G, T), POOLED_SLOT_DTYPE)
-    phist = np.zeros((G, 2, T + 1), np.int64)
-    for g in range(G):
-        member = gid == g
-        for k in POOLED_SLOT_DTYPE.names:
-            pslot[k][g] = slot[k][member].astype(np.int64).sum(0)
-        phist[g] = hist[member].astype(np.int64).sum(0)
+    pslot, phist = rr.pooled_counts(slot, hist, gid, G, POOLED_SLOT_DTYPE)
     return FlexReport(row, slot, day, hist, d_nup, d_ndn, *(box[q].copy() for q in range(4)),
                       *(pool[q].copy() for q in range(4)), pslot, phist, gid.astype(np.int64), int(G),
                       1 if integral else 0, on_frac, short_tol, d_row if rows == "device" else None)
@@ -155,25 +127,12 @@ def flexibility_report(p, records, integral=0, node_ptr=None, groups=None, on_fr
     """flexibility_report_device for charger power held on the host: p (S, n, T) -- or (n, T) for one schedule -- and
     records HOME_DTYPE (S, n) -- or (n,) -- uploaded once, as float32 in the layout (n, S, T) with the records [n][S];
     node_ptr: None or (m + 1,) integers, the CSR offsets of the rows sorted by node."""
-    a = np.asarray(p)
-    records = np.asarray(records)
-    if a.ndim == 2:
-        a = a[None]
-    if records.ndim == 1:
-        records = records[None]
-    if a.ndim != 3 or a.size == 0:
-        raise ValueError(f"flexibility report: p must be (residences, slots) or (scenarios, residences, slots), got {a.shape}")
-    S, n, T = a.shape
-    if records.dtype != HOME_DTYPE or records.shape != (S, n):
-        raise ValueError(f"flexibility report: records must be HOME_DTYPE (scenarios, residences) = {(S, n)}, got "
-                         f"{records.dtype} {records.shape}")
-    check_charge_args(S, n, T, None, groups, on_frac, short_tol)
+    S, n, T, h, hr = rr.host_rows(WHO, p, records)
+    _check_args(S, n, T, groups, on_frac, short_tol)
     if node_ptr is not None:
         node_ptr = np.ascontiguousarray(node_ptr, np.int64)
         if node_ptr.ndim != 1 or len(node_ptr) < 2 or node_ptr[0] != 0 or node_ptr[-1] != n or (np.diff(node_ptr) < 0).any():
             raise ValueError(f"flexibility report: node_ptr must ascend from 0 to {n} residences")
-    h = np.ascontiguousarray(a.transpose(1, 0, 2), np.float32)
-    hr = np.ascontiguousarray(records.T).view(np.uint8).reshape(-1)
     from .engine import _dev_check
     dev = _dev_check(device)
     with torch.cuda.device(dev):
@@ -199,28 +158,11 @@ class FlexMixin:
         Row records, indices and the box records are in the caller's residence order; the slot and day sums are sums in
         the ENGINE's order: within the summation bound of those.  Nothing is uploaded, nothing but records is read
         back; the run's state is read, never written."""
-        shape = self._rule_shape()
-        n, T = shape[0], shape[-1]
-        S = shape[1] if len(shape) == 3 else 1
-        if isinstance(profile, str) and profile not in baselines.POLICIES:
-            raise ValueError(f"flexibility report: profile must be None, one of {sorted(baselines.POLICIES)} or a tensor "
-                             f"on the device, got {profile!r}")
+        S, n, T = rr.engine_sizes(WHO, self, profile)
         mode = self.mode if charger is None else charger
         integral = baselines.rule_args(profile if isinstance(profile, str) else "uncontrolled", fill, mode)[2]
-        check_charge_args(S, n, T, None, groups, on_frac, short_tol)                     # (before any launch)
-        if profile is None:
-            if self._sc_iteration != self.iteration:
-                raise RuntimeError("flexibility report: the last iteration did not write the charger power (run_steps() "
-                                   "and step(write_sc=False) leave it out): take one step(), or pass a profile")
-            p = self.S.view(shape)
-        elif isinstance(profile, str):
-            p = baselines.rule_schedule_device(self.homes, self.load.view(self.sweep_n, self.sweep_T), profile, fill, mode,
-                                               want="p", stream=self.stream)[0].view(shape)
-        else:
-            p = profile
-            if not isinstance(p, torch.Tensor) or tuple(p.shape) != tuple(shape) or p.device != self.S.device:
-                raise ValueError(f"flexibility report: a power tensor must be {tuple(shape)} on {self.S.device}, the "
-                                 f"engine's residence order")
+        _check_args(S, n, T, groups, on_frac, short_tol)                                 # (before any launch)
+        p = rr.engine_power(WHO, self, profile, fill, mode)
         inv = torch.from_numpy(np.asarray(self.inv_perm, np.int64)).to(self.S.device)
         return flexibility_report_device(p, self.homes.view(-1), integral, self.node_ptr if nodes else None, None, groups,
                                          on_frac, short_tol, rows, nodes, order=inv, lib=self.lib, stream=self.stream)

@@ -11,9 +11,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib, baselines
+from . import _lib, baselines, row_reports as rr
 from ._lib import BILL_DTYPE, PROFILE_DAY_DTYPE, check, ptr
-from .bills import check_groups
+
+WHO = "load profile"
 
 
 @dataclass
@@ -66,18 +67,11 @@ def check_profile_args(S, n, T, classes, n_classes, groups, above, index=None, n
     names, group ids int32 (S,), G, above float, index int32 (n,) or None).  classes: None (one set: everybody), or
     integers (S, n) -- (n,) with S == 1 -- where 0 .. C-1 is a class and anything else (negative, >= C) leaves the
     residence out; n_classes: C, default 1 + the largest entry in 0 .. PROFILE_MAX_CLASSES - 1."""
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"load profile: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    if not 1 <= T <= _lib.MAX_T:
-        raise ValueError(f"load profile: {T} slots outside 1..{_lib.MAX_T}")
-    if n < 1 or S * n >= 2 ** 31:
-        raise ValueError(f"load profile: {S} scenarios x {n} residences outside 1..2^31 - 1 rows")
+    rr.check_sizes(WHO, S, n, T)
     above = float(above)
     if math.isnan(above):
         raise ValueError("load profile: above is a NaN")
-    gid, G = check_groups(S, groups)
-    if G > S:
-        raise ValueError(f"load profile: group ids up to {G - 1} for {S} scenarios")
+    gid, G = rr.check_pools(WHO, S, groups)
     cls, C = None, 0
     if classes is not None:
         a = np.asarray(classes)
@@ -99,24 +93,7 @@ def check_profile_args(S, n, T, classes, n_classes, groups, above, index=None, n
     names = tuple(names)
     if len(names) != C:
         raise ValueError(f"load profile: {len(names)} names for {C} classes")
-    if index is not None:
-        index = np.asarray(index)
-        if index.shape != (n,) or not np.issubdtype(index.dtype, np.integer) or index.min() < 0 \
-                or index.max() >= 2 ** 31 - 1:
-            raise ValueError(f"load profile: index must be {n} integers in 0..2^31 - 2")
-        index = np.ascontiguousarray(index, np.int32)
-    return cls, C, names + ("all",), gid, G, above, index
-
-
-def _check_tensor(g):
-    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or g.dim() not in (2, 3):
-        raise ValueError("load profile: the profile must be a float32 tensor (residences, slots) or (residences, "
-                         "scenarios, slots)")
-    if g.dim() == 2:
-        g = g.unsqueeze(1)
-    if g.numel() == 0 or g.stride(2) != 1:
-        raise ValueError(f"load profile: the profile is empty or its slots are not contiguous, {tuple(g.shape)}")
-    return g
+    return cls, C, names + ("all",), gid, G, above, rr.check_index(WHO, n, index)
 
 
 def load_profile_report_device(g, classes=None, n_classes=None, names=None, index=None, groups=None, above=0.0, lib=None,
@@ -126,7 +103,7 @@ def load_profile_report_device(g, classes=None, n_classes=None, names=None, inde
     returns.  classes: None, integers (S, n) on the host, or a uint8 tensor (S, n) on the device (then n_classes is
     needed; a byte >= n_classes leaves the residence out).  index: the index worst_index reports for row i.  Nothing but
     the class bytes and the index is uploaded; nothing but the records is read back."""
-    g = _check_tensor(g)
+    g = rr.check_tensor(WHO, "profile", g)
     n, S, T = g.shape
     on_dev = isinstance(classes, torch.Tensor)
     if on_dev:
@@ -145,8 +122,6 @@ def load_profile_report_device(g, classes=None, n_classes=None, names=None, inde
     dev = g.device
     if dev.type != "cuda":
         raise ValueError(f"load profile: the profile lies on {dev}; the report runs on the GPU")
-    stride_i = g.stride(0) if n > 1 else S * max(g.stride(1), T)
-    stride_s = g.stride(1) if S > 1 else n * stride_i
     Q = C + 1
     with torch.cuda.device(dev):
         lb = lib or _lib.load()
@@ -164,7 +139,7 @@ def load_profile_report_device(g, classes=None, n_classes=None, names=None, inde
             raise ValueError(f"load profile: no scratch size for S={S}, {n} residences, T={T}, {C} classes, {G} groups")
         d_scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         h_group = np.ascontiguousarray(gid, np.int32)
-        check(lb.revs_load_profile(S, n, T, ptr(g), stride_s, stride_i, ptr(d_cls), C, ptr(d_index),
+        check(lb.revs_load_profile(S, n, T, ptr(g), *rr.strides(g), ptr(d_cls), C, ptr(d_index),
                                    h_group.ctypes.data if G else None, G, above, ptr(d_slot), ptr(d_peak), ptr(d_day),
                                    ptr(d_pslot), ptr(d_ppeak), ptr(d_scratch), st), "revs_load_profile")
         slot = d_slot.cpu().numpy().view(BILL_DTYPE).reshape(S, Q, T)
