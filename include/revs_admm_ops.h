@@ -1038,6 +1038,82 @@ int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_hos
                     revs_net_summary_t *summary_out, revs_loss_slot_t *slot_out, revs_loss_line_day_t *line_day_out,
                     revs_loss_day_t *day_out, void *scratch, void *stream);
 
+/* ---- attribution report: who causes the watched node's voltage drop (csrc/attribution_kernels.hip) ------
+ * drop = R g and R[j][i] = wc[lca(i, j)] (revs_headroom_aux_t), so node i contributes wc[lca(i, j*)] g[i] to the drop at a
+ * watched node j*.  Positions j = 0 .. tree->n - 1 are feeder_tree's preorder positions; a is an ancestor-or-self of j iff
+ * a <= j < end[a] (the pack's field).  Per (scenario s, slot t), every operation an IEEE double operation rounded on its
+ * own (no fused multiply-add), with inj[i] the gathered node sum of node_g (+0.0 at a position without a row), ev[i] the
+ * same gather of node_ev (double[S][m][T], the EV part of the injections; all +0.0 when node_ev is NULL) and drop the
+ * bits of revs_net_report's scans:
+ *   watch j*     watch_pos >= 0: that position in every slot.  watch_pos = -1: among the positions with limit_mask != 0
+ *                (NULL: every position with a row) and a caller-side index, the one of largest drop, ties to the lowest
+ *                caller-side index.  No candidate: watch = -1, every output of the slot is +0.0 and every count 0 (the
+ *                summary's included).
+ *   sens[i]      = wc[lca(i, j*)] = R[j*][i]; +0.0 when i and j* share no ancestor.  A selection: no rounding.  (wc must
+ *                not decrease down a path: w >= 0.)
+ *   contrib[i]   = sens[i] inj[i],  ev_contrib[i] = sens[i] ev[i]
+ *   excess       = max(0, drop[j*] - drop_max)
+ *   relief[i]    = excess / sens[i] where sens[i] > 0 (+inf where sens[i] = 0 and excess > 0; 0 when excess = 0): the cut
+ *                at node i alone that brings j* back to the limit.  Not an output: it enters n_can.
+ * Sums over positions: each the root of ONE fixed binary tree exactly as the loss report's (values by position, +0.0 at
+ * padding, padded to the next power of two, x[i] = x[2i] + x[2i + 1]):
+ *   total = sum of contrib (NOT forced to equal drop[j*]: they differ by rounding), ev_total = sum of ev_contrib,
+ *   class_total[k] = sum of contrib over the positions with class_of_pos[j] == k (uint8 per position), k < C <= 4.
+ * Counts over the positions with out_mask != 0 (NULL: all), a caller-side index and sens > 0:
+ *   n_reach  how many there are;  n_big  those with contrib > frac drop[j*] (the product rounded once);
+ *   n_can    those with excess > 0 and relief[i] <= ev[i].
+ * Bad slot: a non-finite injection (node_g or node_ev) at a row of the tree.  Then every double of the slot is a NaN
+ * (sens, contrib, ev_contrib, the slot record), watch = -1, n_bad = 1, the other counts 0, the summary has count 0 and
+ * n_nan = the nodes summarised; drop_out is what the scans give.  One flag for the workgroup; nothing traps.
+ * Outputs, any may be NULL, not all:
+ *   sens_out, contrib_out, ev_contrib_out, drop_out   double[S][n_out][T] in the caller's node order (node_of_pos, n_out
+ *                as revs_net_report's)
+ *   slot_out     revs_attr_slot_t[S][T]; top_value / top_index = the eight nodes counted in n_reach of largest
+ *                contribution, descending, ties to the lowest caller-side index, NaNs left out, unused entries NaN / -1
+ *   summary_out  revs_net_summary_t[S][T]: the box-plot record of contrib over the n_reach nodes (box_select64 and the rules
+ *                of boxplot.h); worst_value / worst_index = the largest contribution and the lowest caller-side index that
+ *                attains it; n_violations = n_big; reserved[0] = the positions with out_mask and a caller-side index whose
+ *                sens is 0
+ *   day_out      revs_attr_day_t[S][n_out]: sum / ev_sum = the node's contrib / ev_contrib summed from +0.0 in ascending
+ *                slot order over the slots with excess > 0; peak / peak_slot = its largest contrib over the slots that are
+ *                not bad and the earliest such slot (NaN / -1: every slot is bad); n_big = the slots in which it counted
+ *                in n_big
+ * Enqueues only (up to three launches on `stream`): capturable, no allocation, no synchronisation.  REVS_EINVAL before any
+ * launch: every case of revs_net_headroom's list that applies (S, T, m, node_g, the tree, n_out, the aux struct, drop_max
+ * not finite, every output NULL); watch_pos outside -1..tree->n - 1; frac not finite or < 0; C outside 0..4; class_of_pos
+ * NULL with C > 0; ev_contrib_out without node_ev; slot_out, summary_out or day_out without a 16-byte aligned scratch of
+ * revs_net_attribution_scratch bytes (17 S T tree_n: contrib and ev_contrib by position and one flag byte per cell,
+ * + 192 S T: the slot records; 0 for a bad size). */
+typedef struct {
+    double drop_watch;                /* drop[j*] */
+    double excess;                    /* max(0, drop_watch - drop_max) */
+    double total;                     /* sum of contrib */
+    double ev_total;                  /* sum of ev_contrib */
+    double class_total[4];            /* sum of contrib per class; entries >= C are 0 */
+    double top_value[8];              /* the eight largest contributions, descending; NaN: unused */
+    int32_t top_index[8];             /* their caller-side indices; -1: unused */
+    int32_t watch;                    /* caller-side index of j*; -1 */
+    int32_t n_reach;
+    int32_t n_big;
+    int32_t n_can;
+    int32_t n_bad;                    /* 1: a bad slot, every double above a NaN */
+    int32_t reserved[3];
+} revs_attr_slot_t;                   /* 192 bytes */
+typedef struct {
+    double sum;                       /* sum over the slots with excess > 0 of contrib */
+    double ev_sum;                    /* ... of ev_contrib */
+    double peak;                      /* the largest contrib of the day */
+    int32_t peak_slot;                /* its earliest slot; -1 */
+    int32_t n_big;                    /* slots in which the node counted in n_big */
+} revs_attr_day_t;                    /* 32 bytes */
+int64_t revs_net_attribution_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_attribution(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const revs_headroom_aux_t *aux_host,
+                         const double *node_g, const double *node_ev, const uint8_t *limit_mask, const uint8_t *out_mask,
+                         const uint8_t *class_of_pos, int32_t C, const int32_t *node_of_pos, int32_t n_out,
+                         int32_t watch_pos, double drop_max, double frac, double *sens_out, double *contrib_out,
+                         double *ev_contrib_out, double *drop_out, revs_attr_slot_t *slot_out,
+                         revs_net_summary_t *summary_out, revs_attr_day_t *day_out, void *scratch, void *stream);
+
 /* ---- transformer report: loading, hot-spot and loss of life of the service transformers (csrc/transformer_kernels.hip,
  * DESIGN.md 3.17) --------------------------------------------------------------------------------------------------------
  * K transformers, each serving a list of rows of the node sums node_g (double[S][m][T], revs_net_node_sums' layout):

@@ -10,6 +10,8 @@
                    chargers on per slot, state of charge at departure and cost per EV
     headroom       AdmmEngine.headroom_report: spare charger power per node and slot, and what limits it
     losses         AdmmEngine.loss_report: line losses, marginal loss per node, the day's lost energy and its cost
+    attribution    AdmmEngine.attribution_report: which nodes' load causes the worst node's voltage drop, and the EVs'
+                   part of it: AttributionReport, attribution_report_device
     transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
     flexibility    how much charging can still be moved: FlexReport, flexibility_report / flexibility_report_device -- up and
                    down reserve per EV, node and slot, the slot a car is ready at and the slack it leaves

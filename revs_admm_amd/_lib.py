@@ -230,6 +230,16 @@ LOSS_DAY_DTYPE = np.dtype([("energy", "<f8"), ("delivered", "<f8"), ("class_ener
 assert LOSS_DAY_DTYPE.itemsize == 192
 LOSS_MAX_CLASSES = 4
 
+# numpy mirrors of revs_attr_slot_t and revs_attr_day_t (include/revs_admm_ops.h)
+ATTR_SLOT_DTYPE = np.dtype([("drop_watch", "<f8"), ("excess", "<f8"), ("total", "<f8"), ("ev_total", "<f8"),
+                            ("class_total", "<f8", (4,)), ("top_value", "<f8", (8,)), ("top_index", "<i4", (8,)),
+                            ("watch", "<i4"), ("n_reach", "<i4"), ("n_big", "<i4"), ("n_can", "<i4"), ("n_bad", "<i4"),
+                            ("reserved", "<i4", (3,))])
+assert ATTR_SLOT_DTYPE.itemsize == 192
+ATTR_DAY_DTYPE = np.dtype([("sum", "<f8"), ("ev_sum", "<f8"), ("peak", "<f8"), ("peak_slot", "<i4"), ("n_big", "<i4")])
+assert ATTR_DAY_DTYPE.itemsize == 32
+ATTR_MAX_CLASSES = 4
+
 # numpy mirrors of revs_xf_day_t and revs_xf_fleet_t (include/revs_admm_ops.h)
 XF_DAY_DTYPE = np.dtype([("peak_ratio", "<f8"), ("peak_hot", "<f8"), ("energy_kwh", "<f8"), ("age_hours", "<f8"),
                          ("lol_percent", "<f8"), ("feqa", "<f8"), ("peak_ratio_slot", "<i4"), ("peak_hot_slot", "<i4"),
@@ -395,6 +405,9 @@ SIGNATURES = {
     "revs_net_losses_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_losses": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _i32, _p, _i32, _f64, _f64, _f64, _p,
                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_attribution_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_attribution": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _p, _p, _i32,
+                                       _p, _i32, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
                                  _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

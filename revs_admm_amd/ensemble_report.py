@@ -139,6 +139,20 @@ class EnsembleReportMixin:
         return headroom.native_headroom_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, need,
                                                rating, limit_nodes, nodes, self.vset, self.vlow, arrays, out)
 
+    def attribution_reports(self, watch=None, limit_nodes=None, nodes=None, classes=None, frac=0.01, arrays=True,
+                            profile=None) -> list:
+        """AdmmEngine.attribution_report for every scenario -> S attribution.AttributionReports from two node-sum
+        launches and one revs_net_attribution over all S (scenario s: the bits of the single engine's report on it).
+        profile: the EV part, see node_sums (None: the schedules P_sch); the injections are LOAD + profile.  The run's
+        state is read, never written."""
+        from . import attribution
+        tree, tree_host, n_nodes = self._report_tree()
+        node_g = self.node_sums(profile, True)
+        node_ev = self.node_sums(profile, False)
+        return attribution.native_attribution_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g,
+                                                     node_ev, watch, limit_nodes, nodes, classes, self.vset, self.vlow,
+                                                     frac, arrays)
+
     def loss_reports(self, lines=None, nodes=None, classes=None, cost=None, slot_hours=None, loss_max=float("inf"),
                      arrays=True, profile=None, add_load=False, out=None) -> list:
         """AdmmEngine.loss_report for every scenario -> S losses.LossReports from one node-sum launch and one

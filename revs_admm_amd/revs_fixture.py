@@ -125,7 +125,7 @@ class REVS:
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              transformers=False, flexibility=False, **opt):
+              transformers=False, flexibility=False, attribution=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -196,7 +196,13 @@ class REVS:
         and slot how much charging could still be added or shed without the car leaving under target -- from the same
         buffer and records as charging=True, pooled by the report's groups, for the charger of opt mode (opt
         flexibility_on_frac, flexibility_short_tol: 0.0 and 1e-6 by default; the row records are read back with opt
-        arrays; no node arrays: those are AdmmEngine.flexibility_report's, over the engine's nodes)."""
+        arrays; no node arrays: those are AdmmEngine.flexibility_report's, over the engine's nodes).
+        attribution=True or a dict of attribution_report_device's options (watch, limit_nodes, classes, frac):
+        StudyReport.attribution, every scenario's attribution.AttributionReport -- per slot the node of largest drop
+        among those that carry residences, per node its contribution to that drop and the EVs' part of it -- from the
+        report's own rows; the EV part is those rows minus the base load's, formed once in float64; counted and
+        summarised over `community`, against opt vmin; one launch for all scenarios on either path (its arrays are read
+        back with opt arrays).  False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -357,7 +363,18 @@ class REVS:
                 kw["rated_kva"] = size_ratings(base.max(axis=1), pf=kw.get("pf", 0.95))
             return transformer_report_device(node_g, kw.pop("xf_of"), kw.pop("rated_kva"),
                                              arrays=opt.get("arrays", False), **kw)
+
+        def attribution_reports(node_g):
+            import torch
+            from .attribution import attribution_report_device
+            base = torch.from_numpy(np.array([all_homes[h] for h in res], np.float64)).to(node_g.device)
+            kw = dict(nodes=[pos[h] for h in community])
+            kw.update(attribution if isinstance(attribution, dict) else {})
+            return attribution_report_device(node_g, (node_g - base[None]).contiguous(), feeder=(parent, edge_r, cons_of),
+                                             vset=opt.get("report_vset", 1.0), vmin=opt.get("vmin", 0.95),
+                                             arrays=opt.get("arrays", False), **kw)
         want_xf = transformers is True or isinstance(transformers, dict)
+        want_attr = attribution is True or isinstance(attribution, dict)
         if device_report:
             import torch
             # (rows are residences here: the ensembles' node sums have one residence per row, like the profiles)
@@ -388,6 +405,8 @@ class REVS:
                 rep.transformers = transformer_reports(buf)
             if flexibility:
                 rep.flexibility = flexibility_report()
+            if want_attr:
+                rep.attribution = attribution_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -415,6 +434,9 @@ class REVS:
             rep.transformers = transformer_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         if flexibility:
             rep.flexibility = flexibility_report()
+        if want_attr:
+            import torch
+            rep.attribution = attribution_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -84,7 +84,8 @@ class StudyReport:
     EV homes.  charging: the charging.ChargingReport of REVS.study(charging=True) over the study's scenarios, else
     None.  headroom / losses / transformers: every scenario's headroom.HeadroomReport / losses.LossReport /
     transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None.  flexibility: the
-    flexibility.FlexReport of REVS.study(flexibility=True) over the study's scenarios, else None."""
+    flexibility.FlexReport of REVS.study(flexibility=True) over the study's scenarios, else None.  attribution: every
+    scenario's attribution.AttributionReport of REVS.study(attribution=True), else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -109,6 +110,7 @@ class StudyReport:
     losses: list | None = None
     transformers: list | None = None
     flexibility: object | None = None
+    attribution: list | None = None
 
     @property
     def n_groups(self):
