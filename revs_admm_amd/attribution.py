@@ -11,10 +11,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tree_reports
 from ._lib import ATTR_DAY_DTYPE, ATTR_SLOT_DTYPE, check, ptr
 from .headroom import aux_on_device, position_mask
-from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays, tree_on_device
+from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays
 
 
 @dataclass
@@ -71,12 +71,7 @@ def class_array(dev, tree_host, n_nodes, classes):
     cl = np.asarray(classes)
     if cl.shape != (n_nodes,):
         raise ValueError(f"attribution report: classes must have one entry per tree node ({n_nodes}), got {cl.shape}")
-    cl = np.where((cl >= 0) & (cl < _lib.ATTR_MAX_CLASSES), cl, 255).astype(np.uint8)
-    order = np.asarray(tree_host["order"], np.int64)
-    real = order < n_nodes
-    by_pos = np.where(real, cl[np.where(real, order, 0)], 255).astype(np.uint8)
-    used = cl[cl < 255]
-    return torch.from_numpy(np.ascontiguousarray(by_pos)).to(dev), (int(used.max()) + 1 if used.size else 0)
+    return tree_reports.position_classes(dev, tree_host, n_nodes, cl, _lib.ATTR_MAX_CLASSES)
 
 
 def native_attribution_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, node_ev=None, watch=None,
@@ -111,21 +106,19 @@ def native_attribution_device(lib, dev, stream, tree, tree_host, n_nodes, node_g
         d_sens, d_con, d_drop = (torch.empty(S, n, T, **f64) for _ in range(3))
         if node_ev is not None:
             d_evc = torch.empty(S, n, T, **f64)
-    d_slot = torch.zeros(S * T * ATTR_SLOT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_sum = torch.zeros(S * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_day = torch.zeros(S * n * ATTR_DAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    nbytes = int(lib.revs_net_attribution_scratch(S, T, tree_host["n"]))
-    if nbytes <= 0:
-        raise ValueError(f"attribution report: no scratch size for S={S}, T={T}, tree of {tree_host['n']}")
-    d_scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+    d_slot = tree_reports.record_buffer(dev, ATTR_SLOT_DTYPE, S * T)
+    d_sum = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * T)
+    d_day = tree_reports.record_buffer(dev, ATTR_DAY_DTYPE, S * n)
+    d_scratch = tree_reports.scratch("attribution report", lib.revs_net_attribution_scratch(S, T, tree_host["n"]),
+                                     f"S={S}, T={T}, tree of {tree_host['n']}", dev)
     drop_max = vset * vset - vmin * vmin
     check(lib.revs_net_attribution(S, M, T, C.byref(tree), C.byref(aux), ptr(node_g), ptr(node_ev), ptr(d_limit),
                                    ptr(d_outm), ptr(d_cls), n_cls, ptr(d_nop), n, watch_pos, drop_max, frac, ptr(d_sens),
                                    ptr(d_con), ptr(d_evc), ptr(d_drop), ptr(d_slot), ptr(d_sum), ptr(d_day),
                                    ptr(d_scratch), stream), "revs_net_attribution")
-    slot = d_slot.cpu().numpy().view(ATTR_SLOT_DTYPE).reshape(S, T)
-    rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, T)
-    day = d_day.cpu().numpy().view(ATTR_DAY_DTYPE).reshape(S, n)
+    slot = tree_reports.records(d_slot, ATTR_SLOT_DTYPE, S, T)
+    rec = tree_reports.records(d_sum, SUMMARY_DTYPE, S, T)
+    day = tree_reports.records(d_day, ATTR_DAY_DTYPE, S, n)
     host = [None if d is None else d.cpu().numpy() for d in (d_sens, d_con, d_evc, d_drop)]
     return [AttributionReport(*[None if a is None else a[s] for a in host], slot[s].copy(), rec[s].copy(), day[s].copy(),
                               frac, vset, vmin) for s in range(S)]
@@ -147,51 +140,20 @@ def attribution_report_device(node_g, node_ev=None, feeder=None, tree=None, watc
     vset, vmin    the limit is a drop R p of vset^2 - vmin^2, formed here in double
     frac          n_big counts the nodes whose contribution exceeds frac x the watched node's drop
     arrays        False: the records only"""
-    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() not in (2, 3) \
-            or not node_g.is_contiguous():
-        raise ValueError("attribution report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
-    if (feeder is None) == (tree is None):
-        raise ValueError("attribution report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
-    single = node_g.dim() == 2
-    g3 = node_g[None] if single else node_g
-    ev3 = node_ev
-    if isinstance(node_ev, torch.Tensor) and single and node_ev.dim() == 2:
-        ev3 = node_ev[None]
-    if not 1 <= g3.shape[0] <= _lib.STUDY_MAX_S:
-        raise ValueError(f"attribution report: {g3.shape[0]} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    dev = node_g.device
+    def native(*on):                # ((M, T) node sums come with (M, T) EV parts)
+        ev3 = node_ev[None] if isinstance(node_ev, torch.Tensor) and node_g.dim() == 2 and node_ev.dim() == 2 else node_ev
+        return native_attribution_device(*on, ev3, watch, limit_nodes, nodes, classes, vset, vmin, frac, arrays)
 
-    def run():
-        if tree is None:
-            th, tr, _keep = tree_on_device(dev, *feeder, g3.shape[1])
-            n_nodes = len(feeder[0])
-        else:
-            tr, th, n_nodes = tree
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
-        reps = native_attribution_device(lib or _lib.load(), dev, st, tr, th, n_nodes, g3, ev3, watch, limit_nodes, nodes,
-                                         classes, vset, vmin, frac, arrays)
-        return reps[0] if single else reps
-
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.device_report("attribution report", node_g, feeder, tree, native, lib, stream)
 
 
 def report_for_tree(parent, edge_r, cons_of, node_p, node_ev=None, watch=None, limit_nodes=None, nodes=None, classes=None,
                     vset=1.0, vmin=0.95, frac=0.01, arrays=True, device="cuda:0"):
     """The attribution report of node injections held on the host: node_p (and node_ev, its EV part) (M, T) or (S, M, T),
     row cons_of[i] injected at tree node i -> one AttributionReport or a list of S."""
-    from .engine import _dev_check
-    _lib.load()
-    dev = _dev_check(device)
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
-    with torch.cuda.device(dev):
-        return attribution_report_device(up(node_p), up(node_ev), feeder=(parent, edge_r, cons_of), watch=watch,
-                                         limit_nodes=limit_nodes, nodes=nodes, classes=classes, vset=vset, vmin=vmin,
-                                         frac=frac, arrays=arrays)
+    return tree_reports.host_report(device, (node_p, node_ev), lambda g, ev: attribution_report_device(
+        g, ev, feeder=(parent, edge_r, cons_of), watch=watch, limit_nodes=limit_nodes, nodes=nodes, classes=classes,
+        vset=vset, vmin=vmin, frac=frac, arrays=arrays))
 
 
 class AttributionMixin:

@@ -57,6 +57,12 @@ class BillReport:
         return slot[:, :, 0].copy()
 
 
+def check_scenarios(who, S):
+    """The bound on the scenarios of one call that every report shares; `who`: the report's name in front of the message."""
+    if not 1 <= S <= _lib.STUDY_MAX_S:
+        raise ValueError(f"{who}: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+
+
 def check_groups(S, groups):
     """-> (group ids int32 (S,), G)."""
     if groups is None:
@@ -70,8 +76,7 @@ def check_groups(S, groups):
 def check_bill_args(S, n, T, tariff, base, groups, keep):
     """The checks of a bill report, before the device is touched -> (tariff float64 (T,), base int32 (S,), group ids
     int32 (S,), G, keep uint8 (S, n) or None)."""
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"bill report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    check_scenarios("bill report", S)
     if not 1 <= T <= _lib.MAX_T:
         raise ValueError(f"bill report: {T} slots outside 1..{_lib.MAX_T}")
     if n < 1 or S * n >= 2 ** 31:

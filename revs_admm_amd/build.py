@@ -24,7 +24,8 @@ SOURCES = ["runtime.cpp", "plan_newton.cpp", "plan_fold.cpp", "plan_stream.cpp",
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "tuning.h"), os.path.join(CSRC, "select_body.h"),
            os.path.join(CSRC, "tree_body.h"), os.path.join(CSRC, "boxplot.h"), os.path.join(CSRC, "fixed_tree.h"),
            os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "rows_pass.h"),
-           os.path.join(ROOT, "include", "revs_admm.h"), os.path.join(ROOT, "include", "revs_admm_ops.h")]
+           os.path.join(CSRC, "net_scans.h"), os.path.join(ROOT, "include", "revs_admm.h"),
+           os.path.join(ROOT, "include", "revs_admm_ops.h")]
 
 
 def hipcc() -> str:

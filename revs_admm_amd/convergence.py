@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import BILL_DTYPE, CONV_RES_DTYPE, CONV_RUN_DTYPE, check, ptr
-from .bills import check_groups
+from .bills import check_groups, check_scenarios
 
 
 @dataclass
@@ -41,8 +41,7 @@ class ConvergenceReport:
 def check_conv_args(S, n, K, eps, patience, groups, keep, index=None):
     """The checks of a convergence report, before the device is touched -> (eps float, patience int, group ids int32
     (S,), G, keep uint8 (S, n) or None, index int32 (n,) or None)."""
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"convergence report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    check_scenarios("convergence report", S)
     if n < 1 or S * n >= 2 ** 31:
         raise ValueError(f"convergence report: {S} scenarios x {n} residences outside 1..2^31 - 1 columns")
     if K < 1:

@@ -9,9 +9,9 @@
 //                          per (scenario, position))
 //
 // One workgroup per (slot, scenario):
-//   1. the flow and the drop scans of the network report, from losses_kernels.hip's text (attr_flow_scan is its
-//      loss_flow_scan without the pair tree and with node_ev's finiteness test; attr_path_scan its loss_path_scan): the
-//      same bits;
+//   1. the flow and the drop scans of the network report in this file's own text (net_scans.h's pieces restated:
+//      attr_flow_scan is net_gather, with node_ev's test, and net_flow_scan; attr_path_scan its net_path_scan -- from
+//      the pieces the kernel was up to 1.5% slower on a 30-scenario grid): the same bits;
 //   2. the slot's one flag (a row's injection not finite: __syncthreads_or), the drops out, and the watched position:
 //      the arg-max of drop over the limit positions in (drop down, caller index up) order, lanes then wavefronts;
 //   3. sens[i] = wc[lca(i, j*)] without a walk.  The marked positions (a <= j* < end[a]) are j*'s root path and wc does
@@ -57,7 +57,7 @@ struct AttrArgs {
     uint8_t *flags;               // [S][T][n] by position, or NULL
 };
 
-constexpr int kAttrChunk = 8;      // positions whose side data are in flight at once (headroom_kernels.hip: kHeadChunk)
+constexpr int kAttrChunk = 8;      // positions whose side data are in flight at once (net_scans.h: kNetChunk)
 constexpr int kAttrSums = 6;       // total, ev_total, class_total[4]
 constexpr int kAttrRedDoubles = kAttrSums * 16 + 16 + 8 + 8 + 8;  // the sums' wave roots; the arg-max's values, indices and
                                                                   // positions; the slot's scalars
@@ -68,8 +68,7 @@ template <int NT, int IPT>
 constexpr size_t attr_lds_doubles() { return (2 + (size_t)NT * IPT + 2 * (NT / 64) + 1) / 2 * 2; }
 inline size_t attr_lds_bytes(int n) { return (tree_lds_doubles_even(n) + kAttrRedDoubles) * sizeof(double); }
 
-// loss_flow_scan (losses_kernels.hip) without the pair tree, and with one addition: bad |= a gathered EV node sum is not
-// finite.
+// net_scans.h's net_gather and net_flow_scan in one, with one addition: bad |= a gathered EV node sum is not finite.
 template <int NT, int IPT>
 __device__ __forceinline__ void attr_flow_scan(const AttrArgs &A, int t, double *lds, const unsigned (&se)[IPT], double (&a)[IPT],
                                                bool &bad) {
@@ -140,7 +139,7 @@ __device__ __forceinline__ unsigned long long attr_load_bytes(const uint8_t *p, 
     return p ? *reinterpret_cast<const unsigned long long *>(p + jl) : 0x0101010101010101ull;
 }
 
-// w' = w flow, the drop scan's terms (net_headroom_kernel's lines, under the same contraction setting)
+// w' = w flow, the drop scan's terms (net_scans.h's net_times_w, under the same contraction setting)
 template <int IPT>
 __device__ __forceinline__ void attr_times_w(const TreeArgs &tr, bool act, int jl, double (&a)[IPT]) {
 #pragma unroll
@@ -154,7 +153,7 @@ __device__ __forceinline__ void attr_times_w(const TreeArgs &tr, bool act, int j
     }
 }
 
-// The drop scan (loss_path_scan): a[i] = the terms of this thread's positions (0 beyond the tree) -> their sums over the
+// The drop scan (net_scans.h's net_path_scan): a[i] = the terms of this thread's positions (0 beyond the tree) -> their sums over the
 // positions' ancestors-or-self.  Every earlier read of the LDS buffer must be done; ends without a barrier behind its own
 // last reads.
 template <int NT, int IPT>

@@ -7,8 +7,8 @@
 //                       the staged values) and headroom_day_kernel (one thread per (scenario, position))
 //
 // One workgroup per (slot, scenario):
-//   1. the flow and the drop scans of the network report, from the same text (head_flow_scan is net_flow_scan with the
-//      test for a non-finite injection added; the drop scans are net_report_kernel's): the same bits;
+//   1. the flow and the drop scans of the network report (net_scans.h, with the gather's test for a non-finite
+//      injection; the drop scan's last step a chunk at a time, as net_report_kernel takes it): the same bits;
 //   2. up:   A[a] = min of the slacks drop_max - drop[j] over the limit nodes of a's subtree, as ordered 64-bit keys in
 //            the scans' LDS buffer.  Round r sends every position's current minimum to its 2^r-th ancestor by an LDS
 //            atomic minimum.  In place: what a position holds is at every moment a minimum over some of its own
@@ -28,6 +28,7 @@
 // that the summary and the day kernel read.
 #include "common.h"
 #include "boxplot.h"
+#include "net_scans.h"
 #include "tree_body.h"
 
 #include <math.h>
@@ -57,66 +58,6 @@ __host__ __device__ inline size_t head_lds_bytes(int n) {
     return tree_lds_bytes(n) + (size_t)sh.nt * sh.ipt / 8;
 }
 
-constexpr int kHeadChunk = 8;      // positions whose side data are in flight at once (network_kernels.hip: kNetChunk),
-#define HEAD_FENCE() __builtin_amdgcn_sched_barrier(0)     // fenced for the scheduler: the 1024 x 16 shape has 128 registers
-
-// net_flow_scan (network_kernels.hip) with one addition: bad |= a gathered node sum is not finite.
-template <int NT, int IPT>
-__device__ __forceinline__ void head_flow_scan(const HeadArgs &A, int t, double *lds, const unsigned (&se)[IPT], double (&a)[IPT],
-                                               bool &bad) {
-    const int tid = threadIdx.x, j0 = IPT * tid;
-    const bool act = j0 < A.tr.n;
-    double *base = lds + 2, *red0 = lds + 2 + NT * IPT;
-#pragma unroll
-    for (int i = 0; i < IPT; ++i) {          // (positions without a row fetch row 0: straight-line loads, masked behind them)
-        const int s = (int)(se[i] & 0xFFFFu) - 1;
-        const bool ok = act && s >= 0 && s < A.m;
-        const double v = A.g[(int64_t)(ok ? s : 0) * A.T + t];
-        a[i] = ok ? v : 0.0;
-        bad |= !(a[i] - a[i] == 0.0);
-    }
-#pragma unroll
-    for (int i = 1; i < IPT; ++i) a[i] += a[i - 1];
-    const double cex = block_excl_offset<NT>(a[IPT - 1], red0);
-    if (act) {
-#pragma unroll
-        for (int i = 0; i < IPT; i += 2)
-            *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i] + cex, a[i + 1] + cex}};
-    }
-    __syncthreads();
-    if (act) {
-#pragma unroll
-        for (int i = IPT - 1; i >= 1; --i) a[i] = base[(int)(se[i] >> 16) - 1] - (a[i - 1] + cex);
-        a[0] = base[(int)(se[0] >> 16) - 1] - cex;
-    }
-    __syncthreads();
-}
-
-template <int IPT>
-__device__ __forceinline__ void head_load_se(const HeadArgs &A, int jl, unsigned (&se)[IPT]) {
-#pragma unroll
-    for (int i = 0; i < IPT; i += 2) {
-        const TreeU2 u = *reinterpret_cast<const TreeU2 *>(A.tr.pack + jl + i);
-        se[i] = (unsigned)u.v[0]; se[i + 1] = (unsigned)u.v[1];
-    }
-}
-
-// a chunk's caller-side node indices (-1: a padding position or a thread beyond the tree)
-__device__ __forceinline__ void head_load_nd(const HeadArgs &A, bool act, int jl, int (&nd)[kHeadChunk]) {
-    if (A.nop) {
-#pragma unroll
-        for (int i = 0; i < kHeadChunk; i += 4) {
-            const int4 u = *reinterpret_cast<const int4 *>(A.nop + jl + i);
-            nd[i] = u.x; nd[i + 1] = u.y; nd[i + 2] = u.z; nd[i + 3] = u.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < kHeadChunk; ++i) nd[i] = jl + i;
-    }
-#pragma unroll
-    for (int i = 0; i < kHeadChunk; ++i) nd[i] = (act && nd[i] >= 0 && nd[i] < A.n_out) ? nd[i] : -1;
-}
-
 // thr[i] = rating - flow where the line above the position is rated, else +inf
 template <int IPT>
 __device__ __forceinline__ void head_thermal(const HeadArgs &A, int jl, const double (&flow)[IPT], double (&thr)[IPT]) {
@@ -132,12 +73,12 @@ __device__ __forceinline__ void head_thermal(const HeadArgs &A, int jl, const do
     }
 }
 
-// The positions of the 2^r-th ancestors of kHeadChunk consecutive positions from jl on (-1: none; an entry that is no
+// The positions of the 2^r-th ancestors of kNetChunk consecutive positions from jl on (-1: none; an entry that is no
 // earlier position -- a table that is not a preorder forest's -- is none as well: nothing is indexed by it).
-__device__ __forceinline__ void head_anc_chunk(const HeadArgs &A, int r, int jl, int (&p)[kHeadChunk]) {
+__device__ __forceinline__ void head_anc_chunk(const HeadArgs &A, int r, int jl, int (&p)[kNetChunk]) {
     if (r == 0) {
 #pragma unroll
-        for (int i = 0; i < kHeadChunk; i += 4) {
+        for (int i = 0; i < kNetChunk; i += 4) {
             const int4 u = *reinterpret_cast<const int4 *>(A.parent + jl + i);
             p[i] = u.x; p[i + 1] = u.y; p[i + 2] = u.z; p[i + 3] = u.w;
         }
@@ -147,7 +88,7 @@ __device__ __forceinline__ void head_anc_chunk(const HeadArgs &A, int r, int jl,
         p[4] = (int)(u.z & 0xFFFFu); p[5] = (int)(u.z >> 16); p[6] = (int)(u.w & 0xFFFFu); p[7] = (int)(u.w >> 16);
     }
 #pragma unroll
-    for (int i = 0; i < kHeadChunk; ++i) p[i] = (p[i] >= 0 && p[i] < jl + i) ? p[i] : -1;
+    for (int i = 0; i < kNetChunk; ++i) p[i] = (p[i] >= 0 && p[i] < jl + i) ? p[i] : -1;
 }
 __device__ __forceinline__ int head_anc_one(const HeadArgs &A, int r, int j) {
     const int p = r == 0 ? A.parent[j] : (int)A.jump[(size_t)(r - 1) * A.tr.n + j];
@@ -173,93 +114,58 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
     const TreeArgs &tr = A.tr;
     const bool act = j0 < n;
     const int jl = act ? j0 : 0;                                    // (threads beyond the tree load position 0's data, unused)
-    double *base = lds + 2, *red0 = lds + 2 + NT * IPT, *red1 = red0 + NT / 64;
-    unsigned long long *kbuf = reinterpret_cast<unsigned long long *>(base);       // A, then q: ordered keys by position
-    unsigned char *kindb = reinterpret_cast<unsigned char *>(red1 + NT / 64);      // one bit per position
+    unsigned long long *kbuf = reinterpret_cast<unsigned long long *>(lds + 2);    // A, then q: ordered keys by position
+    unsigned char *kindb = reinterpret_cast<unsigned char *>(lds + 2 + NT * IPT + 2 * (NT / 64));     // one bit per position
     const unsigned long long kInf = box_key(__builtin_inf());
     // the 1024 x 16 shape has 128 registers per thread: it does not carry the thermal room through the drop scans but
     // runs the flow scan again behind them (the same bits: its order is fixed), as net_report_kernel does for its keys
     constexpr bool kRescan = IPT > 8;
     if (tid == 0) lds[1] = 0.0;                                     // base[-1]
 
-    double a[IPT], b[IPT], thr[IPT];
+    double a[IPT], thr[IPT];
     bool bad = false;
     {
         unsigned se[IPT];
-        head_load_se<IPT>(A, jl, se);
-        head_flow_scan<NT, IPT>(A, t, lds, se, a, bad);
+        net_load_se<IPT>(tr, jl, se);
+        net_gather<IPT>(A.g, A.m, A.T, t, act, se, a, &bad);     // (A's fields, not locals: net_scans.h)
+        net_flow_scan<NT, IPT>(act, lds, se, a);
     }
-    HEAD_FENCE();
+    NET_CHUNK_FENCE();
     const bool nanslot = __syncthreads_or(bad ? 1 : 0) != 0;        // the slot as a whole: one flag for the workgroup
     if constexpr (!kRescan) head_thermal<IPT>(A, jl, a, thr);
     // ---- flow out; w' = w flow
 #pragma unroll
-    for (int c = 0; c < IPT; c += kHeadChunk) {
+    for (int c = 0; c < IPT; c += kNetChunk) {
         if (A.flow) {
-            int nd[kHeadChunk];
-            head_load_nd(A, act, jl + c, nd);
+            int nd[kNetChunk];
+            net_load_nd(A.nop, A.n_out, act, jl + c, nd);
 #pragma unroll
-            for (int i = 0; i < kHeadChunk; ++i)
+            for (int i = 0; i < kNetChunk; ++i)
                 if (nd[i] >= 0) A.flow[(int64_t)nd[i] * T + t] = a[c + i];
         }
-#pragma unroll
-        for (int i = 0; i < kHeadChunk; i += 2) {
-            const TreeD2 wv = *reinterpret_cast<const TreeD2 *>(tr.w + jl + c + i);
-            a[c + i] = act ? a[c + i] * wv.v[0] : 0.0; a[c + i + 1] = act ? a[c + i + 1] * wv.v[1] : 0.0;
-        }
-        HEAD_FENCE();
+        net_times_w_chunk<IPT>(tr, act, jl, c, a);
+        NET_CHUNK_FENCE();
     }
-    if (act) {
-#pragma unroll
-        for (int i = 0; i < IPT; i += 2) *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i], a[i + 1]}};
-    }
-    __syncthreads();
 
-    // ---- the same values in end-order, both prefixes, drop_j = Pre[j] - F_excl[cle_j]; the slack's key where j is a limit node
+    // ---- the drop scan, its last step a chunk at a time into the slack's key where j is a limit node
     unsigned long long key[IPT];
     {
-        unsigned ec[IPT];                                           // eo | cle << 16
+        unsigned ec[IPT];
+        double pex;
+        net_path_prefix<NT, IPT>(tr, act, jl, lds, a, ec, pex);
 #pragma unroll
-        for (int i = 0; i < IPT; i += 2) {
-            const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + i);
-            ec[i] = (unsigned)(u.v[0] >> 32); ec[i + 1] = (unsigned)(u.v[1] >> 32);
-        }
+        for (int c = 0; c < IPT; c += kNetChunk) {
+            const unsigned long long mk = net_limit_bytes(tr, A.limit, jl + c);
+            int nd[kNetChunk];
+            if (A.drop) net_load_nd(A.nop, A.n_out, act, jl + c, nd);
 #pragma unroll
-        for (int i = 0; i < IPT; ++i) b[i] = act ? base[(int)(ec[i] & 0xFFFFu)] : 0.0;
-#pragma unroll
-        for (int i = 1; i < IPT; ++i) { a[i] += a[i - 1]; b[i] += b[i - 1]; }
-        const double pex = block_excl_offset<NT>(a[IPT - 1], red1); // (its barrier: every read of w' is done)
-        const double fex = block_excl_offset<NT>(b[IPT - 1], red0);
-        if (act) {
-#pragma unroll
-            for (int i = 0; i < IPT; i += 2)
-                *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{b[i] + fex, b[i + 1] + fex}};
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < IPT; c += kHeadChunk) {
-            // the chunk's limit nodes, a byte each: the mask's, or (no mask) whether the position carries a row
-            unsigned long long mk = 0ull;
-            if (A.limit) {
-                mk = *reinterpret_cast<const unsigned long long *>(A.limit + jl + c);
-            } else {
-#pragma unroll
-                for (int i = 0; i < kHeadChunk; i += 2) {
-                    const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + c + i);
-                    mk |= (unsigned long long)((u.v[0] & 0xFFFFull) != 0ull) << (8 * i);
-                    mk |= (unsigned long long)((u.v[1] & 0xFFFFull) != 0ull) << (8 * i + 8);
-                }
-            }
-            int nd[kHeadChunk];
-            if (A.drop) head_load_nd(A, act, jl + c, nd);
-#pragma unroll
-            for (int i = 0; i < kHeadChunk; ++i) {
-                const double d = (a[c + i] + pex) - base[act ? (int)(ec[c + i] >> 16) - 1 : -1];
+            for (int i = 0; i < kNetChunk; ++i) {
+                const double d = net_path_at(act, lds, a[c + i], pex, ec[c + i]);
                 if (A.drop && nd[i] >= 0) A.drop[(int64_t)nd[i] * T + t] = d;
                 const bool lim = act && ((mk >> (8 * i)) & 0xFFu) != 0ull;
                 key[c + i] = lim ? box_key(A.drop_max - d) : kInf;
             }
-            HEAD_FENCE();
+            NET_CHUNK_FENCE();
         }
     }
     __syncthreads();                                                // (every read of F is done)
@@ -267,11 +173,11 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
     if (nanslot) {                                                  // (uniform) nothing of this slot is a headroom
         const double nan = __builtin_nan("");
 #pragma unroll
-        for (int c = 0; c < IPT; c += kHeadChunk) {
-            int nd[kHeadChunk];
-            head_load_nd(A, act, jl + c, nd);
+        for (int c = 0; c < IPT; c += kNetChunk) {
+            int nd[kNetChunk];
+            net_load_nd(A.nop, A.n_out, act, jl + c, nd);
 #pragma unroll
-            for (int i = 0; i < kHeadChunk; ++i) {
+            for (int i = 0; i < kNetChunk; ++i) {
                 if (nd[i] < 0) continue;
                 if (A.head) A.head[(int64_t)nd[i] * T + t] = nan;
                 if (A.lim) A.lim[(int64_t)nd[i] * T + t] = -1;
@@ -286,9 +192,9 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
 
     if constexpr (kRescan) {
         unsigned se[IPT];
-        bool again = false;
-        head_load_se<IPT>(A, jl, se);
-        head_flow_scan<NT, IPT>(A, t, lds, se, a, again);
+        net_load_se<IPT>(tr, jl, se);
+        net_gather<IPT>(A.g, A.m, A.T, t, act, se, a, nullptr);
+        net_flow_scan<NT, IPT>(act, lds, se, a);
         head_thermal<IPT>(A, jl, a, thr);
     }
 
@@ -303,11 +209,11 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
     for (int r = 0; r < rounds; ++r) {
         if (act) {
 #pragma unroll
-            for (int c = 0; c < IPT; c += kHeadChunk) {
-                int p[kHeadChunk];
+            for (int c = 0; c < IPT; c += kNetChunk) {
+                int p[kNetChunk];
                 head_anc_chunk(A, r, j0 + c, p);
 #pragma unroll
-                for (int i = 0; i < kHeadChunk; ++i) {
+                for (int i = 0; i < kNetChunk; ++i) {
                     const unsigned long long k = kbuf[j0 + c + i];
                     if (p[i] >= 0 && k != kInf) atomicMin(kbuf + p[i], k);
                 }
@@ -343,11 +249,11 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
     for (int r = 0; r < rounds; ++r) {
         if (act) {
 #pragma unroll
-            for (int c = 0; c < IPT; c += kHeadChunk) {
-                int p[kHeadChunk];
+            for (int c = 0; c < IPT; c += kNetChunk) {
+                int p[kNetChunk];
                 head_anc_chunk(A, r, j0 + c, p);
 #pragma unroll
-                for (int i = 0; i < kHeadChunk; ++i) {
+                for (int i = 0; i < kNetChunk; ++i) {
                     const unsigned long long k = kbuf[p[i] >= 0 ? p[i] : j0 + c + i];
                     key[c + i] = k < key[c + i] ? k : key[c + i];
                 }
@@ -362,23 +268,23 @@ __global__ __launch_bounds__(NT) void net_headroom_kernel(HeadArgs A0) {
     }
     // ---- out: the clamp, and the limiter -- the topmost of the nearest ancestors that share q[j]
 #pragma unroll
-    for (int c = 0; c < IPT; c += kHeadChunk) {
-        int nd[kHeadChunk];
-        head_load_nd(A, act, jl + c, nd);
-        double x[kHeadChunk];
+    for (int c = 0; c < IPT; c += kNetChunk) {
+        int nd[kNetChunk];
+        net_load_nd(A.nop, A.n_out, act, jl + c, nd);
+        double x[kNetChunk];
 #pragma unroll
-        for (int i = 0; i < kHeadChunk; ++i) {
+        for (int i = 0; i < kNetChunk; ++i) {
             const double q = box_val(key[c + i]);
             x[i] = q > 0.0 ? q : 0.0;
             if (A.head && nd[i] >= 0) A.head[(int64_t)nd[i] * T + t] = x[i];
         }
         if (A.stage && act) {
 #pragma unroll
-            for (int i = 0; i < kHeadChunk; i += 2) *reinterpret_cast<TreeD2 *>(A.stage + j0 + c + i) = TreeD2{{x[i], x[i + 1]}};
+            for (int i = 0; i < kNetChunk; i += 2) *reinterpret_cast<TreeD2 *>(A.stage + j0 + c + i) = TreeD2{{x[i], x[i + 1]}};
         }
         if (A.lim) {
 #pragma unroll
-            for (int i = 0; i < kHeadChunk; ++i) {
+            for (int i = 0; i < kNetChunk; ++i) {
                 if (nd[i] < 0) continue;
                 int word = -1;
                 if (key[c + i] != kInf) {
@@ -409,21 +315,6 @@ struct HeadSumArgs {
     double need;
 };
 
-template <class F>
-__device__ __forceinline__ void head_for_each(const HeadSumArgs &A, const double *row, F f) {
-    for (int jb = 0; jb < A.n; jb += kHeadSumNT) {
-        const int j = jb + (int)threadIdx.x;
-        double v = __builtin_nan("");
-        int nd = -1;
-        if (j < A.n) {
-            nd = A.nop ? A.nop[j] : j;
-            nd = (nd >= 0 && nd < A.n_out && (!A.mask || A.mask[j] != 0)) ? nd : -1;
-            v = row[j];
-        }
-        f(v, nd);
-    }
-}
-
 __global__ __launch_bounds__(kHeadSumNT) void headroom_summary_kernel(HeadSumArgs A) {
     __shared__ BoxSelect<kHeadSumNT> sh;
     constexpr int NT = kHeadSumNT;
@@ -432,7 +323,7 @@ __global__ __launch_bounds__(kHeadSumNT) void headroom_summary_kernel(HeadSumArg
     const double ninf = -__builtin_inf(), inf = __builtin_inf();
     // box_select64's walk: an element is part of the sample when it is summarised and finite
     auto walk = [&](auto f) {
-        head_for_each(A, row, [&](double v, int nd) { f(box_key(v), nd >= 0 && v < inf, v, 0, nd); });
+        net_for_each<NT>(row, A.n, A.nop, A.n_out, A.mask, [&](double v, int nd, int) { f(box_key(v), nd >= 0 && v < inf, v, 0, nd); });
     };
     for (int i = tid; i < 3 * 256; i += NT) sh.hist[i] = 0u;
     __syncthreads();
@@ -502,7 +393,7 @@ __global__ void headroom_day_kernel(const double *stage, const int32_t *nop, rev
 using namespace revs;
 
 extern "C" int64_t revs_net_headroom_scratch(int32_t S, int32_t T, int32_t tree_n) {
-    if (S < 1 || S > REVS_STUDY_MAX_S || T < 1 || T > REVS_MAX_T || tree_n < 1 || tree_n > REVS_TREE_MAX) return 0;
+    if (!net_scratch_sizes_ok(S, T, tree_n)) return 0;
     return (int64_t)S * T * tree_n * (int64_t)sizeof(double);
 }
 
@@ -513,13 +404,9 @@ extern "C" int revs_net_headroom(int32_t S, int32_t m, int32_t T, const revs_tre
                                  revs_net_summary_t *summary_out, revs_headroom_day_t *day_out, void *scratch, void *stream) {
     static_assert(sizeof(revs_headroom_day_t) == 16, "");
     const char *who = "revs_net_headroom";
-    REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
-    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
-    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "%s: m=%d outside 1..65535", who, (int)m);
-    REVS_REQUIRE(node_g, "%s: null pointer argument node_g", who);
-    const TreeArgs tr = tree_args(tree);
-    REVS_REQUIRE(tree_form_ok(tr), "%s: " REVS_TREE_FORM_MSG, who, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
-    REVS_REQUIRE(n_out > 0 && n_out <= tr.n, "%s: n_out=%d outside 1..tree nodes", who, (int)n_out);
+    TreeArgs tr;
+    int rc = net_tree_checks(who, S, m, T, tree, node_g, " node_g", n_out, &tr);
+    if (rc != REVS_OK) return rc;
     REVS_REQUIRE(aux && aux->parent_pos && aux->wc, "%s: null aux, aux->parent_pos or aux->wc", who);
     REVS_REQUIRE(aux->n_jump >= 0 && aux->n_jump <= REVS_HEADROOM_MAX_JUMP, "%s: aux->n_jump=%d outside 0..%d", who,
                  (int)aux->n_jump, REVS_HEADROOM_MAX_JUMP);
@@ -528,8 +415,8 @@ extern "C" int revs_net_headroom(int32_t S, int32_t m, int32_t T, const revs_tre
     REVS_REQUIRE(need - need == 0.0 && need >= 0.0, "%s: need must be finite and >= 0", who);
     REVS_REQUIRE(headroom_out || limiter_out || drop_out || flow_out || summary_out || day_out, "%s: every output is NULL", who);
     const bool staged = summary_out || day_out;
-    REVS_REQUIRE(!staged || scratch, "%s: summary_out / day_out need scratch (revs_net_headroom_scratch bytes)", who);
-    REVS_REQUIRE(!staged || ((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", who);
+    rc = net_scratch_checks(who, staged, scratch, "summary_out / day_out need", "revs_net_headroom_scratch");
+    if (rc != REVS_OK) return rc;
     HeadArgs A;
     A.tr = tr;
     A.g = node_g; A.rating = rating; A.wc = aux->wc; A.limit = limit_mask; A.nop = node_of_pos;
@@ -537,7 +424,7 @@ extern "C" int revs_net_headroom(int32_t S, int32_t m, int32_t T, const revs_tre
     A.m = m; A.T = T; A.n_out = n_out; A.drop_max = drop_max;
     A.head = headroom_out; A.lim = limiter_out; A.drop = drop_out; A.flow = flow_out;
     A.stage = staged ? (double *)scratch : nullptr;
-    const int rc = for_tree_shape(tr.n, [&](auto nt, auto ipt) {
+    rc = for_tree_shape(tr.n, [&](auto nt, auto ipt) {
         return launch_lds(net_headroom_kernel<nt(), ipt()>, dim3(T, S), dim3(nt()), head_lds_bytes(tr.n), (hipStream_t)stream, who, A);
     });
     if (rc != REVS_OK) return rc;

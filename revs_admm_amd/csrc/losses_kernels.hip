@@ -7,13 +7,12 @@
 //                     workgroup per scenario: the slot loops and the top 8 by repeated arg-max)
 //
 // One workgroup per (slot, scenario):
-//   1. the flow and the drop scans of the network report, from headroom_kernels.hip's text (loss_flow_scan is its
-//      head_flow_scan, which also leaves each thread's pair-tree sum of the gathered injections; loss_path_scan is the
-//      drop scan as a function of the per-position terms): the same bits;
+//   1. the flow and the drop scans of the network report (net_scans.h; between the gather and the flow scan each thread
+//      takes the pair-tree sum of its gathered injections): the same bits;
 //   2. den = vset2 - drop, and the slot's one flag: a row's injection not finite, or den > 0 failing where the position
 //      has a caller-side index (one __syncthreads_or);
 //   3. loss = ((0.5 w) flow) flow / den and c = (w flow) / den in registers, the losses stored and staged by position;
-//   4. mlf = loss_path_scan(c): the sum of c over the ancestors-or-self, in the drop scan's form;
+//   4. mlf = net_path_scan(c): the sum of c over the ancestors-or-self, in the drop scan's form;
 //   5. the sums -- total, delivered, class_total[4] -- as the root of ONE fixed binary tree over the positions: pairs
 //      inside the thread's aligned 8 (16) positions, an xor butterfly over the lanes, then the wavefronts' roots level by
 //      level in LDS; only the next_pow2(n) / IPT threads that hold leaves take part, so no padding zero is ever added
@@ -28,6 +27,7 @@
 #include "common.h"
 #include "boxplot.h"
 #include "fixed_tree.h"       // pair_tree, arg_better, wave_argmax
+#include "net_scans.h"
 #include "tree_body.h"
 
 #include <math.h>
@@ -51,128 +51,12 @@ struct LossArgs {
     double *stage;                // [S][T][n] by position, or NULL
 };
 
-constexpr int kLossChunk = 8;      // positions whose side data are in flight at once (headroom_kernels.hip: kHeadChunk)
 constexpr int kLossSums = 6;       // delivered, total, class_total[4]
 constexpr int kLossRedDoubles = kLossSums * 16 + 16 + 8;      // the sums' wave roots, the arg-max's values and indices
-#define LOSS_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-template <int NT, int IPT>
-constexpr size_t loss_lds_doubles() { return (2 + (size_t)NT * IPT + 2 * (NT / 64) + 1) / 2 * 2; }
 inline size_t loss_lds_bytes(int n) { return (tree_lds_doubles_even(n) + kLossRedDoubles) * sizeof(double); }
 
-// head_flow_scan (headroom_kernels.hip: net_flow_scan with the finiteness test) with one addition: inj_root = the
-// pair-tree sum of the thread's gathered injections.
-template <int NT, int IPT>
-__device__ __forceinline__ void loss_flow_scan(const LossArgs &A, int t, double *lds, const unsigned (&se)[IPT], double (&a)[IPT],
-                                               bool &bad, double &inj_root) {
-    const int tid = threadIdx.x, j0 = IPT * tid;
-    const bool act = j0 < A.tr.n;
-    double *base = lds + 2, *red0 = lds + 2 + NT * IPT;
-#pragma unroll
-    for (int i = 0; i < IPT; ++i) {          // (positions without a row fetch row 0: straight-line loads, masked behind them)
-        const int s = (int)(se[i] & 0xFFFFu) - 1;
-        const bool ok = act && s >= 0 && s < A.m;
-        const double v = A.g[(int64_t)(ok ? s : 0) * A.T + t];
-        a[i] = ok ? v : 0.0;
-        bad |= !(a[i] - a[i] == 0.0);
-    }
-    inj_root = pair_tree<IPT>(a);
-#pragma unroll
-    for (int i = 1; i < IPT; ++i) a[i] += a[i - 1];
-    const double cex = block_excl_offset<NT>(a[IPT - 1], red0);
-    if (act) {
-#pragma unroll
-        for (int i = 0; i < IPT; i += 2)
-            *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i] + cex, a[i + 1] + cex}};
-    }
-    __syncthreads();
-    if (act) {
-#pragma unroll
-        for (int i = IPT - 1; i >= 1; --i) a[i] = base[(int)(se[i] >> 16) - 1] - (a[i - 1] + cex);
-        a[0] = base[(int)(se[0] >> 16) - 1] - cex;
-    }
-    __syncthreads();
-}
-
-template <int IPT>
-__device__ __forceinline__ void loss_load_se(const LossArgs &A, int jl, unsigned (&se)[IPT]) {
-#pragma unroll
-    for (int i = 0; i < IPT; i += 2) {
-        const TreeU2 u = *reinterpret_cast<const TreeU2 *>(A.tr.pack + jl + i);
-        se[i] = (unsigned)u.v[0]; se[i + 1] = (unsigned)u.v[1];
-    }
-}
-
-// a chunk's caller-side node indices (-1: a padding position or a thread beyond the tree)
-__device__ __forceinline__ void loss_load_nd(const LossArgs &A, bool act, int jl, int (&nd)[kLossChunk]) {
-    if (A.nop) {
-#pragma unroll
-        for (int i = 0; i < kLossChunk; i += 4) {
-            const int4 u = *reinterpret_cast<const int4 *>(A.nop + jl + i);
-            nd[i] = u.x; nd[i + 1] = u.y; nd[i + 2] = u.z; nd[i + 3] = u.w;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < kLossChunk; ++i) nd[i] = jl + i;
-    }
-#pragma unroll
-    for (int i = 0; i < kLossChunk; ++i) nd[i] = (act && nd[i] >= 0 && nd[i] < A.n_out) ? nd[i] : -1;
-}
-
-// a chunk's bytes of a per-position uint8 array, one 8-byte load (NULL: every byte 1)
-__device__ __forceinline__ unsigned long long loss_load_bytes(const uint8_t *p, int jl) {
-    return p ? *reinterpret_cast<const unsigned long long *>(p + jl) : 0x0101010101010101ull;
-}
-
-// w' = w flow, the drop scan's terms (net_headroom_kernel's lines, under the same contraction setting)
-template <int IPT>
-__device__ __forceinline__ void loss_times_w(const TreeArgs &tr, bool act, int jl, double (&a)[IPT]) {
-#pragma unroll
-    for (int c = 0; c < IPT; c += kLossChunk) {
-#pragma unroll
-        for (int i = 0; i < kLossChunk; i += 2) {
-            const TreeD2 wv = *reinterpret_cast<const TreeD2 *>(tr.w + jl + c + i);
-            a[c + i] = act ? a[c + i] * wv.v[0] : 0.0; a[c + i + 1] = act ? a[c + i + 1] * wv.v[1] : 0.0;
-        }
-        LOSS_FENCE();
-    }
-}
-
-// The drop scan as a function: a[i] = the terms of this thread's positions (0 beyond the tree) -> their sums over the
-// positions' ancestors-or-self, Pre[j] - F_excl[cle_j] with Pre the prefix in preorder and F the prefix in end-order.
-// Every earlier read of the LDS buffer must be done; ends without a barrier behind its own last reads.
-template <int NT, int IPT>
-__device__ __forceinline__ void loss_path_scan(const TreeArgs &tr, bool act, int jl, double *lds, double (&a)[IPT]) {
-    const int j0 = IPT * threadIdx.x;
-    double *base = lds + 2, *red0 = lds + 2 + NT * IPT, *red1 = red0 + NT / 64;
-    double b[IPT];
-    unsigned ec[IPT];                                               // eo | cle << 16
-    if (act) {
-#pragma unroll
-        for (int i = 0; i < IPT; i += 2) *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{a[i], a[i + 1]}};
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < IPT; i += 2) {
-        const TreeU2 u = *reinterpret_cast<const TreeU2 *>(tr.pack + jl + i);
-        ec[i] = (unsigned)(u.v[0] >> 32); ec[i + 1] = (unsigned)(u.v[1] >> 32);
-    }
-#pragma unroll
-    for (int i = 0; i < IPT; ++i) b[i] = act ? base[(int)(ec[i] & 0xFFFFu)] : 0.0;
-#pragma unroll
-    for (int i = 1; i < IPT; ++i) { a[i] += a[i - 1]; b[i] += b[i - 1]; }
-    const double pex = block_excl_offset<NT>(a[IPT - 1], red1);     // (its barrier: every read of the terms is done)
-    const double fex = block_excl_offset<NT>(b[IPT - 1], red0);
-    if (act) {
-#pragma unroll
-        for (int i = 0; i < IPT; i += 2)
-            *reinterpret_cast<TreeD2 *>(base + j0 + i) = TreeD2{{b[i] + fex, b[i + 1] + fex}};
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < IPT; ++i) a[i] = (a[i] + pex) - base[act ? (int)(ec[i] >> 16) - 1 : -1];
-}
-
+// (net_scans.h above is compiled as every tree report compiles it: flow and drop keep the network report's bits.)
 // Everything below rounds each operation on its own (the contract's IEEE operations): no product is fused into a sum.
 #pragma clang fp contract(off)
 
@@ -195,7 +79,7 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
     const TreeArgs &tr = A.tr;
     const bool act = j0 < n;
     const int jl = act ? j0 : 0;                                    // (threads beyond the tree load position 0's data, unused)
-    double *sred = lds + loss_lds_doubles<NT, IPT>();               // [kLossSums][16]
+    double *sred = lds + net_lds_doubles<NT, IPT>();               // [kLossSums][16]
     double *mred = sred + kLossSums * 16;                           // [16]
     int *ired = reinterpret_cast<int *>(mred + 16);                 // [16]
     constexpr bool kRescan = IPT > 8;
@@ -207,61 +91,62 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
     bool bad = false;
     {
         unsigned se[IPT];
-        loss_load_se<IPT>(A, jl, se);
-        loss_flow_scan<NT, IPT>(A, t, lds, se, a, bad, root[0]);
+        net_load_se<IPT>(tr, jl, se);
+        net_gather<IPT>(A.g, A.m, A.T, t, act, se, a, &bad);     // (A's fields, not locals: net_scans.h)
+        root[0] = pair_tree<IPT>(a);
+        net_flow_scan<NT, IPT>(act, lds, se, a);
     }
-    LOSS_FENCE();
+    NET_CHUNK_FENCE();
     // ---- flow out
 #pragma unroll
-    for (int c = 0; c < IPT; c += kLossChunk) {
+    for (int c = 0; c < IPT; c += kNetChunk) {
         if (A.flow) {
-            int nd[kLossChunk];
-            loss_load_nd(A, act, jl + c, nd);
+            int nd[kNetChunk];
+            net_load_nd(A.nop, A.n_out, act, jl + c, nd);
 #pragma unroll
-            for (int i = 0; i < kLossChunk; ++i)
+            for (int i = 0; i < kNetChunk; ++i)
                 if (nd[i] >= 0) A.flow[(int64_t)nd[i] * T + t] = a[c + i];
         }
         if constexpr (!kRescan) {
 #pragma unroll
-            for (int i = 0; i < kLossChunk; ++i) f[c + i] = a[c + i];
+            for (int i = 0; i < kNetChunk; ++i) f[c + i] = a[c + i];
         }
-        LOSS_FENCE();
+        NET_CHUNK_FENCE();
     }
     // ---- drop = the path sums of w flow; den = vset2 - drop; the slot's flag
-    loss_times_w<IPT>(tr, act, jl, a);
-    loss_path_scan<NT, IPT>(tr, act, jl, lds, a);
+    net_times_w<IPT>(tr, act, jl, a);
+    net_path_scan<NT, IPT>(tr, act, jl, lds, a);
 #pragma unroll
-    for (int c = 0; c < IPT; c += kLossChunk) {
-        int nd[kLossChunk];
-        loss_load_nd(A, act, jl + c, nd);
+    for (int c = 0; c < IPT; c += kNetChunk) {
+        int nd[kNetChunk];
+        net_load_nd(A.nop, A.n_out, act, jl + c, nd);
 #pragma unroll
-        for (int i = 0; i < kLossChunk; ++i) {
+        for (int i = 0; i < kNetChunk; ++i) {
             if (A.drop && nd[i] >= 0) A.drop[(int64_t)nd[i] * T + t] = a[c + i];
             a[c + i] = A.vset2 - a[c + i];
             bad |= nd[i] >= 0 && !(a[c + i] > 0.0);
         }
-        LOSS_FENCE();
+        NET_CHUNK_FENCE();
     }
     const bool badslot = __syncthreads_or(bad ? 1 : 0) != 0;        // (its barrier: every read of F is done)
     if constexpr (kRescan) {
         unsigned se[IPT];
-        bool again = false;
-        double inj;
-        loss_load_se<IPT>(A, jl, se);
-        loss_flow_scan<NT, IPT>(A, t, lds, se, f, again, inj);
+        net_load_se<IPT>(tr, jl, se);
+        net_gather<IPT>(A.g, A.m, A.T, t, act, se, f, nullptr);
+        net_flow_scan<NT, IPT>(act, lds, se, f);
     }
     // ---- loss and c per line; the losses out and staged; this thread's subtrees of total and class_total
-    double half[IPT / kLossChunk][kLossSums - 1];
+    double half[IPT / kNetChunk][kLossSums - 1];
 #pragma unroll
-    for (int c = 0; c < IPT; c += kLossChunk) {
-        int nd[kLossChunk];
-        loss_load_nd(A, act, jl + c, nd);
-        const unsigned long long lm = loss_load_bytes(A.line_mask, jl + c);
-        const unsigned long long lc = A.line_class ? loss_load_bytes(A.line_class, jl + c) : ~0ull;
-        double x[kLossChunk];
+    for (int c = 0; c < IPT; c += kNetChunk) {
+        int nd[kNetChunk];
+        net_load_nd(A.nop, A.n_out, act, jl + c, nd);
+        const unsigned long long lm = net_load_bytes(A.line_mask, jl + c);
+        const unsigned long long lc = A.line_class ? net_load_bytes(A.line_class, jl + c) : ~0ull;
+        double x[kNetChunk];
         double l1[kLossSums - 1], l2[kLossSums - 1];                // the pair tree's pending nodes: one per level
 #pragma unroll
-        for (int i = 0; i < kLossChunk; i += 2) {
+        for (int i = 0; i < kNetChunk; i += 2) {
             const TreeD2 wv = *reinterpret_cast<const TreeD2 *>(tr.w + jl + c + i);
             double leaf[2][kLossSums - 1];
 #pragma unroll
@@ -282,41 +167,41 @@ __global__ __launch_bounds__(NT) void net_losses_kernel(LossArgs A0) {
                 if ((i & 2) == 0) { l1[q] = pair; continue; }
                 const double quad = l1[q] + pair;
                 if ((i & 4) == 0) l2[q] = quad;
-                else half[c / kLossChunk][q] = l2[q] + quad;
+                else half[c / kNetChunk][q] = l2[q] + quad;
             }
         }
         if (A.loss) {
 #pragma unroll
-            for (int i = 0; i < kLossChunk; ++i)
+            for (int i = 0; i < kNetChunk; ++i)
                 if (nd[i] >= 0) A.loss[(int64_t)nd[i] * T + t] = x[i];
         }
         if (A.stage && act) {
 #pragma unroll
-            for (int i = 0; i < kLossChunk; i += 2) *reinterpret_cast<TreeD2 *>(A.stage + j0 + c + i) = TreeD2{{x[i], x[i + 1]}};
+            for (int i = 0; i < kNetChunk; i += 2) *reinterpret_cast<TreeD2 *>(A.stage + j0 + c + i) = TreeD2{{x[i], x[i + 1]}};
         }
-        LOSS_FENCE();
+        NET_CHUNK_FENCE();
     }
 #pragma unroll
     for (int q = 0; q < kLossSums - 1; ++q) {
-        if constexpr (IPT == kLossChunk) root[1 + q] = half[0][q];
-        else root[1 + q] = half[0][q] + half[IPT / kLossChunk - 1][q];
+        if constexpr (IPT == kNetChunk) root[1 + q] = half[0][q];
+        else root[1 + q] = half[0][q] + half[IPT / kNetChunk - 1][q];
     }
     // ---- mlf = the path sums of c (every read of the buffer is done: the flag's barrier, or the second flow scan's)
-    loss_path_scan<NT, IPT>(tr, act, jl, lds, a);
+    net_path_scan<NT, IPT>(tr, act, jl, lds, a);
     double bv = 0.0;
     int bi = -1;
 #pragma unroll
-    for (int c = 0; c < IPT; c += kLossChunk) {
-        int nd[kLossChunk];
-        loss_load_nd(A, act, jl + c, nd);
-        const unsigned long long nm = loss_load_bytes(A.node_mask, jl + c);
+    for (int c = 0; c < IPT; c += kNetChunk) {
+        int nd[kNetChunk];
+        net_load_nd(A.nop, A.n_out, act, jl + c, nd);
+        const unsigned long long nm = net_load_bytes(A.node_mask, jl + c);
 #pragma unroll
-        for (int i = 0; i < kLossChunk; ++i) {
+        for (int i = 0; i < kNetChunk; ++i) {
             const double v = badslot ? nan : a[c + i];
             if (A.mlf && nd[i] >= 0) A.mlf[(int64_t)nd[i] * T + t] = v;
             if (((nm >> (8 * i)) & 0xFFull) != 0ull && v == v) arg_better(bv, bi, v, nd[i]);
         }
-        LOSS_FENCE();
+        NET_CHUNK_FENCE();
     }
     if (!A.slot && !A.slot_scr) return;                             // (uniform)
     // ---- the fixed tree above the threads: lanes by an xor butterfly, then the wavefronts' roots level by level
@@ -375,21 +260,6 @@ struct LossSumArgs {
     double loss_max;
 };
 
-template <class F>
-__device__ __forceinline__ void loss_for_each(const LossSumArgs &A, const double *row, F f) {
-    for (int jb = 0; jb < A.n; jb += kLossSumNT) {
-        const int j = jb + (int)threadIdx.x;
-        double v = __builtin_nan("");
-        int nd = -1;
-        if (j < A.n) {
-            nd = A.nop ? A.nop[j] : j;
-            nd = (nd >= 0 && nd < A.n_out && (!A.mask || A.mask[j] != 0)) ? nd : -1;
-            v = row[j];
-        }
-        f(v, nd);
-    }
-}
-
 __global__ __launch_bounds__(kLossSumNT) void loss_summary_kernel(LossSumArgs A) {
     __shared__ BoxSelect<kLossSumNT> sh;
     constexpr int NT = kLossSumNT;
@@ -398,7 +268,7 @@ __global__ __launch_bounds__(kLossSumNT) void loss_summary_kernel(LossSumArgs A)
     const double ninf = -__builtin_inf();
     // box_select64's walk: an element is part of the sample when it is summarised and no NaN
     auto walk = [&](auto f) {
-        loss_for_each(A, row, [&](double v, int nd) { f(box_key(v), nd >= 0 && v == v, v, 0, nd); });
+        net_for_each<NT>(row, A.n, A.nop, A.n_out, A.mask, [&](double v, int nd, int) { f(box_key(v), nd >= 0 && v == v, v, 0, nd); });
     };
     for (int i = tid; i < 3 * 256; i += NT) sh.hist[i] = 0u;
     __syncthreads();
@@ -538,7 +408,7 @@ __global__ __launch_bounds__(kLossDayNT) void loss_day_kernel(LossDayArgs A) {
 using namespace revs;
 
 extern "C" int64_t revs_net_losses_scratch(int32_t S, int32_t T, int32_t tree_n) {
-    if (S < 1 || S > REVS_STUDY_MAX_S || T < 1 || T > REVS_MAX_T || tree_n < 1 || tree_n > REVS_TREE_MAX) return 0;
+    if (!net_scratch_sizes_ok(S, T, tree_n)) return 0;
     return (int64_t)S * T * tree_n * (int64_t)sizeof(double) + (int64_t)S * T * (int64_t)sizeof(revs_loss_slot_t) +
            (int64_t)S * tree_n * (int64_t)sizeof(double);
 }
@@ -551,13 +421,9 @@ extern "C" int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_
                                revs_loss_day_t *day_out, void *scratch, void *stream) {
     static_assert(sizeof(revs_loss_slot_t) == 64 && sizeof(revs_loss_line_day_t) == 24 && sizeof(revs_loss_day_t) == 192, "");
     const char *who = "revs_net_losses";
-    REVS_REQUIRE(S >= 1 && S <= REVS_STUDY_MAX_S, "%s: S=%d outside 1..%d", who, (int)S, REVS_STUDY_MAX_S);
-    REVS_REQUIRE(T > 0 && T <= REVS_MAX_T, "%s: T=%d outside 1..%d", who, (int)T, REVS_MAX_T);
-    REVS_REQUIRE(m > 0 && m <= 0xFFFF, "%s: m=%d outside 1..65535", who, (int)m);
-    REVS_REQUIRE(node_g, "%s: null pointer argument node_g", who);
-    const TreeArgs tr = tree_args(tree);
-    REVS_REQUIRE(tree_form_ok(tr), "%s: " REVS_TREE_FORM_MSG, who, REVS_TREE_FORM_ARGS(tr, REVS_TREE_MAX));
-    REVS_REQUIRE(n_out > 0 && n_out <= tr.n, "%s: n_out=%d outside 1..tree nodes", who, (int)n_out);
+    TreeArgs tr;
+    int rc = net_tree_checks(who, S, m, T, tree, node_g, " node_g", n_out, &tr);
+    if (rc != REVS_OK) return rc;
     REVS_REQUIRE(vset2 - vset2 == 0.0 && vset2 > 0.0, "%s: vset2 must be finite and > 0", who);
     REVS_REQUIRE(slot_hours - slot_hours == 0.0 && slot_hours > 0.0, "%s: slot_hours must be finite and > 0", who);
     REVS_REQUIRE(loss_max > 0.0, "%s: loss_max must be > 0 (+inf allowed)", who);
@@ -566,8 +432,8 @@ extern "C" int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_
     REVS_REQUIRE(loss_out || mlf_out || drop_out || flow_out || summary_out || slot_out || line_day_out || day_out,
                  "%s: every output is NULL", who);
     const bool staged = summary_out || line_day_out || day_out;
-    REVS_REQUIRE(!staged || scratch, "%s: summary_out / line_day_out / day_out need scratch (revs_net_losses_scratch bytes)", who);
-    REVS_REQUIRE(!staged || ((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", who);
+    rc = net_scratch_checks(who, staged, scratch, "summary_out / line_day_out / day_out need", "revs_net_losses_scratch");
+    if (rc != REVS_OK) return rc;
     double *stage = staged ? (double *)scratch : nullptr;
     revs_loss_slot_t *slot_scr = staged ? (revs_loss_slot_t *)(stage + (size_t)S * T * tr.n) : nullptr;
     double *energy_scr = staged ? (double *)(slot_scr + (size_t)S * T) : nullptr;
@@ -575,17 +441,11 @@ extern "C" int revs_net_losses(int32_t S, int32_t m, int32_t T, const revs_tree_
     A.tr = tr;
     A.g = node_g; A.line_mask = line_mask; A.node_mask = node_mask; A.line_class = C > 0 ? line_class : nullptr;
     A.nop = node_of_pos;
-    A.m = m; A.T = T; A.n_out = n_out; A.C = C; A.vset2 = vset2;
-    {
-        int p2 = 1;
-        while (p2 < tr.n) p2 <<= 1;
-        const int ipt = tree_shape(tr.n).ipt;
-        A.P = p2 > ipt ? p2 / ipt : 1;
-    }
+    A.m = m; A.T = T; A.n_out = n_out; A.C = C; A.vset2 = vset2; A.P = net_leaf_threads(tr.n);
     A.loss = loss_out; A.mlf = mlf_out; A.drop = drop_out; A.flow = flow_out;
     A.slot = slot_out; A.slot_scr = day_out ? slot_scr : nullptr;
     A.stage = stage;
-    const int rc = for_tree_shape(tr.n, [&](auto nt, auto ipt) {
+    rc = for_tree_shape(tr.n, [&](auto nt, auto ipt) {
         return launch_lds(net_losses_kernel<nt(), ipt()>, dim3(T, S), dim3(nt()), loss_lds_bytes(tr.n), (hipStream_t)stream, who, A);
     });
     if (rc != REVS_OK) return rc;

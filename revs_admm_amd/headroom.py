@@ -11,9 +11,10 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tree_reports
 from ._lib import HEADROOM_DAY_DTYPE, check, ptr
-from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays, tree_on_device
+from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays
+from .tree_reports import position_mask     # (dev, tree_host, n_nodes, nodes): None, the nodes that carry a row
 
 KIND_VOLTAGE, KIND_THERMAL = 0, 1
 
@@ -80,20 +81,6 @@ def aux_on_device(dev, tree_host):
     return _lib.HeadroomAux(ptr(d_par), ptr(d_wc), ptr(d_jump), ax["n_jump"]), (d_par, d_wc, d_jump)
 
 
-def position_mask(dev, tree_host, n_nodes, nodes):
-    """uint8 per preorder position: whether the tree node there is one of `nodes` (indices or a boolean mask); None:
-    the nodes that carry a row of the injections."""
-    order = np.asarray(tree_host["order"], np.int64)
-    real = order < n_nodes
-    if nodes is None:
-        mk = real & (np.asarray(tree_host["src"]) >= 0)
-    else:
-        sel, idx = np.zeros(n_nodes, bool), np.asarray(nodes)
-        sel[idx if idx.dtype == bool else idx.astype(np.int64)] = True
-        mk = real & sel[np.where(real, order, 0)]
-    return torch.from_numpy(np.ascontiguousarray(mk.astype(np.uint8))).to(dev)
-
-
 def native_headroom_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, need, rating=None, limit_nodes=None,
                            nodes=None, vset=1.0, vmin=0.95, arrays=True, out=None) -> list:
     """revs_net_headroom on node sums that lie on the device: node_g (S, M, T) float64 device tensor, tree: _lib.Tree
@@ -105,9 +92,7 @@ def native_headroom_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, n
     need, vset, vmin = float(need), float(vset), float(vmin)
     if not (np.isfinite(need) and need >= 0.0):
         raise ValueError(f"headroom report: need must be finite and >= 0, got {need}")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (S, n, T)
-                            or not out.is_contiguous() or out.device != node_g.device):
-        raise ValueError(f"headroom report: out must be a contiguous float64 {(S, n, T)} tensor on {node_g.device}")
+    tree_reports.check_out("headroom report", out, (S, n, T), node_g.device)
     d_nop, d_rating, _ = side_arrays(dev, tree_host, n, rating, None)
     d_limit = None if limit_nodes is None else position_mask(dev, tree_host, n, limit_nodes)
     d_outm = position_mask(dev, tree_host, n, nodes)
@@ -119,18 +104,16 @@ def native_headroom_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, n
             d_head = torch.empty(S, n, T, dtype=torch.float64, device=dev)
         d_lim = torch.empty(S, n, T, dtype=torch.int32, device=dev)
         d_drop, d_flow = (torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(2))
-    d_sum = torch.zeros(S * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_day = torch.zeros(S * n * HEADROOM_DAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    nbytes = int(lib.revs_net_headroom_scratch(S, T, tree_host["n"]))
-    if nbytes <= 0:
-        raise ValueError(f"headroom report: no scratch size for S={S}, T={T}, tree of {tree_host['n']}")
-    d_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    d_sum = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * T)
+    d_day = tree_reports.record_buffer(dev, HEADROOM_DAY_DTYPE, S * n)
+    d_scratch = tree_reports.scratch("headroom report", lib.revs_net_headroom_scratch(S, T, tree_host["n"]),
+                                     f"S={S}, T={T}, tree of {tree_host['n']}", dev)
     drop_max = vset * vset - vmin * vmin
     check(lib.revs_net_headroom(S, M, T, C.byref(tree), C.byref(aux), ptr(node_g), ptr(d_rating), ptr(d_limit), ptr(d_outm),
                                 ptr(d_nop), n, drop_max, need, ptr(d_head), ptr(d_lim), ptr(d_drop), ptr(d_flow), ptr(d_sum),
                                 ptr(d_day), ptr(d_scratch), stream), "revs_net_headroom")
-    rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, T)
-    day = d_day.cpu().numpy().view(HEADROOM_DAY_DTYPE).reshape(S, n)
+    rec = tree_reports.records(d_sum, SUMMARY_DTYPE, S, T)
+    day = tree_reports.records(d_day, HEADROOM_DAY_DTYPE, S, n)
     reps = []
     if arrays:
         head, drop, flow = d_head.cpu().numpy(), d_drop.cpu().numpy(), d_flow.cpu().numpy()
@@ -160,48 +143,18 @@ def headroom_report_device(node_g, feeder=None, tree=None, need=0.0, rating=None
     out           a contiguous (S, tree nodes, T) float64 tensor on node_g's device that receives the headrooms and
                   stays there, e.g. for revs_net_across (study.native_across) across seeds: a cell with +inf members
                   gets numpy's NaN interpolation there."""
-    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() not in (2, 3) \
-            or not node_g.is_contiguous():
-        raise ValueError("headroom report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
-    if (feeder is None) == (tree is None):
-        raise ValueError("headroom report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
-    single = node_g.dim() == 2
-    g3 = node_g[None] if single else node_g
-    if not 1 <= g3.shape[0] <= _lib.STUDY_MAX_S:
-        raise ValueError(f"headroom report: {g3.shape[0]} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    dev = node_g.device
-
-    def run():
-        if tree is None:
-            th, tr, _keep = tree_on_device(dev, *feeder, g3.shape[1])
-            n_nodes = len(feeder[0])
-        else:
-            tr, th, n_nodes = tree
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
-        reps = native_headroom_device(lib or _lib.load(), dev, st, tr, th, n_nodes, g3, need, rating, limit_nodes, nodes,
-                                      vset, vmin, arrays, out)
-        return reps[0] if single else reps
-
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.device_report(
+        "headroom report", node_g, feeder, tree,
+        lambda *on: native_headroom_device(*on, need, rating, limit_nodes, nodes, vset, vmin, arrays, out), lib, stream)
 
 
 def report_for_tree(parent, edge_r, cons_of, node_p, need=0.0, rating=None, limit_nodes=None, nodes=None, vset=1.0,
                     vmin=0.95, arrays=True, device="cuda:0"):
     """The headroom report of node injections held on the host: node_p (M, T) or (S, M, T), row cons_of[i] injected at
     tree node i (network.report_for_tree's arguments) -> one HeadroomReport or a list of S."""
-    from .engine import _dev_check
-    _lib.load()
-    dev = _dev_check(device)
-    node_p = np.ascontiguousarray(node_p, np.float64)
-    with torch.cuda.device(dev):
-        return headroom_report_device(torch.from_numpy(node_p).to(dev), feeder=(parent, edge_r, cons_of), need=need,
-                                      rating=rating, limit_nodes=limit_nodes, nodes=nodes, vset=vset, vmin=vmin,
-                                      arrays=arrays)
+    return tree_reports.host_report(device, (node_p,), lambda g: headroom_report_device(
+        g, feeder=(parent, edge_r, cons_of), need=need, rating=rating, limit_nodes=limit_nodes, nodes=nodes, vset=vset,
+        vmin=vmin, arrays=arrays))
 
 
 def default_need(engine) -> float:

@@ -14,9 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tree_reports
 from ._lib import LOSS_DAY_DTYPE, LOSS_LINE_DAY_DTYPE, LOSS_SLOT_DTYPE, check, ptr
-from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays, tree_on_device
+from .network import SUMMARY_DTYPE, profile_node_sums, side_arrays
 
 
 @dataclass
@@ -56,33 +56,20 @@ class LossReport:
 
 
 def _position_bytes(dev, tree_host, n_nodes, sel, who):
-    """uint8 per preorder position: whether the tree node there is one of `sel` (indices or a boolean mask); None: no
-    array (the library then takes every position)."""
-    if sel is None:
-        return None
-    order = np.asarray(tree_host["order"], np.int64)
-    real = order < n_nodes
-    mk, idx = np.zeros(n_nodes, bool), np.asarray(sel)
-    if idx.dtype == bool and idx.shape != (n_nodes,):
-        raise ValueError(f"loss report: a boolean {who} mask must have one entry per tree node ({n_nodes})")
-    mk[idx if idx.dtype == bool else idx.astype(np.int64)] = True
-    return torch.from_numpy(np.ascontiguousarray((real & mk[np.where(real, order, 0)]).astype(np.uint8))).to(dev)
+    """tree_reports.position_mask of the loss report's lines= / nodes= (`who`); None: no array, every position."""
+    return tree_reports.position_mask(dev, tree_host, n_nodes, sel, "no array", ("loss report", who))
 
 
 def _position_classes(dev, tree_host, n_nodes, classes):
     """(uint8 per preorder position, C): the class of the line above the tree node there, 255 at padding positions and
-    where classes[i] < 0; None -> (None, 0)."""
+    where classes[i] < 0; None -> (None, 0).  A class of LOSS_MAX_CLASSES or more is refused."""
     if classes is None:
         return None, 0
     cl = np.asarray(classes, np.int64)
     if cl.shape != (n_nodes,) or cl.max(initial=-1) >= _lib.LOSS_MAX_CLASSES:
         raise ValueError(f"loss report: classes must hold one class below {_lib.LOSS_MAX_CLASSES} (or -1) per tree node "
                          f"({n_nodes})")
-    order = np.asarray(tree_host["order"], np.int64)
-    real = order < n_nodes
-    by_pos = np.where(real, cl[np.where(real, order, 0)], -1)
-    n_cls = int(cl.max(initial=-1)) + 1
-    return torch.from_numpy(np.ascontiguousarray(np.where(by_pos < 0, 255, by_pos).astype(np.uint8))).to(dev), n_cls
+    return tree_reports.position_classes(dev, tree_host, n_nodes, cl, _lib.LOSS_MAX_CLASSES)
 
 
 def native_losses_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, lines=None, nodes=None, classes=None,
@@ -101,9 +88,7 @@ def native_losses_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, lin
         raise ValueError(f"loss report: slot_hours must be finite and > 0, got {slot_hours}")
     if not loss_max > 0.0:
         raise ValueError(f"loss report: loss_max must be > 0 (inf allowed), got {loss_max}")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (S, n, T)
-                            or not out.is_contiguous() or out.device != node_g.device):
-        raise ValueError(f"loss report: out must be a contiguous float64 {(S, n, T)} tensor on {node_g.device}")
+    tree_reports.check_out("loss report", out, (S, n, T), node_g.device)
     d_nop, _, _ = side_arrays(dev, tree_host, n, None, None)
     d_lines = _position_bytes(dev, tree_host, n, lines, "lines")
     d_nodes = _position_bytes(dev, tree_host, n, nodes, "nodes")
@@ -122,22 +107,20 @@ def native_losses_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, lin
         if d_loss is None:
             d_loss = torch.empty(S, n, T, dtype=torch.float64, device=dev)
         d_mlf, d_drop, d_flow = (torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3))
-    d_sum = torch.zeros(S * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_slot = torch.zeros(S * T * LOSS_SLOT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_lday = torch.zeros(S * n * LOSS_LINE_DAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_day = torch.zeros(S * LOSS_DAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    nbytes = int(lib.revs_net_losses_scratch(S, T, tree_host["n"]))
-    if nbytes <= 0:
-        raise ValueError(f"loss report: no scratch size for S={S}, T={T}, tree of {tree_host['n']}")
-    d_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    d_sum = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * T)
+    d_slot = tree_reports.record_buffer(dev, LOSS_SLOT_DTYPE, S * T)
+    d_lday = tree_reports.record_buffer(dev, LOSS_LINE_DAY_DTYPE, S * n)
+    d_day = tree_reports.record_buffer(dev, LOSS_DAY_DTYPE, S)
+    d_scratch = tree_reports.scratch("loss report", lib.revs_net_losses_scratch(S, T, tree_host["n"]),
+                                     f"S={S}, T={T}, tree of {tree_host['n']}", dev)
     check(lib.revs_net_losses(S, M, T, C.byref(tree), ptr(node_g), ptr(d_lines), ptr(d_nodes), ptr(d_cls), n_cls, ptr(d_nop),
                               n, vset * vset, slot_hours, loss_max, ptr(d_cost), ptr(d_loss), ptr(d_mlf), ptr(d_drop),
                               ptr(d_flow), ptr(d_sum), ptr(d_slot), ptr(d_lday), ptr(d_day), ptr(d_scratch), stream),
           "revs_net_losses")
-    rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, T)
-    slot = d_slot.cpu().numpy().view(LOSS_SLOT_DTYPE).reshape(S, T)
-    lday = d_lday.cpu().numpy().view(LOSS_LINE_DAY_DTYPE).reshape(S, n)
-    day = d_day.cpu().numpy().view(LOSS_DAY_DTYPE).reshape(S)
+    rec = tree_reports.records(d_sum, SUMMARY_DTYPE, S, T)
+    slot = tree_reports.records(d_slot, LOSS_SLOT_DTYPE, S, T)
+    lday = tree_reports.records(d_lday, LOSS_LINE_DAY_DTYPE, S, n)
+    day = tree_reports.records(d_day, LOSS_DAY_DTYPE, S)
     if arrays:
         loss, mlf, drop, flow = (d.cpu().numpy() for d in (d_loss, d_mlf, d_drop, d_flow))
     reps = []
@@ -170,48 +153,18 @@ def loss_report_device(node_g, feeder=None, tree=None, lines=None, nodes=None, c
     out           a contiguous (S, tree nodes, T) float64 tensor on node_g's device that receives the losses and stays
                   there, e.g. for revs_net_across (study.native_across) across seeds with lo = -inf, hi = loss_max,
                   sense = +1"""
-    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() not in (2, 3) \
-            or not node_g.is_contiguous():
-        raise ValueError("loss report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
-    if (feeder is None) == (tree is None):
-        raise ValueError("loss report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
-    single = node_g.dim() == 2
-    g3 = node_g[None] if single else node_g
-    if not 1 <= g3.shape[0] <= _lib.STUDY_MAX_S:
-        raise ValueError(f"loss report: {g3.shape[0]} scenarios outside 1..{_lib.STUDY_MAX_S}")
-    dev = node_g.device
-
-    def run():
-        if tree is None:
-            th, tr, _keep = tree_on_device(dev, *feeder, g3.shape[1])
-            n_nodes = len(feeder[0])
-        else:
-            tr, th, n_nodes = tree
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
-        reps = native_losses_device(lib or _lib.load(), dev, st, tr, th, n_nodes, g3, lines, nodes, classes, cost,
-                                    slot_hours, loss_max, vset, arrays, out)
-        return reps[0] if single else reps
-
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.device_report(
+        "loss report", node_g, feeder, tree,
+        lambda *on: native_losses_device(*on, lines, nodes, classes, cost, slot_hours, loss_max, vset, arrays, out), lib, stream)
 
 
 def report_for_tree(parent, edge_r, cons_of, node_p, lines=None, nodes=None, classes=None, cost=None, slot_hours=None,
                     loss_max=float("inf"), vset=1.0, arrays=True, device="cuda:0"):
     """The loss report of node injections held on the host: node_p (M, T) or (S, M, T), row cons_of[i] injected at
     tree node i (network.report_for_tree's arguments) -> one LossReport or a list of S."""
-    from .engine import _dev_check
-    _lib.load()
-    dev = _dev_check(device)
-    node_p = np.ascontiguousarray(node_p, np.float64)
-    with torch.cuda.device(dev):
-        return loss_report_device(torch.from_numpy(node_p).to(dev), feeder=(parent, edge_r, cons_of), lines=lines,
-                                  nodes=nodes, classes=classes, cost=cost, slot_hours=slot_hours, loss_max=loss_max,
-                                  vset=vset, arrays=arrays)
+    return tree_reports.host_report(device, (node_p,), lambda g: loss_report_device(
+        g, feeder=(parent, edge_r, cons_of), lines=lines, nodes=nodes, classes=classes, cost=cost, slot_hours=slot_hours,
+        loss_max=loss_max, vset=vset, arrays=arrays))
 
 
 class LossMixin:

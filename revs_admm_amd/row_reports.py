@@ -11,12 +11,11 @@ import torch
 
 from . import _lib, baselines
 from ._lib import BILL_DTYPE, HOME_DTYPE, check, ptr
-from .bills import check_groups
+from .bills import check_groups, check_scenarios
 
 
 def check_sizes(who, S, n, T):
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"{who}: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    check_scenarios(who, S)
     if not 1 <= T <= _lib.MAX_T:
         raise ValueError(f"{who}: {T} slots outside 1..{_lib.MAX_T}")
     if n < 1 or S * n >= 2 ** 31:

@@ -14,8 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tree_reports
 from ._lib import ACROSS_DTYPE, check, ptr
+from .bills import check_scenarios
 from .network import SUMMARY_DTYPE, side_arrays, tree_on_device
 
 # revs_net_pooled_t (include/revs_admm_ops.h): revs_net_summary_t with worst_scenario in the first reserved word
@@ -149,17 +150,14 @@ def native_across(lib, stream, values, keep, groups, n_groups, lo, hi, sense, ba
     d_slot = torch.empty(G * n * T * rec, dtype=torch.uint8, device=dev) if slots else None
     d_daily = torch.empty(G * n * rec, dtype=torch.uint8, device=dev)
     d_exp = torch.empty(G, n, dtype=torch.int32, device=dev)
-    nbytes = int(lib.revs_net_across_scratch(S, n))
-    if nbytes <= 0:
-        raise ValueError(f"across report: no scratch size for S={S}, {n} nodes")
-    d_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    d_scratch = tree_reports.scratch("across report", lib.revs_net_across_scratch(S, n), f"S={S}, {n} nodes", dev)
     h_group = np.ascontiguousarray(groups, np.int32)
     h_band = np.ascontiguousarray(bands, np.float64)
     check(lib.revs_net_across(S, n, T, ptr(values), ptr(d_keep), h_group.ctypes.data, G, float(lo), float(hi), int(sense),
                               h_band.ctypes.data if B else None, B, ptr(d_slot), ptr(d_daily), ptr(d_exp),
                               ptr(d_scratch), stream), "revs_net_across")
-    slot = d_slot.cpu().numpy().view(ACROSS_DTYPE).reshape(G, n, T) if slots else None
-    return slot, d_daily.cpu().numpy().view(ACROSS_DTYPE).reshape(G, n), d_exp.cpu().numpy()
+    slot = tree_reports.records(d_slot, ACROSS_DTYPE, G, n, T) if slots else None
+    return slot, tree_reports.records(d_daily, ACROSS_DTYPE, G, n), d_exp.cpu().numpy()
 
 
 def check_across_args(bands, loading_bands):
@@ -208,10 +206,7 @@ def across_report_device(volt, loading, groups, nodes=None, rated=None, bands=(0
             raise ValueError(f"across report: rated must have one entry per node ({n}), got {keep_l.shape}")
     dev = volt.device
 
-    def run():
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
+    def run(st):
         lb = lib or (_lib.load() if dev.type == "cuda" else None)
         sv, dv, ev = native_across(lb, st, volt, keep_v, gid, G, vmin, vmax, -1, bands, slots)
         sl = dl = el = None
@@ -220,10 +215,7 @@ def across_report_device(volt, loading, groups, nodes=None, rated=None, bands=(0
         return AcrossReport(sv, sl, dv, dl, ev, el, np.bincount(gid[gid >= 0], minlength=G).astype(np.int64), bands,
                             loading_bands)
 
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.on_device(dev, stream, run)
 
 
 def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, groups, n_groups, bands, rating, nodes, vset,
@@ -239,14 +231,12 @@ def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, grou
     d_nop, d_rating, d_mask = side_arrays(dev, tree_host, n, rating, nodes)
     out = ([torch.empty(S, n, T, dtype=torch.float64, device=dev) for _ in range(3)] if arrays or across
            else [None] * 3)
-    d_sum = torch.zeros(S * 2 * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    d_sum = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * 2 * T)
     d_pool = d_scratch = d_band = None
     if G:                                   # staging only when pools are asked for
-        d_pool = torch.zeros(G * 2 * T * POOLED_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        nbytes = int(lib.revs_net_study_scratch(S, T, tree_host["n"]))
-        if nbytes <= 0:
-            raise ValueError(f"study report: no staging size for S={S}, T={T}, tree of {tree_host['n']}")
-        d_scratch = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        d_pool = tree_reports.record_buffer(dev, POOLED_DTYPE, G * 2 * T)
+        d_scratch = tree_reports.scratch("study report", lib.revs_net_study_scratch(S, T, tree_host["n"]),
+                                         f"S={S}, T={T}, tree of {tree_host['n']}", dev, "staging")
     if B:
         d_band = torch.zeros(S, T, B, dtype=torch.int32, device=dev)
     h_group = np.ascontiguousarray(groups, np.int32)
@@ -261,9 +251,8 @@ def native_study_device(lib, dev, stream, tree, tree_host, n_nodes, node_g, grou
                                    bands=bands, vmin=vmin, vmax=vmax, lib=lib, stream=stream)
     if not arrays:
         out = [None] * 3
-    rec = d_sum.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, 2, T)
-    pool = (d_pool.cpu().numpy().view(POOLED_DTYPE).reshape(G, 2, T) if G
-            else np.zeros((0, 2, T), POOLED_DTYPE))
+    rec = tree_reports.records(d_sum, SUMMARY_DTYPE, S, 2, T)
+    pool = tree_reports.records(d_pool, POOLED_DTYPE, G, 2, T) if G else np.zeros((0, 2, T), POOLED_DTYPE)
     counts = d_band.cpu().numpy() if B else np.zeros((S, T, 0), np.int32)
     flow, loading, volt = (None if o is None else o.cpu().numpy() for o in out)
     return StudyReport(rec[:, 0].copy(), rec[:, 1].copy(), pool[:, 0].copy(), pool[:, 1].copy(), counts,
@@ -305,8 +294,7 @@ def _across_kw(across):
 
 def check_study_args(S, bands, groups):
     """study_report's checks of S, bands and groups -> (bands, group ids int32 (S,), G)."""
-    if not 1 <= S <= _lib.STUDY_MAX_S:
-        raise ValueError(f"study report: {S} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    check_scenarios("study report", S)
     bands = tuple(float(b) for b in bands)
     if len(bands) > _lib.STUDY_MAX_BANDS or not np.isfinite(bands).all():
         raise ValueError(f"study report: at most {_lib.STUDY_MAX_BANDS} finite bands, got {bands}")
@@ -351,28 +339,10 @@ def study_report_device(node_g, feeder=None, tree=None, groups=None, rating=None
     on node_g's device (an engine's).  Every other argument and check as study_report's; nothing is uploaded but the
     side arrays, and StudyReport.node_p is node_g read back.  lib / stream: the library and the HIP stream of the
     launch (default: the loaded one, torch's current stream)."""
-    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() != 3 \
-            or not node_g.is_contiguous():
-        raise ValueError("study report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
-    if (feeder is None) == (tree is None):
-        raise ValueError("study report: pass the feeder either as feeder=(parent, edge_r, cons_of) or as tree=")
+    tree_reports.check_node_sums("study report", node_g, (3,), (feeder, tree), bound=False)
     check_across_groups(across, groups)
     bands, gid, G = check_study_args(node_g.shape[0], bands, groups)
-    dev = node_g.device
-
-    def run():
-        if tree is None:
-            th, tr, _keep = tree_on_device(dev, *feeder, node_g.shape[1])
-            n_nodes = len(feeder[0])
-        else:
-            tr, th, n_nodes = tree
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
-        return native_study_device(lib or _lib.load(), dev, st, tr, th, n_nodes, node_g, gid, G, bands, rating, nodes,
-                                   vset, vmin, vmax, arrays, **_across_kw(across))
-
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.run_on_device(
+        node_g, feeder, tree,
+        lambda *on: native_study_device(*on, gid, G, bands, rating, nodes, vset, vmin, vmax, arrays, **_across_kw(across)),
+        lib, stream)

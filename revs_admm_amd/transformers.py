@@ -16,7 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, tree_reports
 from ._lib import XF_DAY_DTYPE, XF_FLEET_DTYPE, check, ptr
 from .network import SUMMARY_DTYPE, profile_node_sums
 
@@ -134,9 +134,7 @@ def native_transformers_device(lib, dev, stream, node_g, xf_ptr, xf_rows, rated_
         raise ValueError(f"transformer report: one rating per transformer ({K}) expected, got {rated_kw.shape}")
     if ambient.shape != (T,):
         raise ValueError(f"transformer report: ambient must be a scalar or one value per slot ({T}), got {ambient.shape}")
-    if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != (S, K, T)
-                            or not out.is_contiguous() or out.device != node_g.device):
-        raise ValueError(f"transformer report: out must be a contiguous float64 {(S, K, T)} tensor on {node_g.device}")
+    tree_reports.check_out("transformer report", out, (S, K, T), node_g.device)
     mdl = model.struct()
     decay_to, decay_w = model.decays(slot_hours, substeps)
     up = lambda a: torch.tensor(np.asarray(a)).to(dev)           # (a copy: the caller's arrays may be read-only)
@@ -148,22 +146,19 @@ def native_transformers_device(lib, dev, stream, node_g, xf_ptr, xf_rows, rated_
         if d_hot is None:
             d_hot = torch.empty(S, K, T, dtype=torch.float64, device=dev)
         d_load, d_ratio, d_oil, d_faa = (torch.empty(S, K, T, dtype=torch.float64, device=dev) for _ in range(4))
-    d_sr = torch.zeros(S * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_sh = torch.zeros(S * T * SUMMARY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_day = torch.zeros(S * K * XF_DAY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    d_fleet = torch.zeros(S * XF_FLEET_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-    nbytes = int(lib.revs_xf_report_scratch(S, T, K))
-    if nbytes <= 0:
-        raise ValueError(f"transformer report: no scratch size for S={S}, T={T}, K={K}")
-    d_scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    d_sr = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * T)
+    d_sh = tree_reports.record_buffer(dev, SUMMARY_DTYPE, S * T)
+    d_day = tree_reports.record_buffer(dev, XF_DAY_DTYPE, S * K)
+    d_fleet = tree_reports.record_buffer(dev, XF_FLEET_DTYPE, S)
+    d_scratch = tree_reports.scratch("transformer report", lib.revs_xf_report_scratch(S, T, K), f"S={S}, T={T}, K={K}", dev)
     check(lib.revs_xf_report(S, M, T, K, len(xf_rows), ptr(node_g), ptr(d_ptr), ptr(d_rows) if len(xf_rows) else None,
                              ptr(d_rated), ptr(d_amb), C.byref(mdl), slot_hours, substeps, decay_to, decay_w, cyclic, to0,
                              w0, over_ratio, hot_limit, ptr(d_load), ptr(d_ratio), ptr(d_oil), ptr(d_hot), ptr(d_faa),
                              ptr(d_sr), ptr(d_sh), ptr(d_day), ptr(d_fleet), ptr(d_scratch), stream), "revs_xf_report")
-    sr = d_sr.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, T)
-    sh = d_sh.cpu().numpy().view(SUMMARY_DTYPE).reshape(S, T)
-    day = d_day.cpu().numpy().view(XF_DAY_DTYPE).reshape(S, K)
-    fleet = d_fleet.cpu().numpy().view(XF_FLEET_DTYPE).reshape(S)
+    sr = tree_reports.records(d_sr, SUMMARY_DTYPE, S, T)
+    sh = tree_reports.records(d_sh, SUMMARY_DTYPE, S, T)
+    day = tree_reports.records(d_day, XF_DAY_DTYPE, S, K)
+    fleet = tree_reports.records(d_fleet, XF_FLEET_DTYPE, S)
     host = [d.cpu().numpy() if arrays else [None] * S for d in (d_load, d_ratio, d_oil, d_hot, d_faa)]
     return [TransformerReport(*(a[s] for a in host), sr[s].copy(), sh[s].copy(), day[s].copy(), fleet[s].copy(), rated_kw,
                               slot_hours, over_ratio, hot_limit) for s in range(S)]
@@ -204,31 +199,19 @@ def transformer_report_device(node_g, xf_of, rated_kva, pf=0.95, ambient=30.0, m
     arrays        False: the records only
     out           a contiguous (S, K, T) float64 tensor on node_g's device that receives the hot-spots and stays there,
                   e.g. for revs_net_across (study.native_across) across seeds with hi = hot_limit, sense = +1"""
-    if not isinstance(node_g, torch.Tensor) or node_g.dtype != torch.float64 or node_g.dim() not in (2, 3) \
-            or not node_g.is_contiguous():
-        raise ValueError("transformer report: node_g must be a contiguous (scenarios, rows, slots) float64 tensor")
-    single = node_g.dim() == 2
-    g3 = node_g[None] if single else node_g
-    if not 1 <= g3.shape[0] <= _lib.STUDY_MAX_S:
-        raise ValueError(f"transformer report: {g3.shape[0]} scenarios outside 1..{_lib.STUDY_MAX_S}")
+    single, g3 = tree_reports.check_node_sums("transformer report", node_g)
     K = int(np.asarray(rated_kva).shape[0]) if np.asarray(rated_kva).ndim else int(np.max(xf_of, initial=-1)) + 1
     xf_ptr, xf_rows = build_csr(xf_of, g3.shape[1], max(K, 1))
     rated_kw = _ratings(rated_kva, pf, max(K, 1))
     dev = node_g.device
 
-    def run():
-        st = stream
-        if st is None and dev.type == "cuda":
-            st = torch.cuda.current_stream(dev).cuda_stream
+    def run(st):
         reps = native_transformers_device(lib or _lib.load(), dev, st, g3, xf_ptr, xf_rows, rated_kw,
                                           _ambient(ambient, g3.shape[2]), model, slot_hours, substeps, initial, over_ratio,
                                           hot_limit, arrays, out)
         return reps[0] if single else reps
 
-    if dev.type != "cuda":          # (a host stand-in of the kernels: no device to make current)
-        return run()
-    with torch.cuda.device(dev):
-        return run()
+    return tree_reports.on_device(dev, stream, run)
 
 
 def report_for_rows(node_p_host, xf_of, rated_kva, device="cuda:0", **kw):

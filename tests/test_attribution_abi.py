@@ -128,3 +128,23 @@ def test_python_entry_checks_its_arguments():
         attribution_report_device(g)
     with pytest.raises(ValueError, match="either as feeder"):
         attribution_report_device(g, feeder=feeder, tree=(None, None, 3))
+
+
+def test_class_array_takes_a_class_out_of_range_as_no_class():
+    """attribution.class_array refuses only a wrong length before tree_reports.position_classes: 4 or more, like a
+    negative entry, is no class (255), not an error."""
+    import torch
+    from revs_admm_amd.attribution import class_array
+    from revs_admm_amd.feeder import feeder_tree
+    parent = np.array([-1, 0, 1, 1, 0])
+    th = feeder_tree(parent, np.ones(5), np.array([-1, 0, -1, 1, 2]), np.ones(3, bool))
+    order = np.asarray(th["order"])
+    real = order < 5
+    dev = torch.device("cpu")
+    cls = np.array([1, 4, -1, 0, 9])
+    by_pos, n_cls = class_array(dev, th, 5, cls)
+    want = np.where((cls >= 0) & (cls < 4), cls, 255)
+    assert n_cls == 2 and (by_pos.numpy() == np.where(real, want[np.where(real, order, 0)], 255)).all()
+    assert class_array(dev, th, 5, np.full(5, 7))[1] == 0
+    with pytest.raises(ValueError, match=r"attribution report: classes must have one entry per tree node \(5\), got \(4,\)"):
+        class_array(dev, th, 5, np.zeros(4, int))

@@ -113,3 +113,22 @@ def test_python_entry_checks_its_arguments():
         headroom_report_device(g)
     with pytest.raises(ValueError, match="either as feeder"):
         headroom_report_device(g, feeder=feeder, tree=(None, None, 3))
+
+
+def test_position_mask_reads_none_as_the_nodes_with_a_row():
+    """headroom.position_mask is tree_reports.position_mask with none="rows": None is the nodes that carry a row, a
+    selection is that selection, by position; a boolean mask's length is not checked here (who=None)."""
+    import torch
+    from revs_admm_amd.feeder import feeder_tree
+    from revs_admm_amd.headroom import position_mask
+    parent, cons_of = np.array([-1, 0, 1, 1, 0]), np.array([-1, 0, -1, 1, 2])     # rows at the nodes 1, 3 and 4
+    th = feeder_tree(parent, np.ones(5), cons_of, np.ones(3, bool))
+    order = np.asarray(th["order"])
+    real = order < 5
+    dev = torch.device("cpu")
+    with_row = np.isin(order, [1, 3, 4]) & real
+    assert (position_mask(dev, th, 5, None).numpy() == with_row).all() and with_row.sum() == 3
+    want = real & np.isin(order, [0, 2])
+    assert (position_mask(dev, th, 5, [0, 2]).numpy() == want).all()
+    assert (position_mask(dev, th, 5, np.array([True, False, True, False, False])).numpy() == want).all()
+    assert position_mask(dev, th, 5, None).dtype == torch.uint8

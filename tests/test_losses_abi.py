@@ -126,3 +126,28 @@ def test_python_entry_checks_its_arguments():
     for kw, msg in ((dict(vset=0.0), "vset"), (dict(slot_hours=-1.0), "slot_hours"), (dict(loss_max=float("nan")), "loss_max")):
         with pytest.raises(ValueError, match=msg):
             native_losses_device(None, g.device, None, None, None, 3, g, **kw)
+
+
+def test_position_builders_of_the_loss_report():
+    """losses._position_bytes is tree_reports.position_mask with none="no array" and the length check of a boolean mask;
+    losses._position_classes refuses a class of 4 or more, and a wrong length, before tree_reports.position_classes."""
+    import torch
+    from revs_admm_amd.feeder import feeder_tree
+    from revs_admm_amd.losses import _position_bytes, _position_classes
+    parent = np.array([-1, 0, 1, 1, 0])
+    th = feeder_tree(parent, np.ones(5), np.array([-1, 0, -1, 1, 2]), np.ones(3, bool))
+    order = np.asarray(th["order"])
+    real = order < 5
+    dev = torch.device("cpu")
+    assert _position_bytes(dev, th, 5, None, "lines") is None
+    assert (_position_bytes(dev, th, 5, [1, 4], "lines").numpy() == (real & np.isin(order, [1, 4]))).all()
+    with pytest.raises(ValueError, match=r"loss report: a boolean nodes mask must have one entry per tree node \(5\)"):
+        _position_bytes(dev, th, 5, np.ones(4, bool), "nodes")
+    assert _position_classes(dev, th, 5, None) == (None, 0)
+    cls = np.array([0, 2, -1, 1, -7])
+    by_pos, n_cls = _position_classes(dev, th, 5, cls)
+    assert n_cls == 3 and (by_pos.numpy() == np.where(real, np.where(cls < 0, 255, cls)[np.where(real, order, 0)], 255)).all()
+    assert _position_classes(dev, th, 5, np.full(5, -1))[1] == 0
+    for bad in (np.array([0, 1, 2, 3, 4]), np.zeros(4, int)):
+        with pytest.raises(ValueError, match=r"loss report: classes must hold one class below 4 \(or -1\) per tree node \(5\)"):
+            _position_classes(dev, th, 5, bad)
