@@ -1114,6 +1114,83 @@ int revs_net_attribution(int32_t S, int32_t m, int32_t T, const revs_tree_t *tre
                          double *ev_contrib_out, double *drop_out, revs_attr_slot_t *slot_out,
                          revs_net_summary_t *summary_out, revs_attr_day_t *day_out, void *scratch, void *stream);
 
+/* ---- risk report: undervoltage odds under forecast error (csrc/risk_kernels.hip) -----------------------
+ * The node sums are a forecast.  With independent zero-mean errors of variance s2[i] at the rows (node_var) and K shared
+ * factors of unit variance with loadings beta_k[i] (node_common), the linear model drop = R g gives
+ *   Var(drop[j]) = sum_i R[j][i]^2 s2[i] + sum_k ((R beta_k)[j])^2
+ * and, with R[j][i] = wc[lca(i, j)] (revs_headroom_aux_t), the first term is the sum over j's ancestors-or-self a of
+ * w2[a] Q[a], Q the subtree sums of s2 and w2[a] = wc[a]^2 - wc[parent(a)]^2.  Positions j = 0 .. tree->n - 1 are
+ * feeder_tree's preorder positions.  Inputs, DEVICE arrays unless said otherwise:
+ *   node_var     double[S][m][T]  variance of the independent error of each row's node sum; NULL: all +0.0
+ *   node_common  double[K][S][m][T], K in 0..REVS_RISK_MAX_COMMON: the loadings of the shared factors; NULL with K = 0
+ *   w2           double[tree->n]  per position w[j] (2.0 wc[j] - w[j]), the subtraction and the product each rounded once,
+ *                +0.0 at padding positions (feeder.risk_weights, from aux_host's wc)
+ *   z_max        (by value) the standard deviations of margin a node must keep, finite and >= 0: a node is at risk when
+ *                z < z_max.  For a probability p_max it is the standard normal's quantile at 1 - p_max.
+ * Per (scenario s, slot t), every operation one IEEE double operation rounded on its own (no fused multiply-add), drop
+ * the bits of revs_net_report's scans, "flow scan" and "drop scan" those scans on other inputs:
+ *   var_ind[j] = max(0, drop scan with w2 in place of w of (flow scan of the gathered node_var))      (+0.0 for a -0.0)
+ *   c_k[j]     = drop scan of node_common[k]: exactly the drop's code path
+ *   var[j]     = (var_ind[j] + c_0[j] c_0[j]) + c_1[j] c_1[j]          k ascending, the product, then the sum
+ *   sd[j]      = sqrt(var[j]), correctly rounded
+ *   slack[j]   = drop_max - drop[j]
+ *   z[j]       = slack[j] / sd[j]; where sd[j] = 0: +inf when slack[j] >= 0, -inf when slack[j] < 0
+ *   drop_q[j]  = drop[j] + z_max sd[j]     the drop that is exceeded with probability p_max (the "secure" drop)
+ *   prob[j]    = 0.5 erfc(z[j] 0.70710678118654752)     P(drop + error > drop_max) for Gaussian errors; erfc is the
+ *                device library's: a few ulp, not correctly rounded
+ * var_ind's and c_k's bits depend on the launch shape as the drop's do; var_ind is within 2 n 2^-53 sum |w2 Q| of any order.
+ * Bad slot: a non-finite node_g, node_var or node_common at a row of the tree, or a negative node_var.  Then every double
+ * of the slot is a NaN (sd, z, prob, drop_q, the slot record), n_bad = 1, the counts 0, z_min_index -1, the summary has
+ * count 0 and n_nan = the positions summarised; drop_out is what the scans give.  One flag for the workgroup; nothing
+ * traps.
+ * The covered positions of the slot record and the summary: limit_mask != 0 (NULL: every position with a row), out_mask
+ * != 0 (NULL: all) and a caller-side index.  Outputs, any may be NULL, not all:
+ *   sd_out, z_out, prob_out, drop_q_out, drop_out   double[S][n_out][T] in the caller's node order (node_of_pos, n_out as
+ *                revs_net_report's)
+ *   slot_out     revs_risk_slot_t[S][T] over the covered positions: expected = the sum of prob, the root of ONE fixed
+ *                binary tree exactly as the loss report's (values by position, +0.0 where not covered, padded to the next
+ *                power of two, x[i] = x[2i] + x[2i + 1]); n_risky = positions with z < z_max; n_det = positions with drop >
+ *                drop_max (what revs_net_report counts); z_min and z_min_index (ties to the lowest caller-side index), sd_at
+ *                / drop_at = sd and drop there; sd_max; none covered: the four doubles NaN, the index -1, expected +0.0
+ *   summary_out  revs_net_summary_t[S][T]: the box-plot record of drop_q over the covered positions (a second launch,
+ *                box_select64 and the rules of boxplot.h); n_violations = positions with drop_q > drop_max; worst_value /
+ *                worst_index = the largest drop_q and the lowest caller-side index that attains it
+ *   day_out      revs_risk_day_t[S][n_out], every node with a caller-side index, over the slots that are not bad: prob_max
+ *                and its earliest slot, z_min, n_risky = the slots with z < z_max, expected_slots = the sum of prob from
+ *                +0.0 in ascending slot order; every slot bad: NaN, -1, NaN, 0, +0.0
+ * Enqueues only (up to three launches on `stream`): capturable, no allocation, no synchronisation.  REVS_EINVAL before any
+ * launch: every case of revs_net_headroom's list that applies (S, T, m, node_g, the tree, n_out, the aux struct, drop_max
+ * not finite, every output NULL); K outside 0..REVS_RISK_MAX_COMMON; node_common NULL with K > 0; a NULL w2; z_max not
+ * finite or < 0; summary_out or day_out without a 16-byte aligned scratch of revs_net_risk_scratch bytes (24 S T tree_n:
+ * drop_q, prob and z by position; 0 for a bad size). */
+#define REVS_RISK_MAX_COMMON 2
+typedef struct {
+    double expected;                  /* sum of prob: the expected number of covered nodes below the limit */
+    double z_min;                     /* the smallest margin in standard deviations */
+    double sd_at;                     /* sd at z_min_index */
+    double drop_at;                   /* drop at z_min_index */
+    double sd_max;                    /* the largest sd */
+    int32_t n_risky;                  /* positions with z < z_max */
+    int32_t n_det;                    /* positions with drop > drop_max */
+    int32_t z_min_index;              /* the lowest caller-side index that attains z_min; -1 */
+    int32_t n_bad;                    /* 1: a bad slot, every double above a NaN */
+    int32_t reserved[2];
+} revs_risk_slot_t;                   /* 64 bytes */
+typedef struct {
+    double prob_max;                  /* the day's largest prob (NaN: every slot is bad) */
+    double z_min;                     /* the day's smallest z */
+    double expected_slots;            /* sum over the slots of prob */
+    int32_t prob_max_slot;            /* the earliest slot of prob_max; -1 */
+    int32_t n_risky;                  /* slots with z < z_max */
+} revs_risk_day_t;                    /* 32 bytes */
+int64_t revs_net_risk_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_risk(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const revs_headroom_aux_t *aux_host,
+                  const double *node_g, const double *node_var, const double *node_common, int32_t K, const double *w2,
+                  const uint8_t *limit_mask, const uint8_t *out_mask, const int32_t *node_of_pos, int32_t n_out,
+                  double drop_max, double z_max, double *sd_out, double *z_out, double *prob_out, double *drop_q_out,
+                  double *drop_out, revs_risk_slot_t *slot_out, revs_net_summary_t *summary_out, revs_risk_day_t *day_out,
+                  void *scratch, void *stream);
+
 /* ---- transformer report: loading, hot-spot and loss of life of the service transformers (csrc/transformer_kernels.hip,
  * DESIGN.md 3.17) --------------------------------------------------------------------------------------------------------
  * K transformers, each serving a list of rows of the node sums node_g (double[S][m][T], revs_net_node_sums' layout):

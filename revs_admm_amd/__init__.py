@@ -12,6 +12,8 @@
     losses         AdmmEngine.loss_report: line losses, marginal loss per node, the day's lost energy and its cost
     attribution    AdmmEngine.attribution_report: which nodes' load causes the worst node's voltage drop, and the EVs'
                    part of it: AttributionReport, attribution_report_device
+    risk           AdmmEngine.risk_report: the odds of undervoltage per node and slot when the net load is a forecast
+                   with independent and shared errors: RiskReport, risk_report_device
     transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
     flexibility    how much charging can still be moved: FlexReport, flexibility_report / flexibility_report_device -- up and
                    down reserve per EV, node and slot, the slot a car is ready at and the slack it leaves

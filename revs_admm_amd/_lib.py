@@ -240,6 +240,16 @@ ATTR_DAY_DTYPE = np.dtype([("sum", "<f8"), ("ev_sum", "<f8"), ("peak", "<f8"), (
 assert ATTR_DAY_DTYPE.itemsize == 32
 ATTR_MAX_CLASSES = 4
 
+# numpy mirrors of revs_risk_slot_t and revs_risk_day_t (include/revs_admm_ops.h)
+RISK_SLOT_DTYPE = np.dtype([("expected", "<f8"), ("z_min", "<f8"), ("sd_at", "<f8"), ("drop_at", "<f8"), ("sd_max", "<f8"),
+                            ("n_risky", "<i4"), ("n_det", "<i4"), ("z_min_index", "<i4"), ("n_bad", "<i4"),
+                            ("reserved", "<i4", (2,))])
+assert RISK_SLOT_DTYPE.itemsize == 64
+RISK_DAY_DTYPE = np.dtype([("prob_max", "<f8"), ("z_min", "<f8"), ("expected_slots", "<f8"), ("prob_max_slot", "<i4"),
+                           ("n_risky", "<i4")])
+assert RISK_DAY_DTYPE.itemsize == 32
+RISK_MAX_COMMON = 2      # REVS_RISK_MAX_COMMON
+
 # numpy mirrors of revs_xf_day_t and revs_xf_fleet_t (include/revs_admm_ops.h)
 XF_DAY_DTYPE = np.dtype([("peak_ratio", "<f8"), ("peak_hot", "<f8"), ("energy_kwh", "<f8"), ("age_hours", "<f8"),
                          ("lol_percent", "<f8"), ("feqa", "<f8"), ("peak_ratio_slot", "<i4"), ("peak_hot_slot", "<i4"),
@@ -408,6 +418,9 @@ SIGNATURES = {
     "revs_net_attribution_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_attribution": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _p, _p, _i32,
                                        _p, _i32, _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_risk_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_risk": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _i32, _p, _p, _p, _p,
+                                _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
                                  _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

@@ -153,6 +153,31 @@ class EnsembleReportMixin:
                                                      node_ev, watch, limit_nodes, nodes, classes, self.vset, self.vlow,
                                                      frac, arrays)
 
+    def risk_reports(self, rel_sd=0.1, ev_rel_sd=0.0, common=None, sd_profile=None, p_max=0.05, limit_nodes=None, nodes=None,
+                     arrays=True, profile=None) -> list:
+        """AdmmEngine.risk_report for every scenario -> S risk.RiskReports from 2 + K node-sum launches and one
+        revs_net_risk over all S (scenario s: the bits of the single engine's report on it).  profile: the EV part, see
+        node_sums (None: the schedules P_sch); the injections are LOAD + profile.  rel_sd, ev_rel_sd, sd_profile, common,
+        p_max: as AdmmEngine.risk_report's, sd_profile and a loading profile in node_sums' forms.  The run's state is
+        read, never written."""
+        from . import risk
+        tree, tree_host, n_nodes = self._report_tree()
+        items = risk.common_spec("risk_reports", common)
+        risk.z_of(p_max)                                         # (refused before anything is launched)
+        ev = self._report_profile(profile)
+        load = self.load.view(ev.shape)
+        node_g = self.node_sums(ev, True)
+        sd = self._report_profile(sd_profile) if sd_profile is not None else float(rel_sd) * load + float(ev_rel_sd) * ev
+        node_var = self.node_sums((sd * sd).contiguous(), False)
+        loads = []
+        for it in items:
+            if isinstance(it, tuple):
+                it = (float(it[1]) * (load if it[0] == "load" else ev)).contiguous()
+            loads.append(self.node_sums(it, False))
+        node_common = torch.stack(loads).contiguous() if loads else None
+        return risk.native_risk_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, node_var,
+                                       node_common, limit_nodes, nodes, self.vset, self.vlow, p_max, arrays)
+
     def loss_reports(self, lines=None, nodes=None, classes=None, cost=None, slot_hours=None, loss_max=float("inf"),
                      arrays=True, profile=None, add_load=False, out=None) -> list:
         """AdmmEngine.loss_report for every scenario -> S losses.LossReports from one node-sum launch and one

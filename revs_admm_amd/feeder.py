@@ -127,6 +127,19 @@ def headroom_aux(tree):
     return dict(parent_pos=parent.astype(np.int32), wc=wc, jump=jump, n_jump=n_jump, depth=depth)
 
 
+def risk_weights(tree, aux=None):
+    """Host-side preparation of revs_net_risk's w2 (include/revs_admm_ops.h) from the dict of feeder_tree and that of
+    headroom_aux (None: formed here), by preorder position: w2[j] = w[j] * (2.0 * wc[j] - w[j]), the subtraction and the
+    product each rounded once (the doubling is exact) -- wc[j]^2 - wc[parent(j)]^2 with wc[parent(j)] = wc[j] - w[j]
+    factored, so that a zero-weight edge gives exactly 0 and nothing is cancelled.  With it the path sum over j's
+    ancestors-or-self a of w2[a] Q[a], Q the subtree sums of s2, is sum_i wc[lca(i, j)]^2 s2[i].  Padding positions
+    (weightless roots) hold +0.0."""
+    ax = headroom_aux(tree) if aux is None else aux
+    w, wc = np.asarray(tree["w"], np.float64), np.asarray(ax["wc"], np.float64)
+    w2 = w * (2.0 * wc - w)
+    return np.where(w == 0.0, 0.0, w2)                     # (+0.0, never -0.0, where the edge weighs nothing)
+
+
 def tree_from_R(R, rtol=1e-12):
     """Recover a radial feeder from its LinDistFlow matrix alone (reference lpsolver.py:17-26, 184-189: callers
     of the solver hold R = 2 F D F^T restricted to the residence nodes, not the network).  For a radial feeder

@@ -125,7 +125,7 @@ class REVS:
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              transformers=False, flexibility=False, attribution=False, **opt):
+              transformers=False, flexibility=False, attribution=False, risk=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -202,7 +202,13 @@ class REVS:
         among those that carry residences, per node its contribution to that drop and the EVs' part of it -- from the
         report's own rows; the EV part is those rows minus the base load's, formed once in float64; counted and
         summarised over `community`, against opt vmin; one launch for all scenarios on either path (its arrays are read
-        back with opt arrays).  False: nothing of it runs."""
+        back with opt arrays).  False: nothing of it runs.
+        risk=True or a dict of rel_sd (0.1), ev_rel_sd (0.0), common, p_max (0.05) and limit_nodes: StudyReport.risk, every
+        scenario's risk.RiskReport -- per node and slot the odds of falling below opt vmin when the report's rows are a
+        forecast: each residence's independent error has the standard deviation rel_sd x its base load + ev_rel_sd x its
+        EV part (the row minus the base load), common lists up to two shared factors, ("load", c) / ("ev", c) or a
+        loading array shaped like the rows; formed once in float64, counted and summarised over `community`; one launch
+        for all scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -373,7 +379,26 @@ class REVS:
             return attribution_report_device(node_g, (node_g - base[None]).contiguous(), feeder=(parent, edge_r, cons_of),
                                              vset=opt.get("report_vset", 1.0), vmin=opt.get("vmin", 0.95),
                                              arrays=opt.get("arrays", False), **kw)
+
+        def risk_reports(node_g):
+            import torch
+            from .risk import common_spec, risk_report_device
+            kw = dict(risk if isinstance(risk, dict) else {})
+            base = torch.from_numpy(np.array([all_homes[h] for h in res], np.float64)).to(node_g.device)
+            ev = node_g - base[None]
+            sd = float(kw.pop("rel_sd", 0.1)) * base[None] + float(kw.pop("ev_rel_sd", 0.0)) * ev
+            loads = []
+            for it in common_spec("REVS.study", kw.pop("common", None)):
+                if isinstance(it, tuple):
+                    loads.append(float(it[1]) * (base[None].expand_as(node_g) if it[0] == "load" else ev))
+                else:
+                    loads.append(torch.as_tensor(np.asarray(it, np.float64), device=node_g.device).expand_as(node_g))
+            kw.setdefault("nodes", [pos[h] for h in community])
+            return risk_report_device(node_g, (sd * sd).contiguous(), torch.stack(loads).contiguous() if loads else None,
+                                      feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
+                                      vmin=opt.get("vmin", 0.95), arrays=opt.get("arrays", False), **kw)
         want_xf = transformers is True or isinstance(transformers, dict)
+        want_risk = risk is True or isinstance(risk, dict)
         want_attr = attribution is True or isinstance(attribution, dict)
         if device_report:
             import torch
@@ -407,6 +432,8 @@ class REVS:
                 rep.flexibility = flexibility_report()
             if want_attr:
                 rep.attribution = attribution_reports(buf)
+            if want_risk:
+                rep.risk = risk_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -437,6 +464,9 @@ class REVS:
         if want_attr:
             import torch
             rep.attribution = attribution_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if want_risk:
+            import torch
+            rep.risk = risk_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -86,7 +86,8 @@ class StudyReport:
     None.  headroom / losses / transformers: every scenario's headroom.HeadroomReport / losses.LossReport /
     transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None.  flexibility: the
     flexibility.FlexReport of REVS.study(flexibility=True) over the study's scenarios, else None.  attribution: every
-    scenario's attribution.AttributionReport of REVS.study(attribution=True), else None."""
+    scenario's attribution.AttributionReport of REVS.study(attribution=True), else None.  risk: every scenario's
+    risk.RiskReport of REVS.study(risk=True), else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -112,6 +113,7 @@ class StudyReport:
     transformers: list | None = None
     flexibility: object | None = None
     attribution: list | None = None
+    risk: list | None = None
 
     @property
     def n_groups(self):
