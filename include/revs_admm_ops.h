@@ -1191,6 +1191,105 @@ int revs_net_risk(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host,
                   double *drop_out, revs_risk_slot_t *slot_out, revs_net_summary_t *summary_out, revs_risk_day_t *day_out,
                   void *scratch, void *stream);
 
+/* ---- price report: nodal prices, congestion rent and line value from the voltage rows' multipliers
+ * (csrc/price_kernels.hip) ---------------------------------------------------------------------------------
+ * The first report of the dual side.  y are the signed multipliers of the voltage rows vlow^2 - vset^2 <= R g <= vhigh^2 -
+ * vset^2 in the operator's convention (y > 0 where the upper row binds: load pulls R g up, so prices rise downstream of
+ * a congested line), s the scale of L(s y).  With R = sum_e w_e 1_sub(e) 1_sub(e)^T, d = R y is the network report's two
+ * scans on y, and g^T R y = sum_e w_e P_e Y_e.  Positions j = 0 .. tree->n - 1 are feeder_tree's preorder positions.
+ * node_g and node_y are DEVICE double[S][m][T]; node_y is gathered through the tree's src exactly as node_g is (a
+ * multiplier of a row the tree does not carry is dropped).  scale: DEVICE double[S], NULL: 1.0.  cost: DEVICE double[T].
+ * Per (scenario, slot t), every operation an IEEE double operation rounded on its own (no fused multiply-add), w[j] =
+ * tree->w[j] = 2 r[j]:
+ *   inj, mu    the gathered node_g / node_y (+0.0 at a position without a row)
+ *   flow, drop revs_net_report's bits on node_g
+ *   Y[j]       the flow scan of mu: the bits revs_net_report's flow gives when fed node_y            -> line_y_out
+ *   d[j]       the drop scan of w[j] Y[j]: the bits revs_net_report's drop gives when fed node_y
+ *   cong[j]    s d[j]                                                                               -> cong_out
+ *   mlf[j]     with_loss != 0: revs_net_losses' mlf at the same vset2 (its bits; den = vset2 - drop, c = (w flow) / den,
+ *              the path sums of c in the drop scan's form); else +0.0
+ *   lossp[j]   cost[t] mlf[j]                                                                       -> lossp_out
+ *   price[j]   (cost[t] + lossp[j]) + cong[j]                                                       -> price_out
+ *   rent[j]    ((w[j] Y[j]) flow[j]) s + 0.0: what the line above j collects (the last addition makes a zero
+ *              rent +0.0 whatever the flow's sign; w = 0 gives +0.0)                                 -> rent_out
+ * Bad slot: a gathered inj or mu is not finite; the scenario's s is not finite or not >= 0; with_loss and den[j] > 0
+ * fails at a position with a caller-side index.  Then every price, cong, lossp, rent and every double of the slot record
+ * is a NaN, the indices are -1, n_priced and n_rows are 0, n_bad is 1, and the summary has count 0 and n_nan = the nodes
+ * summarised; drop_out, flow_out and line_y_out are what the scans give.  One flag for the workgroup; nothing traps.
+ * Sums over positions: each the root of ONE fixed binary tree exactly as the loss report's.
+ * Outputs, any may be NULL, not all:
+ *   price_out, cong_out, lossp_out, line_y_out, rent_out, drop_out, flow_out   double[S][n_out][T] in the caller's node
+ *                  order (node_of_pos, n_out as revs_net_report's)
+ *   summary_out    revs_net_summary_t[S][T]: the box-plot record of price over the nodes with node_mask[j] != 0 (NULL: all)
+ *                  and a caller-side index (a second launch, box_select64 and the rules of boxplot.h); worst_value = the
+ *                  largest price, worst_index the lowest caller-side index that attains it; n_violations = nodes with
+ *                  price > price_cap (+inf allowed)
+ *   slot_out       revs_price_slot_t[S][T]: delivered = sum of inj; energy_pay = cost[t] delivered; loss_pay = sum of
+ *                  inj lossp and cong_pay = sum of inj cong over the masked nodes (node_mask, caller-side index);
+ *                  rent_total = sum of rent over the lines with line_mask[j] != 0 (NULL: all) and a caller-side index;
+ *                  price_max, price_min, cong_max over the masked nodes, each with the lowest caller-side index that
+ *                  attains it (NaN / -1 when there is none); n_priced = masked nodes with cong != 0; n_rows = positions
+ *                  with mu != 0; n_bad
+ *   node_day_out   revs_price_node_day_t[S][n_out]: paid = the sum from +0.0 in ascending slot order of the rounded
+ *                  products inj price, multiplied once by slot_hours; cong_paid by the same rule on inj cong; peak_price /
+ *                  peak_slot = the largest price and its earliest slot; a bad slot makes the doubles NaN and the slot -1
+ *   line_day_out   revs_loss_line_day_t[S][n_out], the loss report's layout and rule on rent: energy = the day's rent
+ *   day_out        revs_price_day_t[S]: the four payments by the same rule over the slot records; peak_price = the largest
+ *                  slot price_max, peak_slot its earliest slot, peak_index that slot's price_max_index (NaN / -1 with a
+ *                  bad slot); n_bad_slots; n_cong_slots = slots with n_rows > 0; top_index[8] / top_rent[8] = the eight
+ *                  summarised lines of largest day rent in descending order, NaNs left out, ties to the lowest caller
+ *                  index, unused entries -1 / NaN
+ * Enqueues only (up to four launches on `stream`): capturable, no allocation, no synchronisation.  REVS_EINVAL before any
+ * launch: S outside 1..REVS_STUDY_MAX_S; T outside 1..REVS_MAX_T; m outside 1..65535; a null node_g, node_y or cost; a tree
+ * over REVS_TREE_MAX, not padded or NULL; n_out outside 1..tree->n; with_loss and vset2 not finite and > 0; slot_hours not
+ * finite and > 0; a NaN price_cap; every output NULL; summary_out, node_day_out, line_day_out or day_out without a 16-byte
+ * aligned scratch of revs_net_prices_scratch bytes (32 S T tree_n: price, rent, inj price and inj cong by position, + 96 S T:
+ * the slot records, + 8 S tree_n: the lines' day rents; 0 for a bad size).  A call with the scratch also parks the flows
+ * and lossp of each (scenario, slot) in its rent and inj price cells until they are overwritten: the same results from
+ * fewer registers. */
+typedef struct {
+    double delivered;                 /* sum of the injections */
+    double energy_pay;                /* cost[t] delivered */
+    double loss_pay;                  /* sum of inj lossp over the masked nodes */
+    double cong_pay;                  /* sum of inj cong over the masked nodes */
+    double rent_total;                /* sum of rent over the summarised lines */
+    double price_max, price_min;      /* over the masked nodes */
+    double cong_max;
+    int32_t price_max_index;          /* the lowest caller-side index that attains each; -1 */
+    int32_t price_min_index;
+    int32_t cong_max_index;
+    int32_t n_priced;                 /* masked nodes with cong != 0 */
+    int32_t n_rows;                   /* positions with mu != 0 */
+    int32_t n_bad;                    /* 1: a bad slot, every double above a NaN */
+    int32_t reserved[2];
+} revs_price_slot_t;                  /* 96 bytes */
+typedef struct {
+    double paid;                      /* (sum over the slots of inj price) slot_hours */
+    double cong_paid;                 /* (sum over the slots of inj cong) slot_hours */
+    double peak_price;                /* the largest price of the day */
+    int32_t peak_slot;                /* its earliest slot; -1 with a bad slot */
+    int32_t reserved;
+} revs_price_node_day_t;              /* 32 bytes */
+typedef struct {
+    double energy_pay, loss_pay;      /* (sum over the slots of the slot record's field) slot_hours */
+    double cong_pay, rent_total;
+    double peak_price;                /* the largest slot price_max */
+    double top_rent[8];               /* day rents of the lines top_index, descending; NaN: unused */
+    int32_t top_index[8];             /* caller-side indices; -1: unused */
+    int32_t peak_slot, peak_index;
+    int32_t n_bad_slots;
+    int32_t n_cong_slots;             /* slots with n_rows > 0 */
+    int32_t reserved[2];
+} revs_price_day_t;                   /* 160 bytes */
+int64_t revs_net_prices_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_prices(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const double *node_g,
+                    const double *node_y, const double *scale, const double *cost, const uint8_t *line_mask,
+                    const uint8_t *node_mask, const int32_t *node_of_pos, int32_t n_out, double vset2, int32_t with_loss,
+                    double slot_hours, double price_cap, double *price_out, double *cong_out, double *lossp_out,
+                    double *line_y_out, double *rent_out, double *drop_out, double *flow_out,
+                    revs_net_summary_t *summary_out, revs_price_slot_t *slot_out, revs_price_node_day_t *node_day_out,
+                    revs_loss_line_day_t *line_day_out, revs_price_day_t *day_out, void *scratch, void *stream);
+
 /* ---- transformer report: loading, hot-spot and loss of life of the service transformers (csrc/transformer_kernels.hip,
  * DESIGN.md 3.17) --------------------------------------------------------------------------------------------------------
  * K transformers, each serving a list of rows of the node sums node_g (double[S][m][T], revs_net_node_sums' layout):

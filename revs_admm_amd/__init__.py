@@ -14,6 +14,9 @@
                    part of it: AttributionReport, attribution_report_device
     risk           AdmmEngine.risk_report: the odds of undervoltage per node and slot when the net load is a forecast
                    with independent and shared errors: RiskReport, risk_report_device
+    prices         AdmmEngine.price_report: nodal prices (energy, marginal loss, congestion) from the voltage rows'
+                   multipliers, the rent every line collects and what reinforcing it would save: PriceReport,
+                   price_report_device
     transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
     flexibility    how much charging can still be moved: FlexReport, flexibility_report / flexibility_report_device -- up and
                    down reserve per EV, node and slot, the slot a car is ready at and the slack it leaves

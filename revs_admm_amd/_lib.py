@@ -250,6 +250,22 @@ RISK_DAY_DTYPE = np.dtype([("prob_max", "<f8"), ("z_min", "<f8"), ("expected_slo
 assert RISK_DAY_DTYPE.itemsize == 32
 RISK_MAX_COMMON = 2      # REVS_RISK_MAX_COMMON
 
+# numpy mirrors of revs_price_slot_t, revs_price_node_day_t and revs_price_day_t (include/revs_admm_ops.h); the lines' day
+# records are LOSS_LINE_DAY_DTYPE
+PRICE_SLOT_DTYPE = np.dtype([("delivered", "<f8"), ("energy_pay", "<f8"), ("loss_pay", "<f8"), ("cong_pay", "<f8"),
+                             ("rent_total", "<f8"), ("price_max", "<f8"), ("price_min", "<f8"), ("cong_max", "<f8"),
+                             ("price_max_index", "<i4"), ("price_min_index", "<i4"), ("cong_max_index", "<i4"),
+                             ("n_priced", "<i4"), ("n_rows", "<i4"), ("n_bad", "<i4"), ("reserved", "<i4", (2,))])
+assert PRICE_SLOT_DTYPE.itemsize == 96
+PRICE_NODE_DAY_DTYPE = np.dtype([("paid", "<f8"), ("cong_paid", "<f8"), ("peak_price", "<f8"), ("peak_slot", "<i4"),
+                                 ("reserved", "<i4")])
+assert PRICE_NODE_DAY_DTYPE.itemsize == 32
+PRICE_DAY_DTYPE = np.dtype([("energy_pay", "<f8"), ("loss_pay", "<f8"), ("cong_pay", "<f8"), ("rent_total", "<f8"),
+                            ("peak_price", "<f8"), ("top_rent", "<f8", (8,)), ("top_index", "<i4", (8,)),
+                            ("peak_slot", "<i4"), ("peak_index", "<i4"), ("n_bad_slots", "<i4"), ("n_cong_slots", "<i4"),
+                            ("reserved", "<i4", (2,))])
+assert PRICE_DAY_DTYPE.itemsize == 160
+
 # numpy mirrors of revs_xf_day_t and revs_xf_fleet_t (include/revs_admm_ops.h)
 XF_DAY_DTYPE = np.dtype([("peak_ratio", "<f8"), ("peak_hot", "<f8"), ("energy_kwh", "<f8"), ("age_hours", "<f8"),
                          ("lol_percent", "<f8"), ("feqa", "<f8"), ("peak_ratio_slot", "<i4"), ("peak_hot_slot", "<i4"),
@@ -421,6 +437,9 @@ SIGNATURES = {
     "revs_net_risk_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_risk": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), C.POINTER(HeadroomAux), _p, _p, _p, _i32, _p, _p, _p, _p,
                                 _i32, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_prices_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_prices": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _p, _p, _p, _i32, _f64, _i32, _f64, _f64,
+                                  _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
                                  _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

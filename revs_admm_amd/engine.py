@@ -35,6 +35,7 @@ from .headroom import HeadroomMixin, HeadroomReport  # noqa: F401  (re-exported)
 from .losses import LossMixin, LossReport  # noqa: F401  (re-exported)
 from .attribution import AttributionMixin, AttributionReport  # noqa: F401  (re-exported)
 from .risk import RiskMixin, RiskReport  # noqa: F401  (re-exported)
+from .prices import PriceMixin, PriceReport  # noqa: F401  (re-exported)
 from .transformers import TransformerMixin, TransformerReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
@@ -210,7 +211,7 @@ def _on_current_stream(fn):
 
 class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
                  LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin, TransformerMixin, FlexMixin,
-                 AttributionMixin, RiskMixin):
+                 AttributionMixin, RiskMixin, PriceMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

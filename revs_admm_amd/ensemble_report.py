@@ -193,6 +193,29 @@ class EnsembleReportMixin:
         return losses.native_losses_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, lines, nodes,
                                            classes, cost, slot_hours, loss_max, self.vset, arrays, out)
 
+    def price_reports(self, multipliers="operator", scale=1.0, with_loss=True, lines=None, nodes=None, cost=None,
+                      slot_hours=None, price_cap=float("inf"), arrays=True, profile=None) -> list:
+        """AdmmEngine.price_report for every scenario -> S prices.PriceReports from one node-sum launch and one
+        revs_net_prices over all S (scenario s: the bits of the single engine's report on it).  multipliers: "operator",
+        the dual Newton path's current y -- yd[0] viewed (M, S, T) and brought to (S, M, T); zero on the ADMM forms' path
+        and when the last solve left no row with a multiplier -- or an (S, M, T) array.  scale: a scalar or one value
+        per scenario (certificates()[s].scale).  cost: None, the ensemble's own tariff.  profile: the EV part, see
+        node_sums (None: the schedules P_sch); the injections are LOAD + profile.  The run's state is read, never
+        written."""
+        from . import prices
+        tree, tree_host, n_nodes = self._report_tree()
+        M, S, T = self.M, self.S_count, self.T_slot
+        if isinstance(multipliers, str):
+            y = prices.operator_multipliers(self, multipliers, (M, S, T), "price_reports").permute(1, 0, 2).contiguous()
+        else:
+            y = prices.operator_multipliers(self, multipliers, (S, M, T), "price_reports")
+        prices.scales_of(scale, S)                               # (refused before anything is launched)
+        if cost is None:
+            cost = self.cost.to(torch.float64)
+        node_g = self.node_sums(profile, True)
+        return prices.native_prices_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, y, scale, cost,
+                                           with_loss, lines, nodes, slot_hours, price_cap, self.vset, arrays)
+
     def transformer_reports(self, xf_of, rated_kva, pf=0.95, ambient=30.0, model=None, slot_hours=None, substeps=1,
                             initial="cyclic", over_ratio=1.0, hot_limit=110.0, arrays=True, profile=None, add_load=False,
                             out=None) -> list:

@@ -155,7 +155,7 @@ def split_scenarios(S: int, T: int):
 def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=15, vset=1.0, vlow=0.95,
                     vhigh=1.05, *, mode="binary", device="cuda:0", operator: OperatorOptions = None, feeder=None,
                     return_certificates=False, return_node_sums=False, return_convergence=None,
-                    convergence_groups=None, convergence_patience=8, return_charging=False):
+                    convergence_groups=None, convergence_patience=8, return_charging=False, return_multipliers=False):
     """solve_ADMM for many scenarios on one graph -> [(diff, P_sch, S, C), ...], one tuple per `homes` dict of
     `homes_list`, each as solve_ADMM returns it.  The scenarios run side by side as ensembles (ensemble.AdmmEnsemble,
     DESIGN.md section 3.9) of at most REVS_ENS_MAX_COLS // T scenarios; the feeder's matrix and tree are formed once.
@@ -178,7 +178,11 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
     empty list gives None for the report.
     return_charging=True: the charger power of every scenario is appended last to the tuple as ONE (n, len(homes_list),
     T) float32 tensor on the device, residences in `res` order -- charging.charging_report_device's layout.  Every
-    ensemble's slice is copied from its own S on the device before it is released; an empty list gives None."""
+    ensemble's slice is copied from its own S on the device before it is released; an empty list gives None.
+    return_multipliers=True: the voltage rows' multipliers of every scenario are appended last of all as ONE
+    (len(homes_list), M, T) float64 tensor on the device, rows as node_g's -- prices.price_report_device's node_y: the
+    dual Newton path's y after the last iteration, zero where its last solve left no row with a multiplier
+    (prices.operator_multipliers); an empty list gives None."""
     import torch
     from .ensemble import AdmmEnsemble
     res = [n for n in graph if graph.nodes[n]["label"] == "H"]
@@ -206,9 +210,10 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
         extra = ((certs,) if return_certificates else ()) + ((node_g,) if return_node_sums else ())
         extra += (conv,) if want_conv else ()
         extra += (charge_p,) if return_charging else ()
+        extra += (mult,) if return_multipliers else ()
         return (out,) + extra if extra else out
 
-    charge_p = None
+    charge_p = mult = None
     if not parts:
         return answer([], [], torch.empty(0, len(res), T, dtype=torch.float64, device=device)
                       if return_node_sums else None)
@@ -243,6 +248,11 @@ def solve_ADMM_many(homes_list, graph, cost, grbpath=None, kappa=5.0, iter_max=1
                 charge_p = torch.empty(len(res), len(recs), T, dtype=torch.float32, device=eng.dev)
             inv = torch.from_numpy(np.ascontiguousarray(eng.inv_perm, dtype=np.int64)).to(eng.dev)
             charge_p[:, a:b] = eng.S.view(len(res), b - a, T).index_select(0, inv)
+        if return_multipliers:
+            from .prices import operator_multipliers
+            if mult is None:
+                mult = torch.empty(len(recs), eng.M, T, dtype=torch.float64, device=eng.dev)
+            mult[a:b] = operator_multipliers(eng, "operator", (eng.M, b - a, T), "solve_ADMM_many").permute(1, 0, 2)
         if return_node_sums:
             if node_g is None:
                 node_g = torch.empty(len(recs), eng.M, T, dtype=torch.float64, device=eng.dev)

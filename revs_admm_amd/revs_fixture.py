@@ -111,21 +111,23 @@ class REVS:
 
     def get_distributed_optimal(self, tariff, homes, dist, save=False, **kwargs):
         """revs_fixture.py:251-280; note the reference reads 'vlow'/'vhigh' (not
-        'vmin'/'vmax') here, defaulting to 0.95 / 1.05."""
-        diff, Pres, Pev, soc = solve_ADMM(
+        'vmin'/'vmax') here, defaulting to 0.95 / 1.05.  return_engine=True: -> (Pres, Pev, soc, engine), the
+        AdmmEngine that solved it (its multipliers: REVS.study(prices=...))."""
+        diff, Pres, Pev, soc, *eng = solve_ADMM(
             homes, dist, tariff, None, kappa=kwargs.get("kappa", 5.0),
             iter_max=kwargs.get("max_iterations", 15), vset=kwargs.get("v0", 1.03),
             vlow=kwargs.get("vlow", 0.95), vhigh=kwargs.get("vhigh", 1.05),
-            mode=kwargs.get("mode", "binary"), device=self.device, feeder=kwargs.get("feeder"))
+            mode=kwargs.get("mode", "binary"), device=self.device, feeder=kwargs.get("feeder"),
+            return_engine=bool(kwargs.get("return_engine", False)))
         if save:
             self._save(combine_result(Pres, Pev, soc, kwargs.get("ev_homes"), diff),
                        kwargs.get("adoption", 90), kwargs.get("rating", 4800), kwargs.get("seed"))
-        return Pres, Pev, soc
+        return (Pres, Pev, soc) + tuple(eng)
 
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              transformers=False, flexibility=False, attribution=False, risk=False, **opt):
+              transformers=False, flexibility=False, attribution=False, risk=False, prices=False, **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -208,7 +210,14 @@ class REVS:
         forecast: each residence's independent error has the standard deviation rel_sd x its base load + ev_rel_sd x its
         EV part (the row minus the base load), common lists up to two shared factors, ("load", c) / ("ev", c) or a
         loading array shaped like the rows; formed once in float64, counted and summarised over `community`; one launch
-        for all scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs."""
+        for all scenarios on either path (its arrays are read back with opt arrays).  False: nothing of it runs.
+        prices=True or a dict of price_report_device's options (scale, with_loss, lines, nodes, slot_hours, price_cap,
+        cost): StudyReport.prices, every scenario's prices.PriceReport -- per node and slot the price (energy + marginal
+        loss + congestion), per line the congestion rent -- from the report's own rows under the study's tariff and the
+        multipliers of the scenario's voltage rows: those the operator holds after the last iteration of a
+        "distributed" scenario (on either path), zero for every other method, whose schedules no voltage row shapes:
+        their prices are energy and loss alone; against opt report_vset; one launch for all scenarios on either path
+        (its arrays are read back with opt arrays).  False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -239,6 +248,8 @@ class REVS:
         # deferred: (position in profiles, homes) of the ensemble's scenarios; owners: every scenario's EV homes
         labels, profiles, deferred, owners = [], [], [], []
         want_p = bool(charging or flexibility)
+        want_prices = prices is True or isinstance(prices, dict)
+        mults = []                                 # prices: every scenario's row multipliers (None: zero)
         charge_p, charge_rec = [], []              # charging / flexibility: every scenario's charger power (None: deferred), records
         for adoption in adoptions:
             for rating in ratings:
@@ -251,6 +262,7 @@ class REVS:
                     for method in methods:
                         labels.append(dict(method=method, adoption=adoption, rating=rating, seed=seed))
                         owners.append(ev_homes)
+                        mults.append(None)
                         if want_p:
                             charge_rec.append(homes_to_arrays(homes, res)[1])
                             charge_p.append(None)
@@ -258,7 +270,13 @@ class REVS:
                             deferred.append((len(profiles), homes))
                             profiles.append(None)
                             continue
-                        if method == "distributed":
+                        if method == "distributed" and want_prices:
+                            from .prices import operator_multipliers
+                            P_res, P_ev, _, eng = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder,
+                                                                               return_engine=True, **opt)
+                            mults[-1] = operator_multipliers(eng, "operator", (eng.M, eng.T), "REVS.study").cpu().numpy()
+                            del eng
+                        elif method == "distributed":
                             P_res, P_ev = self.get_distributed_optimal(tariff, homes, dist, feeder=feeder, **opt)[:2]
                         elif method in RULE_METHODS:
                             sol, status = solve_uncontrolled(homes, len(tariff), policy=method,
@@ -281,7 +299,13 @@ class REVS:
                                    return_certificates=certify, return_node_sums=device_report,
                                    return_convergence=convergence,
                                    convergence_groups=self._deferred_groups(labels, keys, [i for i, _ in deferred]),
-                                   convergence_patience=opt.get("patience", 8), return_charging=want_p)
+                                   convergence_patience=opt.get("patience", 8), return_charging=want_p,
+                                   return_multipliers=want_prices)
+            if want_prices:
+                *head, mult_dev = sols
+                sols = tuple(head) if len(head) > 1 else head[0]
+                for k, (i, _) in enumerate(deferred):
+                    mults[i] = mult_dev[k]
             if want_p:
                 *head, charge_dev = sols
                 sols = tuple(head) if len(head) > 1 else head[0]
@@ -397,6 +421,18 @@ class REVS:
             return risk_report_device(node_g, (sd * sd).contiguous(), torch.stack(loads).contiguous() if loads else None,
                                       feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
                                       vmin=opt.get("vmin", 0.95), arrays=opt.get("arrays", False), **kw)
+
+        def price_reports(node_g):
+            import torch
+            from .prices import price_report_device
+            kw = dict(cost=np.asarray(tariff, np.float64))
+            kw.update(prices if isinstance(prices, dict) else {})
+            node_y = torch.zeros_like(node_g)
+            for s, y in enumerate(mults):
+                if y is not None:
+                    node_y[s].copy_(y if isinstance(y, torch.Tensor) else torch.from_numpy(y))
+            return price_report_device(node_g, node_y, feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
+                                       arrays=opt.get("arrays", False), **kw)
         want_xf = transformers is True or isinstance(transformers, dict)
         want_risk = risk is True or isinstance(risk, dict)
         want_attr = attribution is True or isinstance(attribution, dict)
@@ -434,6 +470,8 @@ class REVS:
                 rep.attribution = attribution_reports(buf)
             if want_risk:
                 rep.risk = risk_reports(buf)
+            if want_prices:
+                rep.prices = price_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -467,6 +505,9 @@ class REVS:
         if want_risk:
             import torch
             rep.risk = risk_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if want_prices:
+            import torch
+            rep.prices = price_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -87,7 +87,8 @@ class StudyReport:
     transformers.TransformerReport of REVS.study(headroom= / losses= / transformers=), else None.  flexibility: the
     flexibility.FlexReport of REVS.study(flexibility=True) over the study's scenarios, else None.  attribution: every
     scenario's attribution.AttributionReport of REVS.study(attribution=True), else None.  risk: every scenario's
-    risk.RiskReport of REVS.study(risk=True), else None."""
+    risk.RiskReport of REVS.study(risk=True), else None.  prices: every scenario's prices.PriceReport of
+    REVS.study(prices=True), else None."""
     summary_loading: np.ndarray
     summary_volt: np.ndarray
     pooled_loading: np.ndarray
@@ -114,6 +115,7 @@ class StudyReport:
     flexibility: object | None = None
     attribution: list | None = None
     risk: list | None = None
+    prices: list | None = None
 
     @property
     def n_groups(self):
