@@ -15,7 +15,8 @@
  * every node could take in every slot, and what limits it, revs_net_losses: what the feeder loses carrying a
  * schedule, per line, per node at the margin, per slot and per day, revs_xf_report: what a schedule does to the
  * service transformers -- load ratio, top-oil and hot-spot temperature per slot, loss of insulation life per day -- and
- * last revs_flex_report: how much of the charging can still be moved, up and down, per EV, node and slot.
+ * revs_flex_report: how much of the charging can still be moved, up and down, per EV, node and slot.  revs_net_powerflow
+ * (beside the other tree reports) solves the nonlinear branch-flow equations that all of them linearise.
  */
 #ifndef REVS_ADMM_OPS_H
 #define REVS_ADMM_OPS_H
@@ -1289,6 +1290,89 @@ int revs_net_prices(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_hos
                     double *line_y_out, double *rent_out, double *drop_out, double *flow_out,
                     revs_net_summary_t *summary_out, revs_price_slot_t *slot_out, revs_price_node_day_t *node_day_out,
                     revs_loss_line_day_t *line_day_out, revs_price_day_t *day_out, void *scratch, void *stream);
+
+/* ---- power-flow report: branch-flow voltages, losses and the linear model's error (csrc/powerflow_kernels.hip, DESIGN.md
+ * 3.22) ------------------------------------------------------------------------------------------------------------------
+ * The nonlinear branch-flow (DistFlow) equations of the radial feeder, which the linear model v^2 = vset^2 - R g of every
+ * other report approximates, solved per (scenario s, slot t) by a fixed-point iteration over the network report's two
+ * scans.  Positions j = 0 .. tree->n - 1 are feeder_tree's preorder positions; every operation is an IEEE double
+ * operation rounded on its own (no fused multiply-add).  w[j] = tree->w[j] = 2 r[j]; xw[j] = 2 x[j] (DEVICE double[tree->n]
+ * by position, 16-byte aligned, or NULL: active power only); inj[j] the gathered node sum (+0.0 without a row);
+ * qinj[j] = tan_phi inj[j] (with xw only).  P[j], Q[j]: the receiving-end flows on the line above j; u[j]: the squared
+ * voltage at j.
+ *   cur[j] = (P[j] P[j] + Q[j] Q[j]) / u[j]      (without xw: (P[j] P[j]) / u[j])
+ *   lp[j]  = (0.5 w[j]) cur[j]                   lq[j] = (0.5 xw[j]) cur[j]
+ *   P[j]   = (the flow scan of inj + lp at j) - lp[j]        Q[j] = (the flow scan of qinj + lq at j) - lq[j]
+ *   u[j]   = vset2 - the path scan at j of the terms ((w P + xw Q) + 0.5 (w lp + xw lq)), each product rounded, the sums
+ *            in the order written
+ * Pass 0 takes lp = lq = 0 and adds nothing for them: without xw its P and vset2 - u are revs_net_report's flow and drop
+ * (the same bits); with xw its u is the linear model with the reactive term xw Q.  Pass k >= 1 forms cur, lp, lq from pass
+ * k - 1's P, Q, u and runs the scans again.  The loop ends behind the first pass k >= 1 with max |u_new - u_old| <= tol vset2
+ * over the positions with a caller-side index (iters = k, status 0), or behind pass max_iter (status 3).  loss_out is the
+ * lp the last pass used: P, Q, u satisfy the flow and voltage equations with it, and it is cur of the pass before.
+ * status per (s, t): 0 converged; 1 a row's injection is not finite; 2 collapse, u[j] > 0 fails at a position with a
+ * caller-side index in some pass (pass 0 included); 3 max_iter reached.  With status != 0 every value of volt_out,
+ * flow_out, loss_out and qflow_out of the slot is a NaN, every double of its slot record a NaN, its indices -1 and its
+ * counts 0, and the summary has count 0; volt_lin_out stays what pass 0 gives.  One flag per workgroup; nothing traps.
+ * Sums over positions: each the root of ONE fixed binary tree exactly as the loss report's.
+ *   volt_out = sqrt(u), volt_lin_out = sqrt(pass 0's u) (a NaN where that is negative), flow_out = P, loss_out = lp,
+ *   qflow_out = Q (needs xw): double[S][n_out][T] in the caller's node order, any may be NULL
+ *   summary_out    revs_net_summary_t[S][T]: the box-plot record of volt over the positions with node_mask[j] != 0
+ *                  (NULL: all) and a caller-side index; n_violations = nodes with volt < vmin; worst_value / worst_index
+ *                  = the lowest voltage and the lowest caller index that attains it
+ *   slot_out       revs_pf_slot_t[S][T]: loss_total / qloss_total = the sums of lp / lq over the positions with a
+ *                  caller-side index, delivered = the sum of inj, supplied = delivered + loss_total; over the masked
+ *                  nodes volt_min / volt_min_index, err_max / err_index = the largest volt_lin - volt (both: the lowest
+ *                  index on ties), n_below (volt < vmin), n_below_lin (volt_lin < vmin), n_missed (volt < vmin and not
+ *                  volt_lin < vmin); iters, status
+ *   node_day_out   revs_pf_node_day_t[S][n_out]: over the slots whose voltage is no NaN the lowest and its earliest slot
+ *                  (NaN / -1: none), slots_below, slots_missed
+ *   day_out        revs_pf_day_t[S]: energy_lost / energy_delivered = the slots' loss_total / delivered summed from +0.0
+ *                  in slot order, multiplied once by slot_hours (a NaN with a bad slot); cost = the sum of the rounded
+ *                  products loss_total[t] cost[t], times slot_hours (cost: DEVICE double[T]; NULL: a NaN); the day's
+ *                  lowest voltage with its earliest slot and that slot's node; the slots' counts added; iters_max;
+ *                  n_bad_slots = slots with status != 0
+ * Enqueues only (up to four launches on `stream`): capturable, no allocation, no synchronisation.  The state of the
+ * iteration lives in the scratch, so every call needs it.  REVS_EINVAL before any launch: the tree and size checks of
+ * revs_net_losses; vset2, slot_hours or tol not finite and > 0; vmin not finite; max_iter outside 1..REVS_PF_MAX_ITER;
+ * tan_phi not finite; tan_phi != 0 with xw == NULL; xw not 16-byte aligned; qflow_out without xw; every output NULL; a
+ * null or not 16-byte aligned scratch of revs_net_powerflow_scratch bytes (6 x 8 S T tree_n: u, then the voltages staged
+ * by position; pass 0's voltages; P; Q; lp; lq, + 80 S T: the slot records; 0 for a bad size). */
+#define REVS_PF_MAX_ITER 64
+typedef struct {
+    double loss_total, qloss_total;   /* kW / kvar lost on the lines */
+    double delivered, supplied;       /* sum of inj; delivered + loss_total */
+    double volt_min;                  /* the lowest voltage over the masked nodes */
+    double err_max;                   /* the largest volt_lin - volt over the masked nodes */
+    int32_t volt_min_index, err_index;
+    int32_t n_below, n_below_lin;     /* masked nodes below vmin by branch flow / by the linear model */
+    int32_t n_missed;                 /* below by branch flow and not by the linear model */
+    int32_t iters;                    /* passes behind pass 0 */
+    int32_t status;                   /* 0 converged, 1 not finite, 2 collapse, 3 max_iter */
+    int32_t reserved;
+} revs_pf_slot_t;                     /* 80 bytes */
+typedef struct {
+    double volt_min;                  /* the day's lowest voltage at the node */
+    int32_t slot;                     /* its earliest slot; -1 */
+    int32_t slots_below, slots_missed;
+    int32_t reserved;
+} revs_pf_node_day_t;                 /* 24 bytes */
+typedef struct {
+    double energy_lost, energy_delivered;     /* (sum over the slots of loss_total / delivered) slot_hours */
+    double cost;                      /* (sum over the slots of loss_total[t] cost[t]) slot_hours; NaN without cost */
+    double volt_min;                  /* the day's lowest voltage */
+    int32_t volt_min_slot, volt_min_index;
+    int32_t n_below, n_below_lin, n_missed;   /* node-slots */
+    int32_t iters_max, n_bad_slots;
+    int32_t reserved;
+} revs_pf_day_t;                      /* 64 bytes */
+int64_t revs_net_powerflow_scratch(int32_t S, int32_t T, int32_t tree_n);
+int revs_net_powerflow(int32_t S, int32_t m, int32_t T, const revs_tree_t *tree_host, const double *node_g,
+                       const double *xw, double tan_phi, const uint8_t *node_mask, const int32_t *node_of_pos,
+                       int32_t n_out, double vset2, double vmin, double tol, int32_t max_iter, double slot_hours,
+                       const double *cost, double *volt_out, double *volt_lin_out, double *flow_out, double *loss_out,
+                       double *qflow_out, revs_net_summary_t *summary_out, revs_pf_slot_t *slot_out,
+                       revs_pf_node_day_t *node_day_out, revs_pf_day_t *day_out, void *scratch, void *stream);
 
 /* ---- transformer report: loading, hot-spot and loss of life of the service transformers (csrc/transformer_kernels.hip,
  * DESIGN.md 3.17) --------------------------------------------------------------------------------------------------------

@@ -17,6 +17,8 @@
     prices         AdmmEngine.price_report: nodal prices (energy, marginal loss, congestion) from the voltage rows'
                    multipliers, the rent every line collects and what reinforcing it would save: PriceReport,
                    price_report_device
+    powerflow      AdmmEngine.powerflow_report: the nonlinear branch-flow voltages, flows and losses beside the linear
+                   model's, and the undervoltages the linear model misses: PowerFlowReport, powerflow_report_device
     transformers   AdmmEngine.transformer_report: the service transformers' loading, hot-spot and loss of life
     flexibility    how much charging can still be moved: FlexReport, flexibility_report / flexibility_report_device -- up and
                    down reserve per EV, node and slot, the slot a car is ready at and the slack it leaves

@@ -266,6 +266,21 @@ PRICE_DAY_DTYPE = np.dtype([("energy_pay", "<f8"), ("loss_pay", "<f8"), ("cong_p
                             ("reserved", "<i4", (2,))])
 assert PRICE_DAY_DTYPE.itemsize == 160
 
+# numpy mirrors of revs_pf_slot_t, revs_pf_node_day_t and revs_pf_day_t (include/revs_admm_ops.h)
+PF_SLOT_DTYPE = np.dtype([("loss_total", "<f8"), ("qloss_total", "<f8"), ("delivered", "<f8"), ("supplied", "<f8"),
+                          ("volt_min", "<f8"), ("err_max", "<f8"), ("volt_min_index", "<i4"), ("err_index", "<i4"),
+                          ("n_below", "<i4"), ("n_below_lin", "<i4"), ("n_missed", "<i4"), ("iters", "<i4"),
+                          ("status", "<i4"), ("reserved", "<i4")])
+assert PF_SLOT_DTYPE.itemsize == 80
+PF_NODE_DAY_DTYPE = np.dtype([("volt_min", "<f8"), ("slot", "<i4"), ("slots_below", "<i4"), ("slots_missed", "<i4"),
+                              ("reserved", "<i4")])
+assert PF_NODE_DAY_DTYPE.itemsize == 24
+PF_DAY_DTYPE = np.dtype([("energy_lost", "<f8"), ("energy_delivered", "<f8"), ("cost", "<f8"), ("volt_min", "<f8"),
+                         ("volt_min_slot", "<i4"), ("volt_min_index", "<i4"), ("n_below", "<i4"), ("n_below_lin", "<i4"),
+                         ("n_missed", "<i4"), ("iters_max", "<i4"), ("n_bad_slots", "<i4"), ("reserved", "<i4")])
+assert PF_DAY_DTYPE.itemsize == 64
+PF_MAX_ITER = 64         # REVS_PF_MAX_ITER
+
 # numpy mirrors of revs_xf_day_t and revs_xf_fleet_t (include/revs_admm_ops.h)
 XF_DAY_DTYPE = np.dtype([("peak_ratio", "<f8"), ("peak_hot", "<f8"), ("energy_kwh", "<f8"), ("age_hours", "<f8"),
                          ("lol_percent", "<f8"), ("feqa", "<f8"), ("peak_ratio_slot", "<i4"), ("peak_hot_slot", "<i4"),
@@ -440,6 +455,9 @@ SIGNATURES = {
     "revs_net_prices_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_net_prices": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _p, _p, _p, _p, _p, _i32, _f64, _i32, _f64, _f64,
                                   _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "revs_net_powerflow_scratch": (_i64, [_i32, _i32, _i32]),
+    "revs_net_powerflow": (C.c_int, [_i32, _i32, _i32, C.POINTER(Tree), _p, _p, _f64, _p, _p, _i32, _f64, _f64, _f64, _i32,
+                                     _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "revs_xf_report_scratch": (_i64, [_i32, _i32, _i32]),
     "revs_xf_report": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, C.POINTER(XfModel), _f64, _i32, _f64,
                                  _f64, _i32, _f64, _f64, _f64, _f64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p]),

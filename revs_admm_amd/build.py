@@ -21,7 +21,7 @@ SOURCES = ["runtime.cpp", "plan_newton.cpp", "plan_fold.cpp", "plan_stream.cpp",
            "across_kernels.hip", "bill_kernels.hip", "convergence_kernels.hip", "rule_kernels.hip",
            "load_profile_kernels.hip", "charge_kernels.hip", "headroom_kernels.hip", "losses_kernels.hip",
            "transformer_kernels.hip", "flex_kernels.hip", "attribution_kernels.hip", "risk_kernels.hip",
-           "price_kernels.hip"]
+           "price_kernels.hip", "powerflow_kernels.hip"]
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "tuning.h"), os.path.join(CSRC, "select_body.h"),
            os.path.join(CSRC, "tree_body.h"), os.path.join(CSRC, "boxplot.h"), os.path.join(CSRC, "fixed_tree.h"),
            os.path.join(CSRC, "internal.h"), os.path.join(CSRC, "plan.h"), os.path.join(CSRC, "rows_pass.h"),

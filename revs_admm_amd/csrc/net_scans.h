@@ -1,6 +1,6 @@
 // The two block scans over the feeder tree that every tree report opens with (DESIGN.md sections 3.7, 3.15, 3.16, 3.19
-// 3.20 and 3.21), and what goes with them, as pieces a report's kernel is put together from: headroom_kernels.hip's,
-// losses_kernels.hip's, risk_kernels.hip's and price_kernels.hip's are.  A report whose flow and drop come from these pieces carries the bytes of revs_net_report.
+// 3.20, 3.21 and 3.22), and what goes with them, as pieces a report's kernel is put together from: headroom_kernels.hip's,
+// losses_kernels.hip's, risk_kernels.hip's, price_kernels.hip's and powerflow_kernels.hip's (every pass of its loop) are.  A report whose flow and drop come from these pieces carries the bytes of revs_net_report.
 // network_kernels.hip and attribution_kernels.hip hold the same scans in their own text: put together from these pieces
 // net_report_kernel and net_attr_kernel were 1 to 2% slower on grids of 30 and more scenarios
 // (profiles/net_scans_refactor_times.json).  A change to a scan is made in the three places.

@@ -36,6 +36,7 @@ from .losses import LossMixin, LossReport  # noqa: F401  (re-exported)
 from .attribution import AttributionMixin, AttributionReport  # noqa: F401  (re-exported)
 from .risk import RiskMixin, RiskReport  # noqa: F401  (re-exported)
 from .prices import PriceMixin, PriceReport  # noqa: F401  (re-exported)
+from .powerflow import PowerFlowMixin, PowerFlowReport  # noqa: F401  (re-exported)
 from .transformers import TransformerMixin, TransformerReport  # noqa: F401  (re-exported)
 from .operator_admm import AdmmFormsMixin
 from .operator_newton import DualNewtonMixin
@@ -211,7 +212,7 @@ def _on_current_stream(fn):
 
 class AdmmEngine(DualNewtonMixin, AdmmFormsMixin, SteadyStateMixin, CertificateMixin, NetworkMixin, RuleScheduleMixin,
                  LoadProfileMixin, ChargingMixin, HeadroomMixin, LossMixin, TransformerMixin, FlexMixin,
-                 AttributionMixin, RiskMixin, PriceMixin):
+                 AttributionMixin, RiskMixin, PriceMixin, PowerFlowMixin):
     """State of one ADMM run on one GPU.
 
     Parameters

@@ -193,6 +193,20 @@ class EnsembleReportMixin:
         return losses.native_losses_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, lines, nodes,
                                            classes, cost, slot_hours, loss_max, self.vset, arrays, out)
 
+    def powerflow_reports(self, edge_x=None, power_factor=1.0, nodes=None, vmin=0.95, tol=1e-12, max_iter=32, cost=None,
+                          slot_hours=None, arrays=True, profile=None) -> list:
+        """AdmmEngine.powerflow_report for every scenario -> S powerflow.PowerFlowReports from one node-sum launch and one
+        revs_net_powerflow over all S (scenario s: the bits of the single engine's report on it).  cost: None, the
+        ensemble's own tariff.  profile: the EV part, see node_sums (None: the schedules P_sch); the injections are
+        LOAD + profile.  The run's state is read, never written."""
+        from . import powerflow
+        tree, tree_host, n_nodes = self._report_tree()
+        if cost is None:
+            cost = self.cost.to(torch.float64)
+        node_g = self.node_sums(profile, True)
+        return powerflow.native_powerflow_device(self.lib, self.dev, self.stream, tree, tree_host, n_nodes, node_g, edge_x,
+                                                 power_factor, nodes, self.vset, vmin, tol, max_iter, cost, slot_hours, arrays)
+
     def price_reports(self, multipliers="operator", scale=1.0, with_loss=True, lines=None, nodes=None, cost=None,
                       slot_hours=None, price_cap=float("inf"), arrays=True, profile=None) -> list:
         """AdmmEngine.price_report for every scenario -> S prices.PriceReports from one node-sum launch and one

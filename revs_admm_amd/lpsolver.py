@@ -87,6 +87,28 @@ def feeder_arrays(graph, res):
     return parent, edge_r, cons_of
 
 
+def feeder_reactances(graph, res):
+    """edge_x beside feeder_arrays' edge_r: the reactance `x` of the edge from every non-substation node to its parent
+    (the same walk, the same node order), or None where an edge of the graph carries no `x`."""
+    nonsub = [n for n in graph.nodes if graph.nodes[n]["label"] != "S"]
+    roots = [n for n in graph.nodes if graph.nodes[n]["label"] == "S"]
+    if len(roots) != 1 or graph.number_of_edges() != graph.number_of_nodes() - 1:
+        raise ValueError("feeder_reactances expects a radial feeder with one substation node")
+    if any("x" not in d for _, _, d in graph.edges(data=True)):
+        return None
+    pos = {n: i for i, n in enumerate(nonsub)}
+    edge_x = np.zeros(len(nonsub))
+    seen, stack = {roots[0]}, [roots[0]]
+    while stack:
+        u = stack.pop()
+        for v in graph.neighbors(u):
+            if v not in seen:
+                seen.add(v)
+                edge_x[pos[v]] = graph.edges[u, v]["x"]
+                stack.append(v)
+    return edge_x
+
+
 def homes_to_arrays(homes, res):
     """Reference `homes` dict -> (LOAD (n,T), revs_home_t records) in `res` order."""
     load = np.array([homes[h]["LOAD"] for h in res], dtype=np.float64)

@@ -127,7 +127,8 @@ class REVS:
     def study(self, tariff, all_homes, dist, community, adoptions, ratings, seeds,
               methods=("distributed", "individual"), group_by="method", ensemble=False, certify=False, device_report=False,
               across=False, bills=False, convergence=None, load_profile=False, charging=False, headroom=None, losses=False,
-              transformers=False, flexibility=False, attribution=False, risk=False, prices=False, **opt):
+              transformers=False, flexibility=False, attribution=False, risk=False, prices=False, powerflow=False,
+              **opt):
         """The grid of scenarios the reference's study scripts read back from disk (test-dist-ind-opt.py:219-342
         compare_method / compare_rating / compare_adoption, test-dist-ind-adopt.py:73-117 compare_node_counts), run
         and reported in one call -> (labels, study.StudyReport).
@@ -217,7 +218,14 @@ class REVS:
         multipliers of the scenario's voltage rows: those the operator holds after the last iteration of a
         "distributed" scenario (on either path), zero for every other method, whose schedules no voltage row shapes:
         their prices are energy and loss alone; against opt report_vset; one launch for all scenarios on either path
-        (its arrays are read back with opt arrays).  False: nothing of it runs."""
+        (its arrays are read back with opt arrays).  False: nothing of it runs.
+        powerflow=True or a dict of powerflow_report_device's options (edge_x, power_factor, nodes, vmin, tol, max_iter,
+        slot_hours, cost): StudyReport.powerflow, every scenario's powerflow.PowerFlowReport -- the branch-flow voltages,
+        flows and losses beside the linear model's voltages, and the undervoltages the linear model misses -- from the
+        report's own rows; the reactances are read off the graph's edges where every edge carries an `x`
+        (lpsolver.feeder_reactances; else active power only); counted and summarised over `community`, against opt vmin
+        and opt report_vset; one launch for all scenarios on either path (its arrays are read back with opt arrays).
+        False: nothing of it runs."""
         from .drawing import line_nodes
         from .lpsolver import feeder_of
         from . import study as st
@@ -381,6 +389,15 @@ class REVS:
             return loss_report_device(node_g, feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
                                       arrays=opt.get("arrays", False), **kw)
 
+        def powerflow_reports(node_g):
+            from .lpsolver import feeder_reactances
+            from .powerflow import powerflow_report_device
+            kw = dict(cost=np.asarray(tariff, np.float64), edge_x=feeder_reactances(dist, res),
+                      nodes=[pos[h] for h in community], vmin=opt.get("vmin", 0.95))
+            kw.update(powerflow if isinstance(powerflow, dict) else {})
+            return powerflow_report_device(node_g, feeder=(parent, edge_r, cons_of), vset=opt.get("report_vset", 1.0),
+                                           arrays=opt.get("arrays", False), **kw)
+
         def transformer_reports(node_g):
             from .transformers import rows_by_transformer, size_ratings, transformer_report_device
             kw = dict(transformers if isinstance(transformers, dict) else {})
@@ -472,6 +489,8 @@ class REVS:
                 rep.risk = risk_reports(buf)
             if want_prices:
                 rep.prices = price_reports(buf)
+            if powerflow is True or isinstance(powerflow, dict):
+                rep.powerflow = powerflow_reports(buf)
             return labels, rep
         rep = st.study_report(parent, edge_r, cons_of, np.stack(profiles), groups=[order.index(c) for c in combos],
                               rating=node_rating, nodes=[pos[h] for h in community],
@@ -508,6 +527,9 @@ class REVS:
         if want_prices:
             import torch
             rep.prices = price_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
+        if powerflow is True or isinstance(powerflow, dict):
+            import torch
+            rep.powerflow = powerflow_reports(torch.from_numpy(np.stack(profiles)).to(self.device))
         return labels, rep
 
     @staticmethod

@@ -116,6 +116,7 @@ class StudyReport:
     attribution: list | None = None
     risk: list | None = None
     prices: list | None = None
+    powerflow: list | None = None     # every scenario's powerflow.PowerFlowReport of REVS.study(powerflow=True), else None
 
     @property
     def n_groups(self):

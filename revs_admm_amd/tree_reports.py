@@ -1,5 +1,5 @@
 """What the reports over the feeder as a tree stage alike around their one call into the library (study.py, headroom.py,
-losses.py, attribution.py, risk.py, prices.py; transformers.py, which has no tree, uses the checks of the node sums, the device context and the
+losses.py, attribution.py, risk.py, prices.py, powerflow.py; transformers.py, which has no tree, uses the checks of the node sums, the device context and the
 buffers): the checks of the node sums and of the feeder, the tree and the stream of the launch, a host caller's upload,
 the out= tensor, the scratch, the records' buffers and their read-back, and the per-position masks and classes.  Plain
 functions; `who` is the report's name in front of every message ("headroom report")."""
