@@ -59,12 +59,30 @@ def _run_evaluate(lib, fake, xp, host_ptr, M, T, ptr_, pe, ps, gm, R, y, kappa, 
 
 @pytest.mark.parametrize("n,M,T,n_mult", [(3000, 300, 7, 5), (2500, 260, 24, 100), (900, 40, 96, 3)])
 def test_dual_evaluate_and_model_match_numpy(gpu_lib, n, M, T, n_mult):
+    _dual_evaluate_and_model(gpu_lib, n, M, T, n_mult, 5.0)
+
+
+# ADMM penalties whose reciprocal is a rounded double (tests/param_cases.py; 7 runs through the engine's operator paths
+# in tests/test_gpu_operator.py)
+OTHER_KAPPAS = [0.8, 3.3]
+
+
+@pytest.mark.parametrize("kappa", OTHER_KAPPAS)
+def test_dual_evaluate_and_model_at_other_penalties(gpu_lib, kappa):
+    """test_dual_evaluate_and_model_match_numpy at its smallest shape with d = R^T y / kappa, K = R N R^T / kappa and
+    -(kappa/2) sum g^2 away from kappa = 5, against tests/fake_kernels.py at the same tolerances."""
+    from param_cases import KAPPAS
+    assert set(OTHER_KAPPAS) < set(KAPPAS)
+    _dual_evaluate_and_model(gpu_lib, 900, 40, 96, 3, kappa)
+
+
+def _dual_evaluate_and_model(gpu_lib, n, M, T, n_mult, kappa):
     import torch
     from fake_kernels import FakeKernels
     from revs_admm_amd._lib import check, ptr
     fake = FakeKernels()
     node_of, ptr_, R, pe, ps, gm, y = _case(n + T, n, M, T, n_mult)
-    kappa, vlo, vhi, kadd, ks = 5.0, -0.05, 0.06, 16, 3
+    vlo, vhi, kadd, ks = -0.05, 0.06, 16, 3
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to("cuda:0")
     gi, gb = _run_evaluate(gpu_lib, fake, up, ptr, M, T, ptr_, pe, ps, gm, R, y, kappa, vlo, vhi, kadd, ks)
     keep = []                                         # numpy buffers must outlive the pointers
@@ -424,11 +442,22 @@ def test_model_problem_sizes(gpu_lib, a):
     the two mask words, the full 128): the returned point satisfies the LCP of the model and
     equals the numpy block-pivoting solution.  K = R R^T / kappa with R a x a, so K is the
     Gram matrix of the candidate rows themselves; two slots get mirrored signs."""
+    _model_problem_size(gpu_lib, a, 5.0)
+
+
+@pytest.mark.parametrize("kappa", OTHER_KAPPAS)
+@pytest.mark.parametrize("a", [5, 65, 128])
+def test_model_problem_sizes_at_other_penalties(gpu_lib, a, kappa):
+    """test_model_problem_sizes with K = R R^T / kappa away from kappa = 5: one mask word, two, the full 128."""
+    _model_problem_size(gpu_lib, a, kappa)
+
+
+def _model_problem_size(gpu_lib, a, kappa):
     import torch
     from fake_kernels import FakeKernels
     from revs_admm_amd._lib import check, ptr
     rng = np.random.default_rng(a)
-    M, T, kappa, delta, nks = a, 3, 5.0, 1e-10, 2
+    M, T, delta, nks = a, 3, 1e-10, 2
     R = rng.normal(size=(M, M)) * (rng.uniform(size=(M, M)) < 0.5) + np.eye(M) * 0.1
     if a > 4:
         R[3] = R[1]                                    # an exactly repeated row: singular K
@@ -723,11 +752,20 @@ def test_model_problem_sizes_big(gpu_lib, a):
     optimal value of the sign-constrained quadratic, which a non-negative least-squares solve on the Cholesky factor gives
     independently.  K = R N R^T / kappa with R a x a; an exactly repeated row makes K singular; slot 1 has clamped nodes,
     slot 2 mirrored signs."""
+    _model_problem_size_big(gpu_lib, a, 5.0)
+
+
+def test_model_problem_sizes_big_at_another_penalty(gpu_lib):
+    """test_model_problem_sizes_big at 129 rows, the first size of that path, with K = R N R^T / 3.3."""
+    _model_problem_size_big(gpu_lib, 129, 3.3)
+
+
+def _model_problem_size_big(gpu_lib, a, kappa):
     import torch
     from scipy.optimize import nnls
     from revs_admm_amd._lib import check, ptr
     rng = np.random.default_rng(a)
-    M, T, kappa, delta, nks = a, 3, 5.0, 1e-10, 3
+    M, T, delta, nks = a, 3, 1e-10, 3
     R = rng.normal(size=(M, M)) * (rng.uniform(size=(M, M)) < 0.5) + np.eye(M) * 0.1
     if a > 4:
         R[3] = R[1]

@@ -99,10 +99,28 @@ def _set_state(e, pe, ps, gm):
 def test_operator_matches_oracle(gpu_lib, n, M, T):
     """Utility QP on the GPU (node-space SVD form, f64 matrix cores) == oracle
     (home-space dense form): the optimum is unique, so the two must agree."""
+    _assert_operator_matches_oracle(n, M, T, 5.0, 1.0)
+
+
+def _operator_grid():
+    """(kappa, vset) away from the default point: tests/param_cases.py's penalties at vset = 1, its set points at kappa = 5."""
+    from param_cases import OFF_KAPPAS, VSETS
+    return [(k, 1.0) for k in OFF_KAPPAS] + [(5.0, v) for v in (VSETS[0], VSETS[-1])]
+
+
+@pytest.mark.parametrize("kappa,vset", _operator_grid())
+def test_operator_matches_oracle_at_other_parameters(gpu_lib, kappa, vset):
+    """test_operator_matches_oracle at its smallest shape with d = R^T y / kappa, K = R N R^T / kappa and the ADMM
+    forms' rho (scaled by kappa) away from kappa = 5, and with the voltage band of another set point (1.045: the
+    upper limit 1.05^2 - vset^2 a fifth of the one at 1.0).  Same four paths, same tolerances."""
+    _assert_operator_matches_oracle(400, 50, 24, kappa, vset)
+
+
+def _assert_operator_matches_oracle(n, M, T, kappa, vset, stress=1.3):
     from helpers import f32
     from oracle import revs_oracle as ro
     from revs_admm_amd.synthetic import make_workload
-    w = make_workload(n, T, n_nodes=M, seed=n + T, stress=1.3)
+    w = make_workload(n, T, n_nodes=M, seed=n + T, stress=stress, kappa=kappa, vset=vset)
     rng = np.random.default_rng(1)
     ps = f32(w.load + rng.uniform(0, 3, (n, T)))
     if M == n:

@@ -272,13 +272,29 @@ def test_multi_iteration_launch_equals_a_chain_of_single_launches(gpu_lib, T, mo
     Node sums ("exact, order-independent"): every slice of the multi-iteration launch equals
     the chain's bit for bit, and the float64 np.add.at within 1e-12 of the slice's largest entry (bit for bit too
     wherever no rounding can occur in any order: addends zero or >= 2^-20 kW in a sum below 2^10 kW)."""
+    _chain_against_links(gpu_lib, T, mode, layout, 5.0)
+
+
+@pytest.mark.parametrize("kappa", [0.8, 3.3, 7.0])
+@pytest.mark.parametrize("mode", ["binary", "relaxed_exact", "pdhg"])
+@pytest.mark.parametrize("T", _ids([24, 96]))
+def test_multi_iteration_launch_at_other_penalties(gpu_lib, T, mode, kappa):
+    """test_multi_iteration_launch_equals_a_chain_of_single_launches (dense layout) with every check and bar as there,
+    at the two bench lane shapes and ADMM penalties whose 1 / kappa and kappa / 2 are rounded floats (tests/
+    param_cases.py: KAPPAS without 5).  The bar on the recomputed estimate, 2^-22 (0.5 (|pe| + |ps|) + |G| / kappa),
+    carries kappa already; at 0.8 its G term is six times the one at 5."""
+    from param_cases import OFF_KAPPAS
+    assert kappa in OFF_KAPPAS and len(OFF_KAPPAS) == 3
+    _chain_against_links(gpu_lib, T, mode, "dense", kappa)
+
+
+def _chain_against_links(lib, T, mode, layout, kappa):
     from test_gpu_agent import _prep, _state
     from sweep_ref import node_sums
-    lib = gpu_lib
     shape = shape_of(T)
     kmax = int(lib.revs_agent_max_inner(T, 0))
     assert kmax == MAX_INNER[shape], (T, shape, kmax)
-    w, oh = _prep(N, T, seed=200 + T, binary_feasible=(mode == "binary"))
+    w, oh = _prep(N, T, seed=200 + T, binary_feasible=(mode == "binary"), kappa=kappa)
     node_of, M = (w.node_of, 16) if layout == "dense" else (np.arange(N), N)
     pe_old, _, ps, gm = _state(w, T + 2)
     state = (pe_old, ps, gm)
@@ -332,7 +348,7 @@ def test_multi_iteration_launch_equals_a_chain_of_single_launches(gpu_lib, T, mo
         assert _same_bits(m_ring[i, :mt][sure], ref[sure]) and _same_bits(c_ring[i, :mt][sure], ref[sure]), i
 
     # ---- every link of the chain against float64 ----
-    links = _oracle_links((T, mode), w, oh, state, chain, mode)
+    links = _oracle_links((T, mode, kappa), w, oh, state, chain, mode)
     rate = max(1.0, float(w.homes["rating"].max()))
     st = tuple(np.asarray(a, np.float64) for a in state)
     worst = dict(pen=0.0, sch=0.0, G=0.0, diff=0.0)
@@ -363,7 +379,7 @@ def test_multi_iteration_launch_equals_a_chain_of_single_launches(gpu_lib, T, mo
         worst["G"] = max(worst["G"], float(np.abs(Gn - Gref).max()))
         worst["diff"] = max(worst["diff"], float(np.abs(c_diff[i] - dref).max()))
         st = (pen_gpu, sch, Gn)
-    _note(2, T=T, shape=shape, mode=mode, layout=layout, kin=f"3+{kmax}", slice=slice_err, tiny_addends=tiny,
+    _note(2, T=T, shape=shape, mode=mode, layout=layout, kappa=kappa, kin=f"3+{kmax}", slice=slice_err, tiny_addends=tiny,
           pen_over_bar=worst["pen"], sch=worst["sch"], G=worst["G"], diff=worst["diff"])
 
 

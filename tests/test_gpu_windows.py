@@ -191,16 +191,30 @@ def test_multi_iteration_launch_on_the_atlas(gpu_lib, T, mode, layout):
     dense: all residences on 16 nodes, sorted by need class (workgroups of like residences); dense_shuffled: the same in
     a random order (mixed workgroups); sparse: one residence per node.  The residences are sorted by node in each, as
     the entry point demands."""
+    _atlas_chain(gpu_lib, T, mode, layout, 5.0)
+
+
+@pytest.mark.parametrize("kappa", [0.8, 3.3, 7.0])
+@pytest.mark.parametrize("mode", ["binary", "relaxed_exact", "pdhg"])
+@pytest.mark.parametrize("T", _ids([24, 96]))
+def test_multi_iteration_launch_on_the_atlas_at_other_penalties(gpu_lib, T, mode, kappa):
+    """test_multi_iteration_launch_on_the_atlas (dense layout), every check and bar as there, at the two bench lane
+    shapes and the ADMM penalties of tests/param_cases.py other than 5: 1 / kappa and kappa / 2 rounded floats."""
+    from param_cases import OFF_KAPPAS
+    assert kappa in OFF_KAPPAS and len(OFF_KAPPAS) == 3
+    _atlas_chain(gpu_lib, T, mode, "dense", kappa)
+
+
+def _atlas_chain(lib, T, mode, layout, kappa):
     from helpers import oracle_homes
     from sweep_ref import link, node_sums
     from test_gpu_agent import _state
     from test_gpu_shapes import _Sweep
-    lib = gpu_lib
     shape = shape_of(T)
     kmax = int(lib.revs_agent_max_inner(T, 0))
     assert kmax == MAX_INNER[shape], (T, shape, kmax)
     a = _ordered(_case(T)[0], layout)
-    w = wc.workload(a)
+    w = wc.workload(a, kappa)
     oh = oracle_homes(w)
     n = len(a.homes)
     node_of, M = (np.arange(n), n) if layout == "sparse" else (np.arange(n) * 16 // n, 16)
@@ -238,7 +252,7 @@ def test_multi_iteration_launch_on_the_atlas(gpu_lib, T, mode, layout):
         assert err <= 1e-12, (i, err)
 
     # ---- every link of the chain against float64 ----
-    key = (T, mode, layout != "dense_shuffled")           # (the state does not depend on the node layout)
+    key = (T, mode, layout != "dense_shuffled", kappa)    # (the state does not depend on the node layout)
     if key in _LINKS and all(_same_bits(x[k], y[k]) for x, y in zip(_LINKS[key][0], chain) for k in ("P_est", "P_sch", "G")):
         links = _LINKS[key][1]
     else:
@@ -280,7 +294,7 @@ def test_multi_iteration_launch_on_the_atlas(gpu_lib, T, mode, layout):
             worst["diff"] = max(worst["diff"], _held(a, f"diff of link {i}", c_diff[i], dref, atol=1e-4, rtol=1e-4))
             _held(a, f"dsq of link {i}", s["dsq"], ((lk.g - p_s) ** 2).sum(axis=1), rtol=2e-3, atol=1e-6)
         st = (pen_gpu, sch, Gn)
-    _note("w-b", T=T, shape=shape, mode=mode, layout=layout, n=n, kin=f"3+{kmax}", flagged=flagged, capped=capped, slice=slice_err,
+    _note("w-b", T=T, shape=shape, mode=mode, layout=layout, kappa=kappa, n=n, kin=f"3+{kmax}", flagged=flagged, capped=capped, slice=slice_err,
           pen_over_bar=worst["pen"], sch=worst["sch"], G=worst["G"], diff=worst["diff"])
 
 
