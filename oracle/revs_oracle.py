@@ -319,16 +319,32 @@ def home_solve_relaxed(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0):
     return p, _soc(h, p), p + h.LOAD, status
 
 
-def pdhg_steps(h: Homes, tau_scale=0.25, sigma_scale=4.0):
-    """Step sizes of the PDHG restatement below and of the HIP kernel
-    (revs_admm_amd/csrc/agent_kernels.hip: pdhg_step_sizes).  The kernel works in
+def pdhg_steps(h: Homes, tau_scale=0.25, sigma_scale=4.0, dtype=np.float64):
+    """Step sizes of the full-rows PDHG restatement below and of the HIP kernel
+    (revs_admm_amd/csrc/agent_kernels.hip: inv_nK under FULL_ROWS), formed in `dtype`.  The kernel works in
     the normalised variable x_t = p_t/rating (objective x^2/2 + b x), where the SOC
-    operator is K = delta * (inclusive prefix sum), delta = rating/capacity, with
-    ||K|| <= delta * T_w * 2/pi * (1 + 1/T_w) (T_w = window length)."""
-    Tw = np.maximum(h.end - h.start, 1).astype(float)
-    delta = np.where(h.ev, h.rating / h.capacity, 1.0)
-    nK = delta * (2.0 / math.pi) * (Tw + 1.0)
-    return tau_scale / nK, sigma_scale / nK, delta
+    operator is K = delta * (inclusive prefix sum), delta = rating/capacity.  x lives on the window
+    clipped to the horizon, [ws, we) with T_w = we - ws slots; the rows in front of it are empty, the
+    T_w rows inside it are the triangle and every one of the T - we rows behind it is delta * 1^T:
+        K = delta [tri(T_w); 1 1^T x (T - we)],
+        ||K||^2 <= ||tri||^2 + ||1 1^T||^2 <= delta^2 (((2/pi)(T_w + 1))^2 + T_w (T - we)),
+    so that tau sigma ||K||^2 <= tau_scale sigma_scale = 1.  -> (tau, sigma, delta), each (N,)."""
+    dt = dtype
+    ws, we = np.maximum(h.start, 0), np.minimum(h.end, h.T)
+    Tw = np.maximum(we - ws, 1).astype(dt)
+    tail = Tw * (h.T - np.maximum(we, 0)).astype(dt)
+    delta = np.where(h.ev, h.rating / h.capacity, 1.0).astype(dt)
+    nt = dt(2.0 / math.pi) * (Tw + dt(1.0))
+    nK = delta * np.sqrt(nt * nt + tail)
+    return dt(tau_scale) / nK, dt(sigma_scale) / nK, delta
+
+
+def soc_operator(h: Homes, i):
+    """The matrix K of residence i that the full-rows PDHG applies, on the window's slots only (columns: the slots of
+    the window clipped to the horizon; rows: every slot of the horizon) -- for checking pdhg_steps' bound."""
+    ws, we = max(int(h.start[i]), 0), min(int(h.end[i]), h.T)
+    t = np.arange(h.T)[:, None]
+    return (h.rating[i] / h.capacity[i]) * (np.arange(ws, max(we, ws))[None, :] <= t).astype(float)
 
 
 def home_solve_relaxed_pdhg(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0,
@@ -339,10 +355,13 @@ def home_solve_relaxed_pdhg(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0,
         x+ = clip((x - tau (K^T y + b)) / (1 + tau), 0, w)
         y+ = v - sigma clip(v / sigma, lo, hi),  v = y + sigma K (2 x+ - x)
     rows j = 0..T-1 of K x are s_{j+1} - init; lo_j = 0 (j < T-1), lo_{T-1} =
-    max(0.9, init) - init, hi_j = 1 - init.  Stops when the largest change of x
+    max(0.9, init) - init, hi_j = 1 - init.  The multiplier is carried as the kernel carries it, yrow = y / sigma:
+        K^T y = sigma delta (suffix sum of yrow),  v = yrow + delta (prefix sum of 2 x+ - x),  yrow+ = v - clip(v, lo, hi).
+    Stops when the largest change of x and yrow
     over a block of `check` iterations' last step falls below tol.
-    x0 (N,T), y0 (N,): the presolved form's warm start (full_rows=False) -- the kernel's when it carries its multiplier:
-    x0 = (P_sch - LOAD) / rating, clipped to the window's box, and the terminal row's multiplier."""
+    x0 (N,T): the warm start, x0 = (P_sch - LOAD) / rating, clipped to the window's box; y0: the carried multiplier in
+    the kernel's units -- (N,T) rows yrow with full_rows, (N,) the terminal row's with full_rows=False.
+    -> p, soc, g, passes (N,) and, with full_rows, yrow (N,T) in `dtype`."""
     dt = dtype
     q = home_linear_term(cost, h, p_est, p_sch, gamma, kappa)
     rate = np.where(h.ev, h.rating, 1.0)
@@ -350,36 +369,39 @@ def home_solve_relaxed_pdhg(cost, h: Homes, p_est, p_sch, gamma, kappa=5.0,
     w = h.window().astype(dt)
     if not full_rows:
         return _pdhg_presolved(h, b, w, iters, tol, check, tau_scale or 0.5, sigma_scale or 2.0, dt, x0, y0)
-    assert x0 is None and y0 is None
-    tau, sig, delta = pdhg_steps(h, tau_scale or 0.25, sigma_scale or 4.0)
-    tau, sig, delta = (tau.astype(dt)[:, None], sig.astype(dt)[:, None],
-                       delta.astype(dt)[:, None])
+    tau, sig, delta = (a[:, None] for a in pdhg_steps(h, tau_scale or 0.25, sigma_scale or 4.0, dt))
+    sd = sig * delta
     lo = np.zeros((h.N, h.T), dt)
     lo[:, -1] = np.maximum(SOC_TARGET, h.initial) - h.initial
     hi = np.repeat((SOC_MAX - h.initial)[:, None], h.T, 1).astype(dt)
-    x = np.zeros((h.N, h.T), dt)
-    y = np.zeros((h.N, h.T), dt)
-    done = ~h.ev.copy()
+    x = np.zeros((h.N, h.T), dt) if x0 is None else np.clip(np.asarray(x0, dt), 0, w)
+    y = np.zeros((h.N, h.T), dt) if y0 is None else np.where(h.ev[:, None], np.asarray(y0, dt), dt(0))
     n_it = np.zeros(h.N, np.int64)
     one = dt(1.0)
+    # (rows are independent: only those still iterating are carried, a row that meets the tolerance is written back)
+    idx = np.flatnonzero(h.ev)
+    per_row = [a[idx] for a in (tau, sd, delta, b, w, lo, hi)]
+    xa, ya = x[idx], y[idx]
     for k in range(iters):
-        act = ~done
-        if not act.any():
+        if not len(idx):
             break
-        KTy = delta * np.cumsum(y[:, ::-1], axis=1, dtype=dt)[:, ::-1]
-        xn = np.clip((x - tau * (KTy + b)) / (one + tau), 0, w)
-        xb = xn + (xn - x)
-        v = y + sig * (delta * np.cumsum(xb, axis=1, dtype=dt))
-        yn = v - sig * np.clip(v / sig, lo, hi)
-        dx = np.abs(xn - x).max(axis=1)
-        dy = (np.abs(yn - y) / sig).max(axis=1)
-        x = np.where(act[:, None], xn, x)
-        y = np.where(act[:, None], yn, y)
-        n_it += act
+        tau_a, sd_a, delta_a, b_a, w_a, lo_a, hi_a = per_row
+        KTy = sd_a * np.cumsum(ya[:, ::-1], axis=1, dtype=dt)[:, ::-1]
+        xn = np.clip((xa - tau_a * (KTy + b_a)) / (one + tau_a), 0, w_a)
+        xb = xn + (xn - xa)
+        v = ya + delta_a * np.cumsum(xb, axis=1, dtype=dt)
+        yn = v - np.clip(v, lo_a, hi_a)
+        n_it[idx] += 1
         if (k + 1) % check == 0:
-            done |= np.maximum(dx, dy) <= tol
+            fin = np.maximum(np.abs(xn - xa).max(axis=1), np.abs(yn - ya).max(axis=1)) <= tol
+            if fin.any():
+                x[idx[fin]], y[idx[fin]] = xn[fin], yn[fin]
+                idx, xn, yn = idx[~fin], xn[~fin], yn[~fin]
+                per_row = [a[~fin] for a in per_row]
+        xa, ya = xn, yn
+    x[idx], y[idx] = xa, ya
     p = x.astype(float) * np.where(h.ev, h.rating, 0.0)[:, None]
-    return p, _soc(h, p), p + h.LOAD, n_it
+    return p, _soc(h, p), p + h.LOAD, n_it, y
 
 
 def _pdhg_presolved(h: Homes, b, w, iters, tol, check, tau_scale, sigma_scale, dt, x0=None, y0=None):

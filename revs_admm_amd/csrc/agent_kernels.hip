@@ -475,7 +475,11 @@ void agent_step_kernel(const AgentArgs a) {
         lo_last = fmaxf(kSocTarget, h.initial) - h.initial;
         inv_kr = __builtin_amdgcn_rcpf(kappa * rate);
         if constexpr (FULL_ROWS) {
-            const float inv_nK = __builtin_amdgcn_rcpf(delta * 0.63661977236758134f * (Tw + 1.0f));
+            // K keeps the rows behind the window too: every slot t >= we holds delta * (the window's sum), so
+            // K = delta [tri(Tw); 1 1^T x (T - we)] and ||K||^2 <= delta^2 (((2/pi)(Tw + 1))^2 + Tw (T - we))
+            const float nt = 0.63661977236758134f * (Tw + 1.0f);
+            const float tail = Tw * (float)(T - max(we, 0));
+            const float inv_nK = __builtin_amdgcn_rcpf(delta * __builtin_amdgcn_sqrtf(nt * nt + tail));
             tau = (a.pd.tau_scale > 0.f ? a.pd.tau_scale : 0.25f) * inv_nK;
             sig = (a.pd.sigma_scale > 0.f ? a.pd.sigma_scale : 4.0f) * inv_nK;
             inv1pt = __builtin_amdgcn_rcpf(1.0f + tau);

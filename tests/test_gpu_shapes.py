@@ -150,7 +150,7 @@ def test_one_iteration_relaxed_at_band_edges(gpu_lib, relaxed_oracle, T, mode):
 class _Sweep:
     """The arguments of revs_agent_step_multi that do not change between launches, on the device."""
 
-    def __init__(self, lib, w, node_of, M, mode):
+    def __init__(self, lib, w, node_of, M, mode, pdhg=None):
         import torch
         from revs_admm_amd import _lib
         from revs_admm_amd._lib import HOME_DTYPE, PDHG
@@ -167,6 +167,8 @@ class _Sweep:
         lib.revs_pdhg_defaults(C.byref(self.pd))
         if mode == "binary":
             self.pd.keys64 = 1                       # the oracle's decision for every residence
+        for k, v in (pdhg or {}).items():            # (revs_pdhg_t fields other than the defaults)
+            setattr(self.pd, k, v)
         self.stream = torch.cuda.current_stream().cuda_stream
 
     def up(self, a, dt=np.float32):
@@ -188,7 +190,9 @@ class _Sweep:
         from revs_admm_amd._lib import check
         cur = [self.up(a) for a in state]
         nxt = [torch.empty_like(t) for t in cur]
-        y = torch.zeros(self.n, dtype=torch.float32, device=self.dev) if self.pdhg_mode else None
+        # the carried multipliers: one per residence, or one per SOC row with revs_pdhg_t::full_rows
+        y_shape = (self.n, self.T) if self.pd.full_rows else (self.n,)
+        y = torch.zeros(y_shape, dtype=torch.float32, device=self.dev) if self.pdhg_mode else None
         y2 = torch.zeros_like(y) if (self.pdhg_mode and rotate_y) else y
         tot = sum(kins)
         ring = torch.zeros(tot, self.stride, dtype=torch.float64, device=self.dev)
