@@ -4,6 +4,8 @@ op_chain_kv_kernel): inputs that take every branch of it, and a plain float64 nu
 On top of tests/select_ref.py (the 2^-10 grid, restate(), star_forest()).  The kernel takes the feeder twice, and the two
 are independent in it: as a TREE for the row voltages, and as the dense R for the Gram sums and the shifts.
   tree      star_forest: the tree form of R p is p, so rows, sums, lists and stats are exact and numpy gives them bit for bit;
+            or (TREES) a chain, a comb, a comb with split edges from tests/tree_cases.py: every edge w = 1 (two halves
+            through a junction where split), random node numbers, and p = the injections whose tree form is v -- as exact;
   dense R   m x m, multiples of 2^-4 with |r| < 2 (zeros included); N integers 0..16 (zeros included); kappa = 4: every
             Gram sum over up to 2048 nodes is below 2^17 at resolution 2^-8 -- exact in double in any order -- so K from
             chain_fast_body, from small_model_body and from numpy agree bit for bit (tests/test_chain_cases.py checks the
@@ -17,6 +19,7 @@ import functools
 import numpy as np
 
 import select_ref as sr
+import tree_cases as tc
 from select_ref import BAND, G, T, VHI, VLO
 
 A = 128                                   # REVS_DUAL_AMAX
@@ -28,7 +31,13 @@ NAMES = ("empty", "a1", "a2", "a3", "a4", "a5", "a6", "a7", "a8", "unsorted_supp
 assert len(NAMES) == T
 SIZES = (1, 9, 255, 257, 2048)            # rows = tree rows; 2048 = REVS_CHAIN_FOLD_MAX_M: the launch's LDS is over 64 KB
 # name -> (rows with a position in the tree, rows m, junction nodes without a row)
-GEOMETRY = {**{str(M): (M, M, 0) for M in SIZES}, "off_tree": (257, 300, 0), "junctions": (255, 255, 10)}
+GEOMETRY = {**{str(M): (M, M, 0) for M in SIZES}, "off_tree": (257, 300, 0), "junctions": (255, 255, 10),
+            "chain255": (255, 255, 0), "chain2048": (2048, 2048, 0), "comb255": (255, 255, 0), "comb2048": (2048, 2048, 0),
+            # (2038 rows on the tree: with the ten junctions its 2048 positions are all the launch holds)
+            "split_edges255": (255, 255, 10), "split_edges2048": (2038, 2048, 10)}
+# the geometries on a real tree -- the others are forests of roots --: name -> (kind of tree_cases.unit_tree, split edges)
+TREES = {"chain255": ("chain", 0), "chain2048": ("chain", 0), "comb255": ("comb", 0), "comb2048": ("comb", 0),
+         "split_edges255": ("comb", 10), "split_edges2048": ("comb", 10)}
 
 
 class _Col:
@@ -217,9 +226,16 @@ def build(name, seed=0):
     junk = rng.integers(-255, 256, (m, T))
     p = np.where(on[:, None], k, junk) * G
     q = -rng.integers(0, 40, (m, T)) * G
-    # the forest: every row's node hangs off the substation by an edge of resistance 0.5, junction nodes in between
-    cons_of = np.concatenate([cons, np.full(njun, -1, np.int64)])[rng.permutation(M + njun)] if njun else cons
-    forest = (np.full(len(cons_of), -1, np.int64), np.full(len(cons_of), 0.5), cons_of)
+    if name in TREES:
+        # a real tree: row r of unit_tree is row cons[r] here, and the node sums are the injections that give v
+        parent, edge_r, rows = tc.unit_tree(*((TREES[name][0], M, TREES[name][1])))
+        assert (rows < 0).sum() == njun
+        p[cons] = tc.injections((parent, edge_r, rows), (k * G)[cons])
+        forest = (parent, edge_r, np.where(rows >= 0, cons[np.maximum(rows, 0)], -1))
+    else:
+        # the forest: every row's node hangs off the substation by an edge of resistance 0.5, junction nodes in between
+        cons_of = np.concatenate([cons, np.full(njun, -1, np.int64)])[rng.permutation(M + njun)] if njun else cons
+        forest = (np.full(len(cons_of), -1, np.int64), np.full(len(cons_of), 0.5), cons_of)
     out = dict(name=name, m=m, forest=forest, on=on, v=np.where(on[:, None], k * G, 0.0), y=y,
                pnq=np.ascontiguousarray(np.stack([p, N, q])), R=np.ascontiguousarray(R), prev_cidx=prev_cidx,
                prev_ccnt=prev_ccnt)

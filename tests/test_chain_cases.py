@@ -37,6 +37,32 @@ def test_preconditions_hold_in_every_column(geo):
 
 
 @pytest.mark.parametrize("geo", GEOS)
+def test_the_tree_form_of_the_node_sums_is_v(geo):
+    """feeder.py's restatement of the three prefix sums turns pnq[0] into v bit for bit on every geometry's forest -- p
+    itself on the forests of roots, the injections of tests/tree_cases.py on the real trees, which are not degenerate:
+    on those a gather in preorder where end-order is due does not return v (the chains aside: there the two agree)."""
+    from revs_admm_amd.feeder import feeder_tree, tree_voltage_host
+    import tree_cases as tc
+    c = cc.case(geo)
+    M, m, njun = cc.GEOMETRY[geo]
+    tr = feeder_tree(*c["forest"], np.ones(m, bool))
+    assert tr["n"] <= 2048 and (tr["src"] >= 0).sum() == M and len(c["forest"][0]) == M + njun
+    assert np.array_equal(tree_voltage_host(tr, np.array(c["pnq"][0])), c["v"])
+    if geo in cc.TREES:
+        assert not np.array_equal(c["pnq"][0][c["on"]], c["v"][c["on"]])
+        assert (c["forest"][0] > np.arange(M + njun)).any() and (tr["cle"] != np.arange(tr["n"])).any()
+        assert (tr["end"] - np.arange(tr["n"]) > 64).any()
+        o = cc.build(geo, seed=1)               # (test_gpu_chain_kv.py's verdict half: another draw on the same rows)
+        p2, v2 = np.array(c["pnq"][0]), np.zeros_like(c["v"])
+        p2[c["on"]], v2[c["on"]] = o["pnq"][0][o["on"]], o["v"][o["on"]]
+        assert np.array_equal(tree_voltage_host(tr, p2), v2)
+        wrong = tc.tree_voltage_preorder_gather(tr, np.array(c["pnq"][0]))
+        assert np.array_equal(wrong, c["v"]) == (cc.TREES[geo][0] == "chain"), geo
+    else:
+        assert np.array_equal(tc.tree_voltage_preorder_gather(tr, np.array(c["pnq"][0])), c["v"])
+
+
+@pytest.mark.parametrize("geo", GEOS)
 def test_gram_sums_are_exact(geo):
     """K of the restatement == the same sums in integers (R 2^4 and N are integers, kappa = 4), and every partial sum of
     |r n r'| stays below 2^17: exact in double at resolution 2^-8 in any order."""

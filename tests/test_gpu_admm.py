@@ -793,20 +793,40 @@ def test_tiny_runs_match_oracle(gpu_lib, n, M, T):
 
 @pytest.mark.parametrize("mode,stress,T,nodes", [("pdhg", 1.02, 24, 200), ("relaxed_exact", 1.0, 24, 200),
                                                  ("binary", 0.5, 24, 200), ("pdhg", 1.02, 96, 200),
-                                                 ("pdhg", 1.02, 24, 4096), ("relaxed_exact", 1.02, 24, 8192)])
+                                                 ("pdhg", 1.02, 24, 4096), ("relaxed_exact", 1.02, 24, 8192),
+                                                 ("pdhg", 1.02, 24, "comb200")])
 def test_streaming_steady_state_equals_dense_product_path(gpu_lib, mode, stress, T, nodes):
     """The steady state as ONE launch per iteration -- rows judged inside the sweep's launch by
     the tree form of R p, later launches silenced on the device after a failed verdict, the
     host only keeping the queue full (revs_plan_stream_run) -- against the path that multiplies
     by the dense R on the matrix cores and reads every verdict on the host: same decisions
     (kept / discarded sweeps at the same iterations), same state bit for bit, in ragged
-    chunks, through discards."""
+    chunks, through discards.
+    comb200: the workload's 200 nodes on a comb (teeth of 8) under random node numbers -- a parent may come after its
+    child, subtrees of every size -- with random positive resistances scaled as make_workload scales its own: the worst
+    node's drop under the coordinated profile is what it was on the workload's feeder."""
     from helpers import f32
     from revs_admm_amd.engine import OperatorOptions
     from revs_admm_amd.synthetic import make_workload
+    comb, nodes = nodes == "comb200", 200 if nodes == "comb200" else nodes
     w = make_workload((8000 if T == 24 else 3000) if nodes == 200 else 3 * nodes, T, n_nodes=nodes, seed=3,
                       binary_feasible=(mode == "binary"), stress=stress)
     w.load, w.cost = f32(w.load), f32(w.cost)
+    if comb:
+        import tree_cases as tc
+        rng = np.random.default_rng(200)
+        h = w.homes                                     # the coordinated profile make_workload scales against
+        need = np.where(h["ev"] != 0, np.maximum(0.9 - h["initial"], 0.0) * h["capacity"], 0.0)
+        t = np.arange(T)[None, :]
+        inwin = (h["ev"][:, None] != 0) & (t >= h["start"][:, None]) & (t < h["end"][:, None])
+        Pn = np.zeros((nodes, T))
+        np.add.at(Pn, w.node_of, w.load + inwin * (need / np.maximum(h["end"] - h["start"], 1))[:, None])
+        worst = (w.Rn @ Pn).max()
+        w.parent, w.edge_r = tc.relabel(tc.comb(nodes, tooth=8), rng), rng.uniform(0.5, 1.5, nodes)
+        R = tc.dense_R(w.parent, w.edge_r)
+        scale = worst / (R @ Pn).max()
+        w.Rn, w.edge_r = R * scale, w.edge_r * scale
+        assert (w.parent > np.arange(nodes)).any()
     a = _engine(w, mode, op=OperatorOptions(voltage="dense"))
     b = _engine(w, mode, op=OperatorOptions(voltage="tree", stream_burst=3, stream_burst_max=24))
     assert a._tree is None and b._tree is not None

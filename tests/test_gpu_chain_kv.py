@@ -8,6 +8,8 @@ holds on the CPU that every column is what its name claims and that every branch
   (c) the shifts against a long-double product of the launch's own trial multipliers, to the rounding of an fma chain;
   (d) both halves in one launch: the verdict half against select_ref.restate(), stats forwarding, the clears;
   (e) the golden 121144 feeder -- its tree with junction nodes and its own R -- against the parts.
+The geometries of chain_cases.TREES put (a)-(d) and the three-pass launch on a chain, a comb and a comb with split edges
+under random node numbers (the others are forests of roots, on which the three scans are the identity).
 Outputs start as junk so that anything left unwritten shows."""
 import ctypes as C
 import functools
@@ -136,11 +138,15 @@ def _parts(lib, d):
     return _host({**b, **mo})
 
 
-def _three_pass(lib, d):
-    """revs_op_dual_tree_select_model_step: the three-pass chain's operator launch"""
+def _three_pass(lib, d, zero_rows=False):
+    """revs_op_dual_tree_select_model_step: the three-pass chain's operator launch (zero_rows: vfull / viol start as
+    zeros -- what a row without a position in the tree keeps, and the selection reads every row)"""
+    import torch
     from revs_admm_amd._lib import check, ptr
     m, par = d["m"], d["par"]
     b, mo = _side_buffers(m), _model_buffers(m)
+    if zero_rows:
+        b["vfull"], b["viol"] = (torch.zeros(m, T, dtype=torch.float64, device="cuda:0") for _ in range(2))
     check(lib.revs_op_dual_tree_select_model_step(
         m, T, C.byref(d["tree"]), ptr(d["pnq1"]), ptr(d["y"]), par["vlo"], par["vhi"], par["kadd"], ptr(b["vfull"]),
         ptr(b["viol"]), ptr(b["partial"]), ptr(b["cidx"]), ptr(b["ccnt"]), ptr(b["cval"]), ptr(b["stats"]), SEQ, ptr(d["R"]),
@@ -305,7 +311,8 @@ def _verdict_case(geo):
     pnq[0][on] = o["pnq"][0][o["on"]]
     pnq[2] = o["pnq"][2]
     eff = pnq.copy()                            # (off the tree: no voltage, no dual term)
-    eff[0], eff[2] = np.where(on[:, None], pnq[0], 0.0), np.where(on[:, None], pnq[2], 0.0)
+    eff[0], eff[2] = 0.0, np.where(on[:, None], pnq[2], 0.0)
+    eff[0][on] = o["v"][o["on"]]                # (the tree form of the node sums: themselves on a forest of roots)
     return pnq, sr.restate(eff[0], c["y"], eff, sr.VLO, sr.VHI, cc.KADD, A)
 
 
@@ -377,12 +384,13 @@ def test_the_golden_feeder_against_its_parts(gpu_lib, feeder_dev):
 
 
 # ---- the three-pass chain's operator launch --------------------------------------------------------------------------
-@pytest.mark.parametrize("geo", ["9", "257", "2048"])
+@pytest.mark.parametrize("geo", ["9", "257", "2048"] + list(cc.TREES))
 def test_tree_select_model_step_against_its_parts(gpu_lib, geo):
     """revs_op_dual_tree_select_model_step == revs_op_dual_rows_tree(with_select) + revs_op_dual_model_small +
-    revs_op_dual_step_pending, bit for bit; it does not stage the rows through LDS: vfull / viol are the restatement's."""
+    revs_op_dual_step_pending, bit for bit; it does not stage the rows through LDS: vfull / viol are the restatement's.
+    (cc.TREES: the same on a chain, a comb and a comb with split edges; split_edges2048 has rows off the tree.)"""
     c, e = cc.case(geo), cc.expected(geo)
-    g, p = _three_pass(gpu_lib, _dev(geo)), _run_parts(geo)
+    g, p = _three_pass(gpu_lib, _dev(geo), zero_rows=not c["on"].all()), _run_parts(geo)
     _assert_same_outputs(g, p, c["on"], c["y"], geo)
     assert np.array_equal(g["y_trial"], p["y_trial"])
     assert np.array_equal(g["vfull"], e["vfull"]) and np.array_equal(g["viol"], e["viol"])

@@ -88,12 +88,13 @@ def test_tiled_home_pass_equals_todays_launch_block_by_block(gpu_lib, cols):
         assert (pen == 0).any() and (pen > 0).any()                      # clamps are exercised
 
 
-@pytest.mark.parametrize("cols", [300, 1024])
-@pytest.mark.parametrize("M", [300, 2600])
-def test_tree_rows_equal_todays_launch_block_by_block(gpu_lib, cols, M):
+@pytest.mark.parametrize("M,cols,forest", [pytest.param(M, cols, "workload", id=f"{M}-{cols}") for cols in (300, 1024)
+                                           for M in (300, 2600)] + [pytest.param(2600, 300, "comb", id="2600-300-comb")])
+def test_tree_rows_equal_todays_launch_block_by_block(gpu_lib, cols, M, forest):
     """revs_op_dual_rows_tree (one workgroup per column; 256 x 8 positions up to 2048 nodes, 512 x 8 beyond) at 300 and
     1024 columns: voltages, violations, the columns' four sums -- and with the selection in the launch the lists and
-    stats -- carry the bits of today's launch on each block of 256 columns, and equal numpy's R p to 1e-12."""
+    stats -- carry the bits of today's launch on each block of 256 columns, and equal numpy's R p to 1e-12.
+    (comb: a comb under random node numbers -- a parent may come after its child -- in the workload's resistances.)"""
     import torch
     from revs_admm_amd import _lib
     from revs_admm_amd.engine import feeder_tree
@@ -101,6 +102,11 @@ def test_tree_rows_equal_todays_launch_block_by_block(gpu_lib, cols, M):
     rng = np.random.default_rng(cols + M)
     w = make_workload(M * 2, 24, n_nodes=M, seed=4)
     par, er, cons = w.feeder
+    if forest == "comb":
+        import tree_cases as tc
+        par = tc.relabel(tc.comb(M), rng)
+        assert (par > np.arange(M)).any()
+        w.Rn = tc.dense_R(par, er)
     tr = feeder_tree(par, er, cons, np.ones(M, bool))
     pnq = np.zeros((3, M, cols))
     pnq[0] = rng.uniform(0.0, 4.0, (M, cols))

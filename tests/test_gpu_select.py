@@ -11,7 +11,9 @@ which branch of csrc/select_body.h a slot takes follows from M and from the colu
 
 (a) the dense rows kernel + dual_select_body<true>; (b) the same behind the tiled rows kernel (more than 256 columns);
 (c) the tree rows kernels in front of it, handing over through LDS (tree <= 2048 nodes, 3 m doubles fit), through
-global memory in the same workgroup (they do not fit) or to a launch of its own (larger trees); (d)
+global memory in the same workgroup (they do not fit) or to a launch of its own (larger trees) -- on the forest of
+roots on which R p = p and on a chain, a comb and a balanced tree under random node numbers, where the node sums are
+the injections whose tree form is v (tests/tree_cases.py: unit_tree, injections) and the expectations are the same; (d)
 dual_select_body<false> inside the residence sweep's launch, fed by the restatement itself; (e) the 512-row lists of
 csrc/newton_big.hip.  chain_rows_select_body (the folded chain's own selection) and revs_op_dual_tree_select_model_step
 are held to a restatement built on this one, branch by branch, in tests/test_gpu_chain_kv.py (columns:
@@ -23,6 +25,7 @@ import numpy as np
 import pytest
 
 import select_ref as sr
+import tree_cases as tc
 
 pytestmark = pytest.mark.gpu
 
@@ -148,24 +151,48 @@ def _rows_tree(lib, m, nt, tree, pnq, y, kadd, vfull, viol, part, b):
                                      SEQ, 1, None), "revs_op_dual_rows_tree")
 
 
-@pytest.mark.parametrize("kadd", [16, 128])
-@pytest.mark.parametrize("M", [1, 257, 2048, 2049, 4097, 8200, 16384])
-def test_tree_rows_and_selection(gpu_lib, M, kadd):
-    """star_forest(M): R p = p, so the tree kernels judge the same v as the dense path.  Up to 2048 nodes (256 x 8
+FORESTS = ("star", "chain", "comb", "binary")
+
+
+def _with_forests(cases):
+    """every case on every forest; the forest of roots keeps the id the case had before the trees were added"""
+    return [pytest.param(*c, f, id="-".join(map(str, c)) + ("" if f == "star" else "-" + f)) for f in FORESTS for c in cases]
+
+
+def _forest(kind, M):
+    return sr.star_forest(M) if kind == "star" else tc.unit_tree(kind, M)
+
+
+@functools.lru_cache(maxsize=None)
+def _dev_pnq(kind, M):
+    """case(M)'s node terms with the injections whose tree form on _forest(kind, M) is v in the place of v"""
+    if kind == "star":
+        return _dev(M)["pnq"]
+    v, y, pnq, _ = sr.case(M)
+    pnq = pnq.copy()
+    pnq[0] = tc.injections(_forest(kind, M), v)
+    return _up(pnq)
+
+
+@pytest.mark.parametrize("M,kadd,forest", _with_forests([(M, kadd) for kadd in (16, 128)
+                                                         for M in (1, 257, 2048, 2049, 4097, 8200, 16384)]))
+def test_tree_rows_and_selection(gpu_lib, M, kadd, forest):
+    """star: R p = p, so the tree kernels judge the same v as the dense path; chain | comb | binary: R p = v by the
+    injections of tests/tree_cases.py, through subtrees that span wavefronts.  Up to 2048 nodes (256 x 8
     positions) rows and selection share a workgroup and the rows go through LDS; beyond (512 x 8 at 2049, 1024 x 8 at
     4097, 1024 x 16 at 8200 and 16384) the selection is a launch of its own behind them."""
     d, exp, names = _dev(M), sr.expected(M, kadd), sr.case(M)[3]
-    tree, keep, tr = _device_tree(*sr.star_forest(M), M)
+    tree, keep, tr = _device_tree(*_forest(forest, M), M)
     b, vfull, viol, part = _lists(), _junk((M, T)), _junk((M, T)), _junk((1, T, 4))
-    _rows_tree(gpu_lib, M, T, tree, d["pnq"], d["y"], kadd, vfull, viol, part, b)
+    _rows_tree(gpu_lib, M, T, tree, _dev_pnq(forest, M), d["y"], kadd, vfull, viol, part, b)
     _assert_lists(b, exp, names)
     _assert_partials(part, exp, names)
     if M > 2048:                      # (up to 2048 nodes the rows are staged in LDS: vfull / viol are scratch there)
         assert np.array_equal(vfull.cpu().numpy(), exp["vfull"]) and np.array_equal(viol.cpu().numpy(), exp["viol"])
 
 
-@pytest.mark.parametrize("kadd", [16, 128])
-def test_tree_rows_hand_over_through_global_memory(gpu_lib, kadd):
+@pytest.mark.parametrize("kadd,forest", _with_forests([(16,), (128,)]))
+def test_tree_rows_hand_over_through_global_memory(gpu_lib, kadd, forest):
     """2048 tree nodes scattered over m = 4500 rows: 3 m doubles do not fit in LDS beside the scan buffer, so rows and
     selection share a workgroup but meet in vfull / viol.  Rows without a position in the tree (y = 0 there) keep
     v = 0 and violation 0 -- whatever the node sums hold at them -- and are never admitted."""
@@ -180,7 +207,11 @@ def test_tree_rows_hand_over_through_global_memory(gpu_lib, kadd):
     y = np.where(on[:, None], y, 0.0)
     exp = sr.restate(np.where(on[:, None], v, 0.0), y, np.where(on[:, None], pnq, 0.0), sr.VLO, sr.VHI, kadd)
     assert (exp["sums"][:, 3] > 256).any() and (exp["ccnt"] > 0).sum() >= 20 and (exp["ccnt"] >= kadd).any()
-    tree, keep, tr = _device_tree(np.full(n, -1, np.int64), np.full(n, 0.5), cons, m)
+    parent, edge_r, cons_of = _forest(forest, n)              # (row r of the forest is row cons[r] of the launch)
+    if forest != "star":
+        pnq = pnq.copy()
+        pnq[0][cons] = tc.injections((parent, edge_r, cons_of), v[cons])
+    tree, keep, tr = _device_tree(parent, edge_r, cons[cons_of], m)
     z = lambda: torch.zeros(m, T, dtype=torch.float64, device="cuda:0")
     b, vfull, viol, part = _lists(), z(), z(), _junk((1, T, 4))
     _rows_tree(gpu_lib, m, T, tree, _up(pnq), _up(y), kadd, vfull, viol, part, b)
